@@ -23,6 +23,16 @@ of the same step, untimed and reported (`clock_priming`) -- `value`.  `--prime-m
 
 With `--gpus N > 1` and no WORLD_SIZE in the environment this process only launches the N ranks (before anything
 touches the GPU) and relays rank 0's JSON line; a failed rank makes the exit code non-zero.
+
+A plain run does only what the headline needs: set-up, `--prime-ms` of priming, the W warm-up and K timed steps, the
+result line (`value`, `ms_per_step` and the other contract keys).  `--full` adds everything else this file measures
+or checks -- the cold-clock region, the accuracy check against the CPU oracle, rooflines, the Hessian / sparse / solver /
+two-stream legs, the other configs, the CPU baseline -- and the detailed record (DETAILS_FILE).  `--only-eval`,
+`--only-hessian` and `--only-sparse` are profiling modes and run as they always did.
+
+`--dump-outputs DIR`: after the timed steps, the outputs of the last timed step (f, grad, g, jac_dense of rank 0's batch) as
+DIR/<name>.npy in the engine's precision; above DUMP_MAX_BYTES a fixed, seeded sample of the problems (the same rows of
+every array).  Inputs and weights come from fixed seeds, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -76,6 +86,7 @@ def algorithmic_work(cfg, B, m, n):
 # ------------------------------------------------------------------------------------------------------------------
 DRIVER_LINE_MAX = 4096         # bytes; tests/test_bench_line_cpu.py holds the line to it
 DETAILS_FILE = "bench_details.json"
+DUMP_MAX_BYTES = 60 << 20      # --dump-outputs: all arrays together, headers included, stay under 64 MB
 
 
 def _r(x, sig=6):
@@ -116,10 +127,11 @@ def _leg(us, rf):
     return {"us": _r(us, 5), "frac": _r(rf.get("frac"), 4), "bound": rf.get("bound")}
 
 
-def driver_line(full):
+def driver_line(full, details=True):
     """The ONE stdout line of the driver's contract, from the detailed result `full`: the contract's keys, `roofline`,
     `cpu_baseline` and one compact `summary` of the other legs (microseconds and roofline fraction each, no prose).
-    Everything else stays in DETAILS_FILE.  Strict JSON (no NaN / Infinity tokens), < DRIVER_LINE_MAX bytes."""
+    Everything else stays in DETAILS_FILE (details=False: a plain run, which writes no such file).  Strict JSON (no NaN /
+    Infinity tokens), < DRIVER_LINE_MAX bytes."""
     # (the contract's own numbers at full precision: value == n_gpus * B * steps / (ms_per_step * steps) has to hold to the bit)
     line = {k: _sanitize(full[k]) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
                                              "higher_is_better", "scaling", "vs_baseline", "dtype", "data") if k in full}
@@ -178,7 +190,8 @@ def driver_line(full):
                              if k.startswith("budget_")}
     if summ:
         line["summary"] = summ
-    line["details"] = DETAILS_FILE
+    if details:
+        line["details"] = DETAILS_FILE
     text = json.dumps(line, allow_nan=False, separators=(",", ":"))
     if len(text) >= DRIVER_LINE_MAX:          # never hand the driver an oversized line: drop the summary, keep the contract
         line["summary"] = {"dropped": "summary exceeded the line budget; see " + DETAILS_FILE}
@@ -214,6 +227,24 @@ def write_details(full, also_stderr=True, name=None):
     if also_stderr:
         sys.stderr.write("bench.py details: " + json.dumps(_sanitize(full), allow_nan=False) + "\n")
         sys.stderr.flush()
+
+
+def dump_sample(batch, bytes_per_problem, limit=DUMP_MAX_BYTES):
+    """--dump-outputs: None (every problem) when the whole batch fits `limit`, else the sorted indices of a fixed, seeded
+    sample of problems that does"""
+    if batch * bytes_per_problem <= limit:
+        return None
+    import numpy as np
+    k = max(1, (limit - 4096) // bytes_per_problem)
+    return np.sort(np.random.default_rng(0).choice(batch, size=k, replace=False))
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per output array"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def usable_cpus():
@@ -318,6 +349,8 @@ class Rank:
         import torch
         self.np, self.torch = np, torch
         self.args = args
+        # a plain run: the headline's own steps only (module docstring); the profiling modes keep their own set of legs
+        self.lean = not (args.full or args.only_eval or args.only_hessian or args.only_sparse)
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
         self.rank = int(os.environ.get("RANK", "0"))
         local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -545,20 +578,30 @@ class Rank:
                 self.barrier()
                 return self.max_over_ranks(w_), ng, last
 
-            # the same region twice: as the process finds the GPU (cold, reported next to the headline), then -- the metric
-            # is a sustained rate -- after the priming run
-            res["wall_cold"] = timed_region()[0] if args.prime_ms > 0 else None
+            # the same region twice: as the process finds the GPU (cold, reported next to the headline; --full only), then
+            # -- the metric is a sustained rate -- after the priming run
+            res["wall_cold"] = timed_region()[0] if args.prime_ms > 0 and not self.lean else None
             res["primed_ms"] = self.prime(step) if args.prime_ms > 0 else 0.0
             wall, n_gather, gathered = timed_region()
             res["wall"] = wall
-            self.region_event_s = None
-            timed_region(with_events=True)                    # the same region once more, bracketed by HIP events
-            res["t_region_events"] = self.region_event_s      # average launch-to-launch time of the timed launches
+            if args.dump_outputs:
+                # what the last timed step left in the outputs, before any other launch can overwrite them
+                per_problem = sum(outs[k][0].numel() * outs[k].element_size() for k in want)
+                idx = dump_sample(B, per_problem)
+                sel = None if idx is None else torch.as_tensor(idx, device=self.dev)
+                res["dumped"] = {k: (outs[k] if sel is None else outs[k].index_select(0, sel)).to("cpu").numpy() for k in want}
+                res["dump_sample"] = None if idx is None else [int(i) for i in idx]
+            if not self.lean:
+                self.region_event_s = None
+                timed_region(with_events=True)                    # the same region once more, bracketed by HIP events
+                res["t_region_events"] = self.region_event_s      # average launch-to-launch time of the timed launches
             res["n_gather"] = n_gather
             if gather and n_gather:
                 assert gathered.shape[0] == self.world * B
                 mine = gathered[self.rank * B:(self.rank + 1) * B]
                 assert torch.equal(mine, Z[:, H * nx:H * nx + nu]), "all-gather returned a wrong shard"
+            if self.lean:
+                return res
         else:
             for _ in range(warmup):
                 step()
@@ -750,14 +793,16 @@ class Rank:
         t = self.timed_events(fn, reps, prime_ms=0)
         return self.max_over_ranks(t) * 1e6
 
-    def emit(self, full):
-        """rank 0: detailed record to the side file and stderr, then the driver's line as the LAST stdout line"""
+    def emit(self, full, details=True):
+        """rank 0: detailed record to the side file and stderr (details=False: a plain run, the line only), then the
+        driver's line as the LAST stdout line"""
         if self.rank != 0:
             return
-        write_details(full, name=self.args.details_file)
+        if details:
+            write_details(full, name=self.args.details_file)
         sys.stdout.flush()
         os.dup2(self.saved_stdout, 1)
-        print(driver_line(full), flush=True)
+        print(driver_line(full, details), flush=True)
         os.dup2(2, 1)
 
     # -------------------------------------------------------------------------------------------------------------
@@ -780,7 +825,11 @@ class Rank:
             return
         res = self.run_config(args.config, args.steps, args.warmup, headline=True, kernel=args.kernel)
         cfg, B, eng, wall = res["cfg"], res["B"], res["eng"], res["wall"]
-        primary, secondary, rf_extra = self.roofline_of(res)
+        if args.dump_outputs and self.rank == 0:
+            write_outputs(args.dump_outputs, res["dumped"])
+            if res["dump_sample"] is not None:
+                print(f"bench.py: --dump-outputs holds {len(res['dump_sample'])} of {B} problems (seeded sample, "
+                      f"first {res['dump_sample'][:4]})", file=sys.stderr)
         out = {
             "metric": "nlp_callback_evals_per_sec (f + grad f + g + dense jac g)",
             "value": self.world * B * args.steps / wall,
@@ -792,14 +841,26 @@ class Rank:
             "config": {"workload": cfg["label"], "batch_per_gpu": B, "H": cfg["H"], "nx": cfg["nx"], "nu": cfg["nu"],
                        "hidden": cfg["hidden"], "integrator": cfg["integrator"], "n": eng.n, "m": eng.m,
                        "row_kernel": eng.kernel_variant, "parallelism": f"problem-sharded x{self.world}",
-                       # `value` is a SUSTAINED-CLOCK rate: the timed region is run once as the process finds the GPU
-                       # (value_from_cold_gpu) and again after prime_ms of the same step, untimed (value)
+                       # `value` is a SUSTAINED-CLOCK rate: the timed region runs after prime_ms of the same step, untimed
+                       # (value); --full runs it once more before that, as the process finds the GPU (value_from_cold_gpu)
                        "clock": "sustained (timed region after prime_ms of the same step)" if args.prime_ms > 0 else "cold",
                        "prime_ms": res.get("primed_ms", 0.0),
                        "value_from_cold_gpu": (self.world * B * args.steps / res["wall_cold"]) if res.get("wall_cold") else None,
                        "latency_bound_note": ("B=256 is 320 tiles on 256 CUs: launch latency, not throughput, sets the time"
                                               if B * cfg["H"] <= 16 * 2 * 256 else None)},
             "batch_evals_per_s": args.steps / wall,
+            "clock_priming": {"ms": res.get("primed_ms", 0.0),
+                              "note": "untimed run of the same step before the W warm-up steps: an idle GPU starts below its "
+                                      "sustained clock (--prime-ms 0 measures from cold)"},
+        }
+        if self.lean:
+            self.emit(out, details=False)
+            if self.dist is not None:
+                self.barrier()
+                self.dist.destroy_process_group()
+            return
+        primary, secondary, rf_extra = self.roofline_of(res)
+        out.update({
             "jacobian_max_abs_err_vs_cpu": res["errs"]["jac"], "max_abs_err_vs_cpu": res["errs"],
             "err_checked_on": f"outputs of the timed B={B} launch, problems {res['checked_slices']} (+16 each), rank {self.rank}",
             "roofline": primary,
@@ -808,10 +869,7 @@ class Rank:
             "eval_us": {"timed_loop": wall / args.steps * 1e6, "event_loop": res["t_all"] * 1e6,
                         "p10_median_p90": res["step_pcts"]},
             "value_from_cold_gpu": (self.world * B * args.steps / res["wall_cold"]) if res.get("wall_cold") else None,
-            "clock_priming": {"ms": res.get("primed_ms", 0.0),
-                              "note": "untimed run of the same step before the W warm-up steps: an idle GPU starts below its "
-                                      "sustained clock (--prime-ms 0 measures from cold)"},
-        }
+        })
         if self.dist is None and not args.only_eval:
             out["allgather_u0"] = self.single_rank_gather_latency(res)
         if self.dist is not None:
@@ -1215,8 +1273,14 @@ def main():
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=0, help="problems per GPU (default: the config's)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "valu", "mfma", "mfma_tile"])
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the C2-B256 / C3 / C5 legs of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the cold-clock region, the accuracy check against the CPU oracle, rooflines, "
+                         "the Hessian / sparse / solver / two-stream legs, the other configs, the CPU baseline and the "
+                         "detailed record (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (f, grad, g, jac_dense) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the C2-B256 / C3 / C5 legs")
     ap.add_argument("--only-eval", action="store_true",
                     help="profiling mode: the timed loop, the row-kernel timing and the accuracy check of the timed "
                          "launch only (no two-stream, solver, Hessian, other-config or CPU legs), so that a rocprofv3 "
@@ -1226,7 +1290,8 @@ def main():
     ap.add_argument("--only-sparse", action="store_true",
                     help="profiling mode: the sparse-contract leg (f, grad, g, band values in one launch) of --config only")
     ap.add_argument("--hessian", action="store_true", help="(kept for old command lines: the Hessian legs run by default)")
-    ap.add_argument("--no-hessian", action="store_true", help="skip the Hessian-callback legs (exact Lagrangian + Gauss-Newton)")
+    ap.add_argument("--no-hessian", action="store_true",
+                    help="--full: skip the Hessian-callback legs (exact Lagrangian + Gauss-Newton)")
     ap.add_argument("--evals-per-mpc-step", type=int, default=17,
                     help="N > 1: one u0 all-gather per this many callback evaluations inside the timed loop")
     ap.add_argument("--prime-ms", type=float, default=40.0,
@@ -1237,6 +1302,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.only_hessian or args.only_sparse):
+        raise SystemExit("--dump-outputs writes the headline's outputs; --only-hessian / --only-sparse do not run it")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launcher role: nothing above this line has touched HIP (torch is not even imported yet)
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))

@@ -119,3 +119,22 @@ def test_details_file_round_trip(tmp_path, monkeypatch):
     bench.write_details(full, also_stderr=False)
     back = strict_loads(open(tmp_path / bench.DETAILS_FILE).read())
     assert back["metric"] == full["metric"] and back["roofline"]["frac"] == full["roofline"]["frac"]
+
+
+def test_plain_run_line_has_the_contract_keys_and_no_side_file_reference():
+    """a plain run's record (no roofline, CPU baseline or legs) still makes a strict line with the headline's keys"""
+    full = {k: v for k, v in canned().items() if k in CONTRACT and k not in ("roofline", "cpu_baseline")}
+    line = strict_loads(bench.driver_line(full, details=False))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert line[k] == full[k], k
+    assert "details" not in line and "summary" not in line and "roofline" not in line
+    assert strict_loads(bench.driver_line(full))["details"] == bench.DETAILS_FILE
+
+
+def test_dump_sample_is_seeded_and_fits_the_budget():
+    """--dump-outputs: the whole batch when it fits, else the same seeded sample of problems on every run"""
+    assert bench.dump_sample(1024, 20_000) is None               # the headline: B = 1024, ~20 KB of outputs per problem
+    a, b = bench.dump_sample(1024, 250_000), bench.dump_sample(1024, 250_000)
+    assert a is not None and list(a) == list(b)
+    assert 0 < len(a) * 250_000 + 4096 <= bench.DUMP_MAX_BYTES < 64_000_000
+    assert all(x < y for x, y in zip(a[:-1], a[1:])) and 0 <= a[0] and a[-1] < 1024

@@ -125,7 +125,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     import tempfile
     with tempfile.TemporaryDirectory() as cwd:
         r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "34", "--warmup", "3",
-                            "--batch", "64", "--no-cpu", "--no-other-configs", "--no-hessian", "--prime-ms", "0",
+                            "--batch", "64", "--full", "--no-cpu", "--no-other-configs", "--no-hessian", "--prime-ms", "0",
                             "--solver-iters", "10"], capture_output=True, text=True, env=env, timeout=600, cwd=cwd)
         assert r.returncode == 0, r.stderr[-2000:]
         details = json.load(open(os.path.join(cwd, "bench_details.json")))      # the detailed record (side file)
@@ -144,6 +144,46 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     assert details["batched_solver"]["gathered_rows"] == 128
     assert out["jacobian_max_abs_err_vs_cpu"] < 1e-12
     assert out["roofline"]["frac"] > 0 and "FUSE = true" in out["roofline"]["kernel"]
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_outputs():
+    """A plain `bench.py` run: the contract's keys with `steps` timed steps behind `ms_per_step`, no side file, and
+    --dump-outputs holding the timed launch's own outputs (checked here against the CPU oracle on seeded inputs)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import tempfile
+    import numpy as np
+    from oracle import nempc_oracle as orc
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    with tempfile.TemporaryDirectory() as cwd:
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--dump-outputs", "dump"], capture_output=True, text=True, env=env, timeout=300, cwd=cwd)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert not os.path.exists(os.path.join(cwd, "bench_details.json"))
+        got = {k: np.load(os.path.join(cwd, "dump", k + ".npy")) for k in ("f", "grad", "g", "jac_dense")}
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and r.stdout.rstrip().endswith(lines[0]), r.stdout[-2000:]
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 7 and out["warmup"] == 2 and out["dtype"] == "f64" and out["higher_is_better"] is True
+    B = out["config"]["batch_per_gpu"]
+    assert abs(out["value"] - B * 7 / (out["ms_per_step"] * 7 * 1e-3)) / out["value"] < 1e-9
+    assert "roofline" not in out and "details" not in out
+    # the headline workload (bench.CONFIGS["c2"]): weights of seed 0, inputs of seed 1
+    net = orc.MLP.random(3, [64, 64], 2, seed=0)
+    prob = orc.Problem(net, 20, 2, 1, orc.DISCRET, 1.0)
+    Z, X0 = orc.synthetic_inputs(B, 20, 2, 1, seed=1)
+    assert got["jac_dense"].shape == (B, prob.m, prob.n) and all(a.dtype == np.float64 for a in got.values())
+    for sl in (slice(0, 8), slice(B - 8, B)):
+        f, grad, g, jac = prob.eval_batch(Z[sl], X0[sl])
+        for name, ref in (("f", f), ("grad", grad), ("g", g), ("jac_dense", jac)):
+            np.testing.assert_allclose(got[name][sl], ref, rtol=1e-12, atol=1e-12, err_msg=name)
 
 
 _TWO_RANK_WORKER = r'''

@@ -8,10 +8,10 @@ set -e -o pipefail
 TAG=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
-python3 bench.py --hessian --steps 200 --warmup 20 > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+python3 bench.py --full --hessian --steps 200 --warmup 20 > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
 echo "bench default done"
 for cfg in c3 c5; do
-  python3 bench.py --config $cfg --hessian --steps 100 --warmup 10 --no-cpu > $O/${TAG}_bench_${cfg}.json 2> $O/${TAG}_bench_${cfg}.err
+  python3 bench.py --full --config $cfg --hessian --steps 100 --warmup 10 --no-cpu > $O/${TAG}_bench_${cfg}.json 2> $O/${TAG}_bench_${cfg}.err
   echo "bench $cfg done"
 done
 # enough timed steps that the clock-priming launches of bench.py (40 ms per timing loop, in synchronised batches of 16)

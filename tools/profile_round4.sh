@@ -9,12 +9,12 @@ TAG=${1:-r04}; PART=${2:-all}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
 if [ "$PART" = bench ] || [ "$PART" = all ]; then
-  python3 bench.py --steps 200 --warmup 20 > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+  python3 bench.py --full --steps 200 --warmup 20 > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
   echo "bench default done"
-  python3 bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_driver_form.json 2> $O/${TAG}_bench_driver_form.err
+  python3 bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_driver_form.json 2> $O/${TAG}_bench_driver_form.err
   echo "bench driver form done"
   for cfg in c3 c5; do
-    python3 bench.py --config $cfg --steps 100 --warmup 10 --no-cpu > $O/${TAG}_bench_${cfg}.json 2> $O/${TAG}_bench_${cfg}.err
+    python3 bench.py --full --config $cfg --steps 100 --warmup 10 --no-cpu > $O/${TAG}_bench_${cfg}.json 2> $O/${TAG}_bench_${cfg}.err
     echo "bench $cfg done"
   done
 fi
