@@ -1325,7 +1325,10 @@ int run_layered(Handle& h, int B, const void* Zv, const void* X0v, void* gv, voi
             const T cdt = st == 0 ? T(0) : (st == 3 ? DT : T(0.5) * DT);
             const bool fuse_out = layered_fuse();
             static const bool outskip = [] { const char* e = getenv("NEMPC_LAYERED_OUTSKIP"); return !(e && atoi(e) == 0); }();      // (A/B, tested)
-            const bool lin_skip = outskip && fuse_out && nl >= 3 && !rk4 && h.act[nl - 1] == NEMPC_ACT_LINEAR;
+            // (only where the partial sums -- nx rows per 64-feature block -- fit the spare activation buffer of maxw rows: a
+            // network narrower than its state would write past it into x1 and the s' slots)
+            const bool lin_skip = outskip && fuse_out && nl >= 3 && !rk4 && h.act[nl - 1] == NEMPC_ACT_LINEAR &&
+                                  (h.dout[nl - 2] + 63) / 64 * nx <= h.maxw;
             // gather + layer 0 in one vector-unit launch (layered_first_kernel): few inputs, two hidden layers or more (layer 0 is
             // not the layer the output contraction leaves from), Discret / Unity (the RK4 stages' inputs carry c DT k_{s-1} and
             // their records want xi)

@@ -763,6 +763,10 @@ def test_every_matrix_core_instantiation_with_its_hessian_against_the_oracle():
     ([150], ["swish", "linear"], 2, 2, "unity"),
     ([140, 90], ["mish", "softsign", "linear"], 2, 1, "discret"),
     ([100, 100, 60], ["exponential", "relu6", "mish", "tanh"], 3, 1, "rk4"),
+    # bottleneck widths (hidden layers narrower than the state) on the route AUTO gives these activations
+    ([8, 8], ["swish", "gelu", "linear"], 12, 1, "discret"),
+    ([4, 4, 4], ["mish", "softsign", "relu6", "linear"], 16, 4, "unity"),
+    ([6, 5], ["gelu", "exponential", "tanh"], 7, 1, "discret"),              # non-linear output: layered_outfinish_kernel
 ])
 def test_layered_matrix_core_path_against_the_oracle(dtype, hidden, acts, nx, nu, integ):
     """Networks outside the register-resident kernels (width > 128, more than three hidden layers, per-layer activation
@@ -850,10 +854,21 @@ def test_layered_matrix_core_path_against_the_oracle(dtype, hidden, acts, nx, nu
     ([40] * 7, 2, 1, "rk4", 4, 5),                   # eight dense layers
     ([72, 72], 3, 1, "unity", 1, 1),                 # one row
     ([130], 5, 4, "rk4", 2, 70),                     # one hidden layer, more rows than one GEMM block
+    # bottleneck widths: the widest hidden layer narrower than nx, nin or one 16-deep K chunk.  A linear output layer's
+    # partial sums (ceil(w / 64) * nx rows) only fit the activation buffer (max width rows) while that is >= nx
+    ([8, 8], 12, 1, "discret", 5, 70),               # 12 rows of partial sums, 8 in the buffer
+    ([6, 6], 7, 1, "unity", 5, 70),                  # nin = 8: layer 0 in layered_first_kernel
+    ([4, 4, 4], 16, 4, "discret", 3, 70),            # three hidden layers of 4 behind 20 inputs
+    ([1, 1], 2, 1, "unity", 4, 9),                   # width 1
+    ([11, 11], 12, 1, "discret", 4, 9),              # one row over the fit ...
+    ([12, 12], 12, 1, "discret", 4, 9),              # ... and exactly on it
+    ([8, 8], 12, 1, "rk4", 4, 9),                    # the RK4 rows and the RK4 Hessian pipeline at a bottleneck width
+    ([3], 16, 16, "discret", 3, 9),                  # one hidden layer narrower than nx, nin = 32
 ])
 def test_layered_path_at_the_edges_of_its_shape_range(hidden, nx, nu, integ, H, B):
-    """The layered path's limits (widths <= 1024, <= 8 layers, <= 32 network inputs, nx <= 16) and its smallest launches:
-    rows and Lagrangian blocks against the oracle."""
+    """The layered path's limits (widths <= 1024, <= 8 layers, <= 32 network inputs, nx <= 16), its smallest launches and
+    networks narrower than their state: rows (every problem of the batch, g, dense Jacobian and tiles) and Lagrangian blocks
+    against the oracle."""
     from pyneuralempc_amd import CallbackEngine
     DT = 0.1 if integ == "rk4" else 1.0
     kind = {"discret": orc.DISCRET, "unity": orc.UNITY, "rk4": orc.RK4}[integ]
@@ -863,17 +878,79 @@ def test_layered_path_at_the_edges_of_its_shape_range(hidden, nx, nu, integ, H, 
                          kernel="layered")
     assert eng.kernel_variant == "layered"
     Zh, X0h = orc.synthetic_inputs(B, H, nx, nu, seed=4)
-    res = eng.eval_numpy(Zh, X0h, want=("g", "jac_dense"))
-    k = min(B, 3)
-    f, grad, g, J = prob.eval_batch(Zh[:k], X0h[:k])
-    np.testing.assert_allclose(res["g"][:k], g, rtol=1e-10, atol=1e-10)
-    np.testing.assert_allclose(res["jac_dense"][:k], J, rtol=1e-10, atol=1e-10)
+    res = eng.eval_numpy(Zh, X0h, want=("g", "jac_dense", "jac_tiles"))
+    assert eng.last_row_kernel == "layered_gemm_kernel"
+    f, grad, g, J = prob.eval_batch(Zh, X0h)
+    np.testing.assert_allclose(res["g"], g, rtol=1e-10, atol=1e-10)
+    np.testing.assert_allclose(res["jac_dense"], J, rtol=1e-10, atol=1e-10)
+    for i in range(B):
+        _, A, Bt = prob.tiles_AB(Zh[i], X0h[i])
+        np.testing.assert_allclose(res["jac_tiles"][i][:, :, :nx], A, rtol=1e-10, atol=1e-10)
+        np.testing.assert_allclose(res["jac_tiles"][i][:, :, nx:], Bt, rtol=1e-10, atol=1e-10)
     lam = np.random.default_rng(2).normal(size=(B, eng.m))
     hv = eng.hess(eng.to_device(Zh), eng.to_device(X0h), eng.to_device(lam), eng.to_device(np.ones(B)))["hvals"].cpu().numpy()
-    assert eng.last_hess_kernel.endswith("layered_gemm_kernel")
-    for i in range(min(B, 2)):
+    assert eng.last_hess_kernel == ("rk4:layered_gemm_kernel" if integ == "rk4" else "layered_gemm_kernel")
+    for i in range(B):
         ref = prob.hessian_values(Zh[i], X0h[i], lam[i], 1.0)
         np.testing.assert_allclose(hv[i], ref, rtol=0, atol=1e-9 * max(1.0, np.abs(ref).max()))
+
+
+@pytest.mark.parametrize("hidden,acts,nx,nu,ne,window,integ", [
+    ([4, 4], "tanh", 5, 1, 2, 1, "discret"),         # nin + ne = 8: layered_first_kernel
+    ([4, 4], "tanh", 5, 1, 3, 1, "unity"),           # 9: the gather launch
+    ([2, 2], "swish", 3, 1, 0, 2, "discret"),        # rolling window, nin = 8
+    ([5, 5], "tanh", 3, 1, 1, 2, "discret"),         # rolling window with a parameter, 9
+])
+def test_layered_path_bottleneck_widths_with_extra_inputs_and_rolling_windows(hidden, acts, nx, nu, ne, window, integ):
+    """Hidden layers narrower than the state behind the layered path's input gather: extra network inputs (one set per
+    problem) and rolling windows (one history per problem), on both sides of the first-layer kernel's input limit.  Rows,
+    Lagrangian blocks and the Gauss-Newton callback of every problem against the oracle, and against the generic kernel."""
+    from pyneuralempc_amd import CallbackEngine
+    H, B = 6, 12                                     # 72 rows: more than one 64-row block
+    kind = {"discret": orc.DISCRET, "unity": orc.UNITY}[integ]
+    box = (-2.0, 2.0)
+    rng = np.random.default_rng(17)
+    net = orc.MLP.random(window * (nx + nu) + ne, hidden, nx, seed=6, activations=acts)
+    Zh, X0h = orc.synthetic_inputs(B, H, nx, nu, seed=9)
+    ex = rng.normal(size=(B, H, ne)) if ne else None
+    hx, hu = (rng.normal(size=(B, window - 1, nx)), rng.uniform(-1, 1, size=(B, window - 1, nu))) if window > 1 else (None, None)
+    lamh, sigh, wh = rng.normal(size=(B, 2 * H * nx)), rng.uniform(0.5, 1.5, size=B), rng.uniform(0.2, 1.5, size=(B, H * nx))
+    probs = [orc.Problem(net, H, nx, nu, kind, box=box, extra=None if ex is None else ex[i], window=window,
+                         hist_x=None if hx is None else hx[i], hist_u=None if hu is None else hu[i]) for i in range(B)]
+    g = np.stack([p.constraints(Zh[i], X0h[i]) for i, p in enumerate(probs)])
+    jac = np.stack([p.jacobian(Zh[i], X0h[i]) for i, p in enumerate(probs)])
+    hv = np.stack([p.hessian_values(Zh[i], X0h[i], lamh[i], sigh[i]) for i, p in enumerate(probs)])
+    gn = np.stack([p.gauss_newton_values(Zh[i], X0h[i], wh[i], sigh[i]) for i, p in enumerate(probs)])
+    out = {}
+    for kernel in ("layered", "valu"):
+        eng = CallbackEngine(net.W, net.b, H, nx, nu, integrator=integ, dtype=torch.float64, device="cuda:0", max_batch=B,
+                             kernel=kernel, n_extra=ne, rolling_window=window, activations=net.act)
+        assert eng.kernel_variant == kernel
+        rows_k = {"layered": "layered_gemm_kernel", "valu": "rows_valu_kernel"}[kernel]
+        eng.set_box_rows(*box)
+        if ex is not None:
+            eng.bind_extra(eng.to_device(ex))
+        if hx is not None:
+            eng.bind_history(eng.to_device(hx), eng.to_device(hu))
+        Z, X0 = eng.to_device(Zh), eng.to_device(X0h)
+        res = eng.eval(Z, X0, ("g", "jac_dense"))
+        assert eng.last_row_kernel == rows_k
+        r = {k: res[k].cpu().numpy() for k in ("g", "jac_dense")}
+        r["hess"] = eng.hess(Z, X0, eng.to_device(lamh), eng.to_device(sigh))["hvals"].cpu().numpy()
+        assert eng.last_hess_kernel == {"layered": "layered_gemm_kernel", "valu": "rowhess_valu_kernel"}[kernel]
+        r["gn"] = eng.hess_gn(Z, X0, eng.to_device(wh), eng.to_device(sigh))["hvals"].cpu().numpy()
+        assert eng.last_row_kernel == rows_k
+        np.testing.assert_allclose(r["g"], g, rtol=1e-11, atol=1e-11)
+        np.testing.assert_allclose(r["jac_dense"], jac, rtol=1e-11, atol=1e-11)
+        np.testing.assert_allclose(r["hess"], hv, rtol=0, atol=1e-9 * max(1.0, np.abs(hv).max()))
+        np.testing.assert_allclose(r["gn"], gn, rtol=1e-11, atol=1e-11)
+        out[kernel] = r
+        del eng
+    lay, gen = out["layered"], out["valu"]
+    np.testing.assert_allclose(lay["g"], gen["g"], rtol=1e-11, atol=1e-11)
+    np.testing.assert_allclose(lay["jac_dense"], gen["jac_dense"], rtol=1e-11, atol=1e-11)
+    np.testing.assert_allclose(lay["hess"], gen["hess"], rtol=0, atol=1e-10 * max(1.0, np.abs(gen["hess"]).max()))
+    np.testing.assert_allclose(lay["gn"], gen["gn"], rtol=1e-11, atol=1e-11)
 
 
 @pytest.mark.parametrize("hidden,acts,nx,nu,integ", [
@@ -928,13 +1005,17 @@ from pyneuralempc_amd import CallbackEngine
 out = {}
 for tag, hidden, acts, nx, nu, integ in (("a", [200, 136], ["tanh", "sigmoid", "linear"], 2, 1, "discret"), ("b", [144], "tanh", 3, 2, "rk4"),
                                          ("c", [136, 150, 72], ["tanh", "softplus", "relu", "linear"], 2, 2, "rk4"),
-                                         ("d", [160, 130], "tanh", 1, 1, "unity")):
+                                         ("d", [160, 130], "tanh", 1, 1, "unity"),
+                                         ("e", [8, 8], "tanh", 12, 1, "discret"),             # (bottleneck widths: narrower than nx)
+                                         ("f", [4, 4, 4], ["swish", "tanh", "gelu", "linear"], 16, 4, "unity")):
     H, B, DT = 6, 90, (0.1 if integ == "rk4" else 1.0)
     net = orc.MLP.random(nx + nu, hidden, nx, seed=5, activations=acts)
     eng = CallbackEngine(net.W, net.b, H, nx, nu, integrator=integ, DT=DT, dtype=torch.float64, device="cuda:0", max_batch=B,
                          activations=net.act, kernel="layered")
+    assert eng.kernel_variant == "layered"
     Zh, X0h = orc.synthetic_inputs(B, H, nx, nu, seed=6)
     r = eng.eval_numpy(Zh, X0h, want=("g", "jac_tiles"))
+    out[tag + "_rk"] = np.array([eng.last_row_kernel])
     lam = np.random.default_rng(2).normal(size=(B, eng.m))
     hv = eng.hess(eng.to_device(Zh), eng.to_device(X0h), eng.to_device(lam), eng.to_device(np.ones(B)))["hvals"].cpu().numpy()
     out[tag + "_g"], out[tag + "_J"], out[tag + "_H"] = r["g"], r["jac_tiles"], hv
@@ -953,7 +1034,7 @@ def test_layered_path_run_time_switches_agree_with_the_default(tmp_path):
     product for layer 0 instead of layered_first_kernel), NEMPC_LAYERED_OUTSKIP=0 (a linear output layer's partial sums through
     layered_outfinish_kernel instead of the finish kernel) -- are read once per process: each runs in a process of
     its own and has to reproduce the default's rows and Lagrangian blocks to rounding (round-4 review: switches nobody tests
-    are build variants nobody knows)."""
+    are build variants nobody knows), on wide networks and on networks narrower than their state (e, f)."""
     import os
     import subprocess
     import sys
@@ -974,9 +1055,13 @@ def test_layered_path_run_time_switches_agree_with_the_default(tmp_path):
         res[name] = dict(np.load(out))
     ref = res["default"]
     for name, got in res.items():
-        for k in [t + sfx for t in "abcd" for sfx in ("_g", "_J", "_H")]:
+        for k in [t + sfx for t in "abcdef" for sfx in ("_g", "_J", "_H")]:
             np.testing.assert_allclose(got[k], ref[k], rtol=0, atol=1e-11 * max(1.0, np.abs(ref[k]).max()), err_msg=f"{name}/{k}")
-    assert str(ref["a_hk"][0]) == "layered_gemm_kernel" and str(res["nohess"]["a_hk"][0]) == "rowhess_valu_kernel"    # (the switch did switch)
+        for t in "abcdef":
+            assert str(got[t + "_rk"][0]) == "layered_gemm_kernel", (name, t)
+    for t in "aef":
+        assert str(ref[t + "_hk"][0]) == "layered_gemm_kernel", t
+    assert str(res["nohess"]["a_hk"][0]) == "rowhess_valu_kernel"    # (the switch did switch)
 
 
 def test_layered_path_chunks_large_batches():

@@ -12,9 +12,12 @@ ACTS = ["tanh", "relu", "sigmoid", "softplus", "elu", "elu:0.6", "leaky_relu:0.1
         "exponential", "relu6", "linear"]
 bad = 0
 for case in range(N):
-    nx, nu = int(rng.integers(1, 7)), int(rng.integers(1, 5))
+    # nx up to the path's 16 (nin = nx + nu <= 20 of its 32); widths from 1, every other case narrower than nx (nx = 1: width
+    # 1), so that networks narrower than their state, their inputs or one 16-deep K chunk come up as often as wide ones
+    nx, nu = int(rng.integers(1, 17)), int(rng.integers(1, 5))
     nl_h = int(rng.integers(1, 6))
-    hidden = [int(rng.integers(5, 300)) for _ in range(nl_h)]
+    wmax = max(nx, 2) if rng.integers(0, 2) else 300
+    hidden = [int(rng.integers(1, wmax)) for _ in range(nl_h)]
     integ = ["discret", "unity", "rk4"][int(rng.integers(0, 3))]
     H, B = int(rng.integers(1, 9)), int(rng.integers(1, 40))
     acts = [ACTS[int(rng.integers(0, len(ACTS)))] for _ in range(nl_h)]
