@@ -911,7 +911,7 @@ void launch_first(int act, int K, dim3 grid, hipStream_t s, Args... args) {
 }
 // NEMPC_LAYERED_FIRST=0: gather launch + one-chunk GEMM launch for layer 0, as before (A/B; tested against the default)
 bool lg_first_on() {
-    static const bool on = [] { const char* e = getenv("NEMPC_LAYERED_FIRST"); return !(e && atoi(e) == 0); }();
+    static const bool on = env_enabled("NEMPC_LAYERED_FIRST");
     return on;
 }
 
@@ -1182,7 +1182,7 @@ int gemm_ft(hipStream_t s, const GemmArgs& a) {
     b.dbg = nullptr;
 #ifdef NEMPC_STAMPS
     {
-        static const int sel = [] { const char* e = getenv("NEMPC_LG_STAMP"); return e ? atoi(e) : 11; }();
+        static const int sel = env_int("NEMPC_LG_STAMP", 11);
         if (sel == 10 * (int)SEED + CONTRACT) b.dbg = g_lg_dbg;
     }
 #endif
@@ -1192,7 +1192,7 @@ int gemm_ft(hipStream_t s, const GemmArgs& a) {
     long long groups = (mblk + 7) / 8;
     b.ncot = 1; b.rbc = 0; b.ncot_magic = 0;
     constexpr bool il = CONTRACT == LG_CONTRACT_HPAIR;
-    static const bool cot_order = [] { const char* e = getenv("NEMPC_LG_COT_ORDER"); return !(e && atoi(e) == 0); }();
+    static const bool cot_order = env_enabled("NEMPC_LG_COT_ORDER");
     if (cot_order && !il && (SEED || a.mode == LG_REVERSE) && a.Rmod > 0 && a.Rmod % S::BM == 0 && a.M % a.Rmod == 0 && a.M / a.Rmod > 1) {
         b.ncot = (int)(a.M / a.Rmod);
         b.rbc = (int)(a.Rmod / S::BM);
@@ -1213,7 +1213,7 @@ int gemm_ft(hipStream_t s, const GemmArgs& a) {
 // already; the contraction form measured 9 % slower).  NEMPC_LG_RM = 2 | 4 forces one form (A/B, tests).
 template <typename T>
 bool lg_rows32(int num_cus, long long M, int N) {
-    static const int rm_env = [] { const char* e = getenv("NEMPC_LG_RM"); return e ? atoi(e) : 0; }();
+    static const int rm_env = env_int("NEMPC_LG_RM", 0);
     if (rm_env == 2) return true;
     if (rm_env == 4 || sizeof(T) != 8) return false;
     const long long tiles64 = ((M + 63) / 64) * (long long)((N + 63) / 64);
@@ -1243,10 +1243,7 @@ int gemm(int num_cus, hipStream_t s, int mode, int act, const T* A, long long ld
 // The fused forms of the reverse sweep (64-feature blocks only): NEMPC_LAYERED_FUSE=0 walks it with the seed kernel, plain
 // products and the skinny last step instead (A/B knob)
 bool layered_fuse() {
-    static const bool on = [] {
-        const char* e = getenv("NEMPC_LAYERED_FUSE");
-        return !(e && atoi(e) == 0);
-    }();
+    static const bool on = env_enabled("NEMPC_LAYERED_FUSE");
     return on;
 }
 
@@ -1254,20 +1251,20 @@ bool layered_fuse() {
 // form them from the activation in the Hessian sweeps and, with three or more hidden layers, in the rows path; 2 everywhere
 // (A/B; each tested against the default)
 int lg_dfa_on() {
-    static const int on = [] {
-        const char* e = getenv("NEMPC_LAYERED_DFA");
-        return e ? atoi(e) : 1;
-    }();
+    static const int on = env_int("NEMPC_LAYERED_DFA", 1);
     return on;
 }
 
 // NEMPC_LAYERED_HFOLD=0: the Hessian's tangents are written and contracted by layered_hcontract_kernel, as in round 4 (A/B,
 // tested against the default)
 bool lg_hfold_on() {
-    static const bool on = [] {
-        const char* e = getenv("NEMPC_LAYERED_HFOLD");
-        return !(e && atoi(e) == 0);
-    }();
+    static const bool on = env_enabled("NEMPC_LAYERED_HFOLD");
+    return on;
+}
+
+// NEMPC_LAYERED_OUTSKIP=0: a linear output layer is always formed as a product of its own (A/B, tested)
+bool lg_outskip_on() {
+    static const bool on = env_enabled("NEMPC_LAYERED_OUTSKIP");
     return on;
 }
 
@@ -1283,7 +1280,7 @@ template <typename T>
 int gemm_reverse_fused(hipStream_t s, const GemmArgs& a, bool seed, bool last) {
     // (A/B, NEMPC_LG_RM_REV=2: the seed + contraction product on 32-row blocks measured 7 - 11 % slower -- 2 x 256, B*H = 20480:
     // 257 -> 274 us per evaluation in fp64, 136 -> 151 in fp32 -- so the reverse products keep the 64-row block)
-    static const int rm_env = [] { const char* e = getenv("NEMPC_LG_RM_REV"); return e ? atoi(e) : 0; }();
+    static const int rm_env = env_int("NEMPC_LG_RM_REV", 0);
     if (rm_env == 2 && seed && last) return gemm_ft<T, 1, true, LG_CONTRACT_REVERSE, 2>(s, a);
     if (seed && last) return gemm_ft<T, 1, true, LG_CONTRACT_REVERSE>(s, a);
     if (seed) return gemm_ft<T, 1, true, LG_CONTRACT_NONE>(s, a);
@@ -1324,10 +1321,9 @@ int run_layered(Handle& h, int B, const void* Zv, const void* X0v, void* gv, voi
         for (int st = 0; st < nstages; ++st) {
             const T cdt = st == 0 ? T(0) : (st == 3 ? DT : T(0.5) * DT);
             const bool fuse_out = layered_fuse();
-            static const bool outskip = [] { const char* e = getenv("NEMPC_LAYERED_OUTSKIP"); return !(e && atoi(e) == 0); }();      // (A/B, tested)
             // (only where the partial sums -- nx rows per 64-feature block -- fit the spare activation buffer of maxw rows: a
             // network narrower than its state would write past it into x1 and the s' slots)
-            const bool lin_skip = outskip && fuse_out && nl >= 3 && !rk4 && h.act[nl - 1] == NEMPC_ACT_LINEAR &&
+            const bool lin_skip = lg_outskip_on() && fuse_out && nl >= 3 && !rk4 && h.act[nl - 1] == NEMPC_ACT_LINEAR &&
                                   (h.dout[nl - 2] + 63) / 64 * nx <= h.maxw;
             // gather + layer 0 in one vector-unit launch (layered_first_kernel): few inputs, two hidden layers or more (layer 0 is
             // not the layer the output contraction leaves from), Discret / Unity (the RK4 stages' inputs carry c DT k_{s-1} and
@@ -1768,8 +1764,7 @@ int run_layered_hess(Handle& h, int B, const void* Zv, const void* X0v, const vo
         const dim3 rb(256), rg((unsigned)((R + 255) / 256));
         // ---- forward, every layer's s' and s'' kept
         const bool first = lg_first_on() && !stage && nl - 1 >= 2 && nin + ne <= LG_FIRST_KMAX;        // (see run_layered)
-        static const bool outskip = [] { const char* e = getenv("NEMPC_LAYERED_OUTSKIP"); return !(e && atoi(e) == 0); }();
-        const bool lin_noout = outskip && lin_out;
+        const bool lin_noout = lg_outskip_on() && lin_out;
         if (stage)
             hipLaunchKernelGGL(layered_hgather_direct_kernel<T>, rg, rb, 0, s, stage, stage_stride, nin, ne, static_cast<const T*>(h.d_extra),
                                r0, R, Rp, ws + o.xi);
@@ -1931,6 +1926,9 @@ bool layered_supported(const Handle& h) {
     return true;
 }
 
+// NEMPC_LAYERED_CHUNK_ROWS: rows per chunk of both workspaces below (tests of the chunk loop; read at every sizing)
+static int layered_chunk_rows_env() { return env_int("NEMPC_LAYERED_CHUNK_ROWS", 0); }
+
 // chunk workspace: rows per chunk so that the whole workspace stays near 6 GB (of 288), between 4096 and 65536 rows -- the
 // larger the products, the smaller the share of their launch tails (4 x 512, 6/3, B*H = 30720 in fp64 is one chunk of 2.3 GB)
 int layered_prepare(Handle& h) {
@@ -1939,10 +1937,7 @@ int layered_prepare(Handle& h) {
     size_t rc_rows = ((size_t)6144 << 20) / (per.total * h.esz);
     if (rc_rows > 65536) rc_rows = 65536;
     if (rc_rows < 4096) rc_rows = 4096;
-    if (const char* e = getenv("NEMPC_LAYERED_CHUNK_ROWS")) {     // (tests of the chunk loop)
-        const long long v = atoll(e);
-        if (v > 0) rc_rows = (size_t)v;
-    }
+    if (const int v = layered_chunk_rows_env(); v > 0) rc_rows = (size_t)v;
     if (rc_rows > cap) rc_rows = cap;
     rc_rows = (rc_rows + LG_BM - 1) / LG_BM * LG_BM;
     if (h.d_layered_ws && h.layered_chunk_rows == (long long)rc_rows) return NEMPC_OK;
@@ -1974,10 +1969,7 @@ int layered_hess_prepare(Handle& h) {
     size_t rc_rows = ((size_t)6144 << 20) / (per.total * h.esz);
     if (rc_rows > 65536) rc_rows = 65536;
     if (rc_rows < 4096) rc_rows = 4096;
-    if (const char* e = getenv("NEMPC_LAYERED_CHUNK_ROWS")) {     // (tests of the chunk loop)
-        const long long v = atoll(e);
-        if (v > 0) rc_rows = (size_t)v;
-    }
+    if (const int v = layered_chunk_rows_env(); v > 0) rc_rows = (size_t)v;
     if (rc_rows > cap) rc_rows = cap;
     rc_rows = (rc_rows + LG_BM - 1) / LG_BM * LG_BM;
     if (h.d_layered_hws && h.layered_hess_chunk_rows == (long long)rc_rows) return NEMPC_OK;
@@ -2017,7 +2009,7 @@ int layered_reserve(Handle& h) {
 // Lagrangian blocks on the GEMM path: Discret / Unity directly, RK4 through the stage pipeline of kernels_rk4hess.hip.
 // NEMPC_EUNSUPPORTED: a nonlinear output layer behind a single hidden layer, NEMPC_LAYERED_HESS=0 (A/B knob).
 static bool layered_hess_usable(const Handle& h) {
-    static const bool off = [] { const char* e = getenv("NEMPC_LAYERED_HESS"); return e && atoi(e) == 0; }();
+    static const bool off = !env_enabled("NEMPC_LAYERED_HESS");
     if (off || !(h.layered || h.layered_hess)) return false;
     return h.nl >= 2 && !(h.nl == 2 && h.act[h.nl - 1] != NEMPC_ACT_LINEAR);
 }

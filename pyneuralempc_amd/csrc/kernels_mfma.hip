@@ -275,7 +275,7 @@ int launch_eval_fused(Handle& h, int B, const void* Z, const void* X0, void* g, 
 // NEMPC_EUNSUPPORTED (nothing launched, no error message) sends nempc_eval to the row + assembly launches.
 int launch_rows_mfma_sparse(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* sparse, void* f,
                             void* grad, hipStream_t s) {
-    static const int on = [] { const char* e = getenv("NEMPC_COOP_SPARSE"); return e ? atoi(e) : 1; }();
+    static const int on = env_int("NEMPC_COOP_SPARSE", 1);
     if (!on || !h.mfma.blob || !sparse || h.w != 1 || ((f || grad) && !h.d_obj)) return NEMPC_EUNSUPPORTED;
     MfmaParams p = base_params(h, B, Z, X0, g, tiles);
     p.fuse_sparse = sparse; p.sp_nnz = (int)h.jac_rows.size();
@@ -293,7 +293,7 @@ int launch_rows_mfma_sparse(Handle& h, int B, const void* Z, const void* X0, voi
 // rolling windows, and when the Hessian map has no scatter form.
 int launch_hess_gn_fused(Handle& h, int B, const void* Z, const void* X0, const void* w, const void* sigma, void* hvals,
                          hipStream_t s) {
-    static const int on = [] { const char* e = getenv("NEMPC_GN_FUSED"); return e ? atoi(e) : 1; }();
+    static const int on = env_int("NEMPC_GN_FUSED", 1);
     if (!on || !h.mfma.blob || !hvals || h.w != 1 || !h.d_hess_smap || h.hess_n_orph < 0 || h.cfg.dtype != NEMPC_F64)
         return NEMPC_EUNSUPPORTED;
     MfmaParams p = base_params(h, B, Z, X0, h.d_g_ws, nullptr);
@@ -308,7 +308,7 @@ int launch_hess_gn_fused(Handle& h, int B, const void* Z, const void* X0, const 
 // NEMPC_EUNSUPPORTED (nothing launched, no error message) sends nempc_eval to the row + assembly launches.
 int launch_rows_mfma_dense(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* jac, void* f,
                            void* grad, hipStream_t s) {
-    static const int on = [] { const char* e = getenv("NEMPC_COOP_DENSE"); return e ? atoi(e) : 1; }();
+    static const int on = env_int("NEMPC_COOP_DENSE", 1);
     if (!on || !h.mfma.blob || !jac || ((f || grad) && !h.d_obj)) return NEMPC_EUNSUPPORTED;
     MfmaParams p = base_params(h, B, Z, X0, g, tiles);
     p.fuse_jac = jac;
@@ -381,7 +381,7 @@ int launch_rowhess_mfma_hvals(Handle& h, int B, const void* Z, const void* X0, c
 // fixed-shape Hessian kernel -- the batched solver's trial point.  NEMPC_EUNSUPPORTED (nothing launched) for other shapes.
 int launch_rowhess_eval_mfma(Handle& h, int B, const void* Z, const void* X0, const void* lambda, void* blocks, void* g,
                              void* tiles, hipStream_t s) {
-    static const int on = [] { const char* e = getenv("NEMPC_HFX_EVAL"); return e ? atoi(e) : 1; }();
+    static const int on = env_int("NEMPC_HFX_EVAL", 1);
     if (!on || !h.mfma.blob || h.w != 1 || h.ne != 0 || !blocks || !g || !tiles) return NEMPC_EUNSUPPORTED;
     return launch_rowhess_mfma_direct(h, B, Z, X0, lambda, blocks, nullptr, 0, nullptr, 1, s, nullptr, nullptr, g, tiles);
 }

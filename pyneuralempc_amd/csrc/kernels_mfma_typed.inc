@@ -17,6 +17,10 @@ constexpr int kAct = NEMPC_ACT;          // this translation unit's activation
 constexpr int kLdsBudget = 150 * 1024;  // of the CU's 160 KiB
 constexpr int kLdsBudgetCoop = 160 * 1024;
 constexpr int kMaxWaves = 8;            // 512 threads: keeps 256 VGPRs per lane available
+// A/B knobs read at two sites each: NEMPC_COOP_DIMS=0 keeps the 6/3 3x128 fp32 rows off their compiled-dimension
+// cooperative kernel, NEMPC_HFX=0 the Lagrangian blocks off the fixed-shape kernels
+inline int coop_dims_on() { static const int on = env_int("NEMPC_COOP_DIMS", 1); return on; }
+inline int hfx_on() { static const int on = env_int("NEMPC_HFX", 1); return on; }
 
 // CU-cooperative kernel: weight slices in registers; LDS holds the exchange buffer, partials, per-tile scratch
 template <typename T, int WP, int NH, int TPW, bool SR = false, int OCC = 2, int NXc = 0, int NUc = 0>
@@ -170,8 +174,7 @@ int launch_shape(const MfmaParams& p, bool allow_coop, hipStream_t s, int* kerne
             // RK4 Hessian pipeline: the stage-record instantiation, one tile per pass
             int rc = NEMPC_OK;
             if constexpr (WP == 128 && NH == 3 && sizeof(T) == 4) {
-                static const int c3fx = [] { const char* e = getenv("NEMPC_COOP_DIMS"); return e ? atoi(e) : 1; }();
-                if (c3fx && p.nx == 6 && p.nu == 3 && p.nin == 9 && p.gk.w == 1 &&
+                if (coop_dims_on() && p.nx == 6 && p.nu == 3 && p.nin == 9 && p.gk.w == 1 &&
                     try_launch_coop<T, WP, NH, 1, true, 2, 6, 3>(p, s, &rc)) {
                     *kernel_used = 2;
                     return rc;
@@ -189,7 +192,7 @@ int launch_shape(const MfmaParams& p, bool allow_coop, hipStream_t s, int* kerne
                 // fp64 2x64 and larger: the 3-tile instantiation sits at the 256-VGPR cap and spills; measured 21.2 us
                 // against 20.4 us for 2-tile passes at C2 dims (B=1024).  NEMPC_COOP_TPW is an A/B knob.
                 constexpr int tpw_default = (sizeof(T) == 8 && WP >= 64 && NH >= 2) ? 2 : 3;
-                static const int tpw_cap = [] { const char* e = getenv("NEMPC_COOP_TPW"); return e ? atoi(e) : tpw_default; }();
+                static const int tpw_cap = env_int("NEMPC_COOP_TPW", tpw_default);
 #ifdef NEMPC_EXP_OCC3   // experiment: three workgroups per CU, single-tile passes
                 if constexpr (sizeof(T) == 8 && WP == 64 && NH == 2) {
                     if (try_launch_coop<T, WP, NH, 1, false, 3>(p, s, &rc)) { *kernel_used = 2; return rc; }
@@ -204,8 +207,7 @@ int launch_shape(const MfmaParams& p, bool allow_coop, hipStream_t s, int* kerne
             // width 128 = 8 waves per workgroup (two per SIMD): one tile per pass is what LDS and registers allow
             // (BASELINE configs[2] dims -- 6 states, 3 controls, plain model -- as compile-time constants)
             if constexpr (WP == 128 && NH == 3 && sizeof(T) == 4) {
-                static const int c3fx = [] { const char* e = getenv("NEMPC_COOP_DIMS"); return e ? atoi(e) : 1; }();
-                if (c3fx && p.nx == 6 && p.nu == 3 && p.nin == 9 && p.gk.w == 1 &&
+                if (coop_dims_on() && p.nx == 6 && p.nu == 3 && p.nin == 9 && p.gk.w == 1 &&
                     try_launch_coop<T, WP, NH, 1, false, 2, 6, 3>(p, s, &rc)) {
                     *kernel_used = 2;
                     return rc;
@@ -236,7 +238,7 @@ int launch_shape(const MfmaParams& p, bool allow_coop, hipStream_t s, int* kerne
     // (Round 3 kept three of these streamed instantiations -- fp32 128-wide 2 layers, fp64 128-wide 2 layers, fp64 64-wide
     // 3 layers -- away from the launcher because they returned wrong rows.  The cause was a spill store the compiler had put
     // in front of an exec restore; the build repairs that placement and checks every kernel for it: _isa.py, DESIGN.md.)
-    static const int waves_env = [] { const char* e = getenv("NEMPC_TILE_WAVES"); return e ? atoi(e) : 4; }();   // A/B knob
+    static const int waves_env = env_int("NEMPC_TILE_WAVES", 4);   // A/B knob
     int waves = waves_env < 1 ? 1 : (waves_env > 4 ? 4 : waves_env);
     while (waves > 1 && (size_t)waves * scratch > (size_t)kLdsBudget) waves >>= 1;
     const int grid = (p.ntiles + waves - 1) / waves;
@@ -273,7 +275,7 @@ using FxTable = std::conditional_t<kAct == NEMPC_ACT_RUNTIME, FxList<>,      // 
 
 template <typename T, typename SH>
 bool fx_shape_matches(const Handle& h, const MfmaParams& p) {
-    static const int fx_on = [] { const char* e = getenv("NEMPC_FX"); return e ? atoi(e) : 1; }();
+    static const int fx_on = env_int("NEMPC_FX", 1);
     constexpr int MT = SH::WP / 16;
     return fx_on && h.variant != NEMPC_KERNEL_MFMA_TILE && p.mb == 1 && p.ks <= 4 &&
            (unsigned long long)p.B * p.H * p.H < 0x100000000ull && h.mfma.wp == SH::WP && h.mfma.nh == SH::NH && p.nx == SH::NX &&
@@ -289,7 +291,7 @@ int fx_rows_table(const Handle& h, const MfmaParams& p, bool dense_here, bool sp
                   FxList<SH, Rest...>) {
     constexpr int WP = SH::WP, NH = SH::NH, NX = SH::NX, NU = SH::NU;
     if (!fx_shape_matches<T, SH>(h, p)) return fx_rows_table<T>(h, p, dense_here, sparse_here, s, taken, FxList<Rest...>{});
-    static const int fx_tpw = [] { const char* e = getenv("NEMPC_FX_TPW"); return e ? atoi(e) : 3; }();
+    static const int fx_tpw = env_int("NEMPC_FX_TPW", 3);
     constexpr int VEC = 16 / (int)sizeof(T);
     if (p.gn_hvals) {
         // Gauss-Newton callback in one launch (tril values): fp64, two states (the epilogue sums the states by a quad permute)
@@ -477,9 +479,8 @@ int fx_hess_table(const Handle&, const HessParams&, bool, hipStream_t, bool*, Fx
 
 template <typename T, typename SH, typename... Rest>
 int fx_hess_table(const Handle& h, const HessParams& hp, bool allow_coop, hipStream_t s, bool* taken, FxList<SH, Rest...>) {
-    static const int hfx_on = [] { const char* e = getenv("NEMPC_HFX"); return e ? atoi(e) : 1; }();
     const MfmaParams& p = hp.base;
-    if (hfx_on && allow_coop && h.mfma.wp == SH::WP && h.mfma.nh == SH::NH && p.nx == SH::NX && p.nu == SH::NU &&
+    if (hfx_on() && allow_coop && h.mfma.wp == SH::WP && h.mfma.nh == SH::NH && p.nx == SH::NX && p.nu == SH::NU &&
         p.nin == SH::NX + SH::NU && p.ne == 0 && p.gk.w == 1 && p.kind != NEMPC_RK4 && !hp.xi_direct && (hp.blocks || hp.hvals) &&
         (unsigned long long)p.B * p.H * p.H < 0x100000000ull) {
         *taken = true;
@@ -518,9 +519,8 @@ int launch_rowhess_mfma_act<NEMPC_T, NEMPC_ACT>(const Handle& h, HessParams hp, 
     // BASELINE configs[2] dims (6 states, 3 controls, 3x128, fp32): the Discret / Unity blocks and the (row, stage) pairs
     // of the RK4 pipeline (direct mode), three tangent directions per exchange
     if constexpr (sizeof(T) == 4) {
-        static const int hfx_on = [] { const char* e = getenv("NEMPC_HFX"); return e ? atoi(e) : 1; }();
         const MfmaParams& p = hp.base;
-        if (kAct != NEMPC_ACT_RUNTIME && hfx_on && allow_coop && wp == 128 && nh == 3 && p.nx == 6 && p.nu == 3 && p.nin == 9 && p.ne == 0 && p.gk.w == 1 &&
+        if (kAct != NEMPC_ACT_RUNTIME && hfx_on() && allow_coop && wp == 128 && nh == 3 && p.nx == 6 && p.nu == 3 && p.nin == 9 && p.ne == 0 && p.gk.w == 1 &&
             (hp.xi_direct || p.kind != NEMPC_RK4) && (hp.blocks || hp.hvals) && !(hp.xi_direct && hp.hvals) &&
             (unsigned long long)p.B * p.H * p.H * (hp.xi_direct ? hp.vdiv : 1) < 0x100000000ull) {
             h.last_hess_kernel = 4;

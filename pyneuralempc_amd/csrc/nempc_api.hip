@@ -378,7 +378,7 @@ int nempc_create(const nempc_config* cfg, nempc_handle* out) {
     if (h->mfma_act < 0 && h->nl >= 2 && h->act[h->nl - 1] == NEMPC_ACT_LINEAR) {
         bool ok = true;
         for (int l = 0; l < h->nl - 1; ++l) ok = ok && h->act[l] >= NEMPC_ACT_LINEAR && h->act[l] < NEMPC_ACT_FIRST_ZBASED;
-        static const bool rt_off = [] { const char* e = getenv("NEMPC_MFMA_RUNTIME_ACT"); return e && atoi(e) == 0; }();    // (A/B: the layered path instead)
+        static const bool rt_off = !env_enabled("NEMPC_MFMA_RUNTIME_ACT");    // (A/B: the layered path instead)
         if (ok && !rt_off) h->mfma_act = NEMPC_ACT_RUNTIME;
     }
     {
@@ -387,10 +387,7 @@ int nempc_create(const nempc_config* cfg, nempc_handle* out) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0)
             h->num_cus = prop.multiProcessorCount;
-        if (const char* e = getenv("NEMPC_NUM_CUS")) {
-            const int v = atoi(e);
-            if (v > 0) h->num_cus = v;
-        }
+        if (const int v = env_int("NEMPC_NUM_CUS", 0); v > 0) h->num_cus = v;
     }
     h->variant = NEMPC_KERNEL_VALU;
     // swish / gelu / softsign / mish / exponential / relu6 are written from the pre-activation: the layered path (any layer,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -19,6 +20,13 @@ constexpr int32_t MAP_PLUS_ONE = -3;
 
 void set_error(const std::string& msg);
 int hip_fail(hipError_t e, const char* what);
+
+// Environment knobs (A/B switches, diagnostics): the only readers of the environment in the library.  A call reads the
+// variable afresh; a knob that is read once per process keeps the value in a `static const` at its (one) site.
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline double env_double(const char* name, double dflt) { const char* e = getenv(name); return e ? atof(e) : dflt; }
+inline bool env_enabled(const char* name) { const char* e = getenv(name); return !(e && atoi(e) == 0); }   // on unless it parses to 0
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }                                   // set at all, to anything
 
 #define NEMPC_HIP(call)                                            \
     do {                                                           \

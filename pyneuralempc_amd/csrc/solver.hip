@@ -2190,8 +2190,8 @@ struct SolverWs {
     void *X0p = nullptr, *exp_ = nullptr;           // initial states / extras of the problems still backtracking, dense
     void *Zsoc = nullptr, *gsoc = nullptr;          // second-order-correction trial points and their defects, dense
     int* pend[2] = {nullptr, nullptr};              // ... and their indices (two lists: one read, one appended to)
-    void *lb = nullptr, *ub = nullptr, *mu = nullptr, *nu = nullptr, *reg = nullptr, *alpha = nullptr, *phi0 = nullptr,
-         *dir = nullptr, *hblk = nullptr, *lam = nullptr, *lamn = nullptr, *sig = nullptr, *dz = nullptr, *Kst = nullptr, *kst = nullptr, *Pst = nullptr, *pst = nullptr,
+    void *lb = nullptr, *ub = nullptr, *alpha = nullptr, *phi0 = nullptr, *dir = nullptr, *hblk = nullptr, *lamn = nullptr,
+         *sig = nullptr, *dz = nullptr, *Kst = nullptr, *kst = nullptr, *Pst = nullptr, *pst = nullptr,
          *tmp = nullptr;   // (info lives in infoc: it is read across iterations)
     int *lsdone = nullptr, *n_active = nullptr;
     // state that lives across iterations, in two buffer sets (compaction gathers from one into the other)
@@ -2203,10 +2203,25 @@ struct SolverWs {
     int *perm = nullptr, *count = nullptr;
     int* hpoll = nullptr;                      // pinned host: [0] convergence counter (blocking polls), [2] backtracking poll
     int *hpub = nullptr, *hpub_dev = nullptr;  // pinned host memory the device publishes the convergence counter to
-    int cap = 0;
+    int cap = 0;                              // problems the buffers hold; 0 until every allocation has succeeded
     int m = 0, n = 0;                         // row / variable counts the buffers were sized for (box rows change m)
     size_t ex_per = 0;
     std::vector<unsigned char> bounds_host;   // the bounds as last uploaded (lb | ub in the handle's dtype)
+
+    // The workspace owns its memory: every buffer above comes from alloc(), which records what it hands out, and
+    // release() walks the records.  A pointer is recorded once its allocation has succeeded, so a failure part-way leaves
+    // a workspace that the next release frees completely.  Buffers stay allocations of their own.
+    std::vector<void*> dev_allocs, host_allocs;
+    int alloc(void** p, size_t bytes, int host_flags = -1) {     // device memory, or pinned host memory with these flags
+        NEMPC_HIP(host_flags < 0 ? hipMalloc(p, bytes ? bytes : 16)      // (an empty array still has an address of its own)
+                                 : hipHostMalloc(p, bytes, (unsigned)host_flags));
+        (host_flags < 0 ? dev_allocs : host_allocs).push_back(*p);
+        return NEMPC_OK;
+    }
+    void release() {
+        for (void* p : dev_allocs) (void)hipFree(p);
+        for (void* p : host_allocs) (void)hipHostFree(p);
+    }
 };
 
 // polite busy-wait on a word the device writes (the waits are microseconds: no yield, no sleep)
@@ -2222,32 +2237,7 @@ int lq_tmp_elems(int nx, int nu) { return 3 * nx * nx + 3 * nx * nu + nu * nu + 
 
 void solver_free(Handle& h) {
     SolverWs* w = static_cast<SolverWs*>(h.solver_ws);
-    if (!w) return;
-    void** ptrs[] = {&w->Zt, &w->f, &w->ft, &w->grad, &w->g, &w->gt, &w->tiles, &w->lb, &w->ub, &w->mu, &w->nu, &w->reg,
-                     &w->alpha, &w->phi0, &w->dir, &w->hblk, &w->lam, &w->lamn, &w->sig, &w->dz, &w->Kst, &w->kst, &w->Pst, &w->pst, &w->tmp,
-                     &w->tiles_t, &w->grad_t, &w->X0p, &w->exp_, &w->lam_t, &w->hblk_t, &w->Zsoc, &w->gsoc};
-    for (void** p : ptrs)
-        if (*p) (void)hipFree(*p);
-    if (w->lsdone) (void)hipFree(w->lsdone);
-    for (int k = 0; k < 2; ++k)
-        if (w->pend[k]) (void)hipFree(w->pend[k]);
-    if (w->n_active) (void)hipFree(w->n_active);
-    if (w->hpoll) (void)hipHostFree(w->hpoll);
-    if (w->hpub) (void)hipHostFree(w->hpub);
-    for (int k = 0; k < 2; ++k) {
-        void* ps[] = {w->Zc[k], w->X0c[k], w->lamc[k], w->muc[k], w->nuc[k], w->regc[k], w->exc[k], w->infoc[k], w->stc[k],
-                      w->orig[k], w->itc[k], w->zlc[k], w->zuc[k]};
-        for (void* p : ps)
-            if (p) (void)hipFree(p);
-    }
-    for (void* p : {w->dzl, w->dzu, w->alz, w->bh})
-        if (p) (void)hipFree(p);
-    if (w->perm) (void)hipFree(w->perm);
-    if (w->count) (void)hipFree(w->count);
-    for (void* p : {w->rZ, w->rg, w->rtiles, w->rhblk, w->rgrad, w->rlam, w->rZin, w->rS0, w->rZout, w->robj,
-                    (void*)w->rt.src, (void*)w->rt.src0, (void*)w->rt.prim, (void*)w->rt.isprim, (void*)w->rt.dcol,
-                    (void*)w->rt.shift})
-        if (p) (void)hipFree(p);
+    if (w) w->release();
     delete w;
     h.solver_ws = nullptr;
 }
@@ -2255,149 +2245,220 @@ void solver_free(Handle& h) {
 namespace {
 // the handle's extras binding is pointed at the compacted copy while the solve runs; put back on every exit path
 struct ExtraBindingGuard {
-    Handle& h;
-    const void* saved;
-    int saved_B;
+    Handle& h; const void* saved; int saved_B;
     explicit ExtraBindingGuard(Handle& hh) : h(hh), saved(hh.d_extra), saved_B(hh.extra_B) {}
     ~ExtraBindingGuard() { h.d_extra = saved; h.extra_B = saved_B; }
 };
-}  // namespace
 
+// The solver's environment knobs (README "Environment switches"), read where declared: ProcessKnobs once per process and dtype
+// (the function-local static of Solve<T>::read_knobs), what SolverKnobs adds on every solve (tests flip these in one process).
+struct ProcessKnobs {
+    int lq_attempts = env_int("NEMPC_LQ_ATTEMPTS", 0);   // A/B knob (counts when positive)
+    int lq_scan = env_int("NEMPC_LQ_SCAN", 1);   // A/B knob
+    double slack_eps = env_double("NEMPC_SOLVER_SLACK_EPS", 0.0);
+    // NEMPC_SOLVER_NONMONO: 0 monotone Armijo test (rounds 1-3), 1 .. 4 merit values of previous iterates the test may
+    // refer to (default 4).  configs[2] dims, B = 1024, converged after 40 / 60 / 80 / 160 iterations
+    // (profiles/r04_solver_nonmonotone.txt): 664 / 825 / 918 / 1008 monotone, 722 / 854 / 932 / 1014 (1), 747 / 881 / 966 /
+    // 1020 (2), 766 / 906 / 974 / 1019 (3), 775 / 924 / 985 / 1021 (4); C2 dims 965 / 979 / 997 / 1015 -> 968 / 994 / 1011 / 1019
+    int nonmono = env_int("NEMPC_SOLVER_NONMONO", 4);
+    // The Levenberg term moves in half decades (round 5).  In whole decades -- x 10 when a sweep meets a pivot that is not
+    // positive, x 0.1 after a clean one -- a problem whose reduced Hessian needs a term of, say, 2 alternates between 1
+    // (fails, retried) and 10: it is damped five times harder than it has to be, and the slow problems of configs[2]'s dims
+    // crawled through a dozen iterations of 4e-2 steps that way (tools/c3_slow_trace.py).  sqrt(10) each way: converged
+    // after 40 / 60 / 80 iterations 994 / 1024 / 1024 of 1024 instead of 847 / 990 / 1021, the last problem through in
+    // 81 ms instead of 123; C2 dims unchanged (968 / 991 / 1010 / 1021 against 968 / 993 / 1010 / 1019);
+    // profiles/r05_solver_reg_steps.txt.  NEMPC_SOLVER_REG_RAISE / _RELAX are the A/B knobs.
+    double reg_relax = env_double("NEMPC_SOLVER_REG_RELAX", 0.31622776601683794);
+    double reg_raise = env_double("NEMPC_SOLVER_REG_RAISE", 3.1622776601683795);
+    bool stats = env_set("NEMPC_SOLVER_STATS");   // Riccati restarts per iteration (diagnostic, synchronises)
+    int trace_slot = env_int("NEMPC_SOLVER_TRACE", -1);   // one line per iteration for that slot (diagnostic, synchronises)
+};
+struct SolverKnobs : ProcessKnobs {
+    int lq_spec = env_int("NEMPC_LQ_SPEC", 0);   // A/B knob (tests)
+    int no_fuse_step = env_int("NEMPC_SOLVER_NO_FUSE_STEP", 0);   // (tests)
+    int no_carry = env_int("NEMPC_SOLVER_NO_CARRY", 0);   // A/B knob (tests)
+    int hess_trial = env_int("NEMPC_SOLVER_HESS_TRIAL", 1);   // A/B knob (tests)
+    int fuse_accept = env_int("NEMPC_SOLVER_FUSE_ACCEPT", 1);   // A/B knob (tests)
+    bool soc = env_enabled("NEMPC_SOLVER_SOC");      // (read per solve)
+};
+
+struct RollTablesHost { std::vector<int> src, src0, prim, isprim, dcol, shift; };
+
+// One solve: handle, workspace, options, knobs, dimensions, what plan_lq decides, the kernels' arguments and the state the
+// iteration carries from one step to the next.  run() is the algorithm; the members behind it are its steps.
 template <typename T>
-static int solve_impl(Handle& h, int B, const void* X0, void* Z, const double* lb, const double* ub,
-                      const nempc_solver_opts& o, int32_t* status_dev, int32_t* iters_host, hipStream_t s) {
-    // rolling-window models run as a plain problem in the augmented (window) state, see RollTables: nx, nin, n, m below are
+struct Solve {
+    Handle& h; SolverWs& ws; const nempc_solver_opts& o; const int B; const void* const X0; const hipStream_t s;
+    // rolling-window models run as a plain problem in the augmented (window) state, see RollTables: nx, nin, n, m are
     // the SOLVER's stage dimensions; *_r the handle's (the caller's variables, the callbacks' shapes)
-    const bool rolling = h.w > 1;
-    const int H = h.cfg.H, nx_r = h.cfg.nx, nu = h.cfg.nu, nin_r = h.nin, n_r = h.n, m_r = h.m, back = h.w - 1;
-    const int nx = rolling ? h.w * nx_r + back * nu : nx_r, nin = rolling ? nx + nu : nin_r, n = rolling ? H * (nx + nu) : n_r,
-              m = rolling ? H * nx : m_r;
-    const size_t ex_per = (size_t)H * h.ne;
-    if (!h.solver_ws) h.solver_ws = new SolverWs();
-    {
-        SolverWs& w = *static_cast<SolverWs*>(h.solver_ws);
-        if (w.cap < B || w.ex_per != ex_per || w.m != m || w.n != n) {
-            solver_free(h);
-            h.solver_ws = new SolverWs();
-            SolverWs& w2 = *static_cast<SolverWs*>(h.solver_ws);
-            const size_t e = sizeof(T), Bn = (size_t)B;
-            struct { void** p; size_t bytes; } al[] = {
-                {&w2.Zt, Bn * n * e}, {&w2.f, Bn * e}, {&w2.ft, Bn * e}, {&w2.grad, Bn * n * e}, {&w2.g, Bn * m * e},
-                {&w2.gt, Bn * m * e}, {&w2.tiles, Bn * H * nx * nin * e}, {&w2.lb, (size_t)n * e}, {&w2.ub, (size_t)n * e},
-                {&w2.alpha, Bn * e}, {&w2.phi0, Bn * e},
-                {&w2.dir, Bn * e}, {&w2.hblk, Bn * H * nin * nin * e}, {&w2.lamn, Bn * m * e},
-                {&w2.sig, Bn * e}, {&w2.dz, Bn * n * e}, {&w2.Kst, Bn * H * nu * nx * e},
-                {&w2.kst, Bn * H * nu * e}, {&w2.Pst, Bn * H * nx * nx * e}, {&w2.pst, Bn * H * nx * e},
-                {&w2.tmp, Bn * lq_tmp_elems(nx, nu) * e}, {&w2.dzl, Bn * n * e}, {&w2.dzu, Bn * n * e}, {&w2.alz, Bn * e},
-                {&w2.bh, Bn * n * e}, {&w2.tiles_t, Bn * H * nx * nin * e}, {&w2.grad_t, Bn * n * e},
-                {&w2.X0p, Bn * nx * e}, {&w2.exp_, Bn * ex_per * e}, {&w2.lam_t, Bn * m * e}, {&w2.hblk_t, Bn * H * nin * nin * e},
-                {&w2.Zsoc, Bn * n * e}, {&w2.gsoc, Bn * m * e}};
-            for (auto& x : al) NEMPC_HIP(hipMalloc(x.p, x.bytes ? x.bytes : 16));
-            for (int k = 0; k < 2; ++k) {
-                struct { void** p; size_t bytes; } al2[] = {
-                    {&w2.Zc[k], Bn * n * e}, {&w2.X0c[k], Bn * nx * e}, {&w2.lamc[k], Bn * m * e}, {&w2.muc[k], Bn * e},
-                    {&w2.nuc[k], Bn * e}, {&w2.regc[k], Bn * e}, {&w2.exc[k], Bn * ex_per * e}, {&w2.infoc[k], Bn * INFO_N * e},
-                    {&w2.zlc[k], Bn * n * e}, {&w2.zuc[k], Bn * n * e},
-                    {(void**)&w2.stc[k], Bn * sizeof(int)}, {(void**)&w2.orig[k], Bn * sizeof(int)},
-                    {(void**)&w2.itc[k], Bn * sizeof(int)}};
-                for (auto& x : al2) NEMPC_HIP(hipMalloc(x.p, x.bytes ? x.bytes : 16));
-            }
-            NEMPC_HIP(hipMalloc((void**)&w2.lsdone, Bn * sizeof(int)));
-            for (int k = 0; k < 2; ++k) NEMPC_HIP(hipMalloc((void**)&w2.pend[k], Bn * sizeof(int)));
-            NEMPC_HIP(hipMalloc((void**)&w2.n_active, 8 * sizeof(int)));   // [unconverged, still backtracking, blocks done, -, unconverged (odd iterations)]
-            NEMPC_HIP(hipMemset(w2.n_active, 0, 8 * sizeof(int)));
-            NEMPC_HIP(hipHostMalloc((void**)&w2.hpoll, 4 * sizeof(int), hipHostMallocDefault));
-            NEMPC_HIP(hipHostMalloc((void**)&w2.hpub, 8 * sizeof(int), hipHostMallocMapped));
-            NEMPC_HIP(hipHostGetDevicePointer((void**)&w2.hpub_dev, w2.hpub, 0));
-            NEMPC_HIP(hipMalloc((void**)&w2.perm, Bn * sizeof(int)));
-            NEMPC_HIP(hipMalloc((void**)&w2.count, sizeof(int)));
-            if (rolling) {
-                struct { void** p; size_t bytes; } alr[] = {
-                    {&w2.rZ, Bn * n_r * e}, {&w2.rg, Bn * m_r * e}, {&w2.rtiles, Bn * H * nx_r * nin_r * e},
-                    {&w2.rhblk, Bn * H * nin_r * nin_r * e}, {&w2.rgrad, Bn * n_r * e}, {&w2.rlam, Bn * m_r * e},
-                    {&w2.rZin, Bn * n * e}, {&w2.rS0, Bn * nx * e}, {&w2.rZout, Bn * n * e},
-                    {&w2.robj, (size_t)obj_offsets(H, nx, nu).total * e}};
-                for (auto& x : alr) NEMPC_HIP(hipMalloc(x.p, x.bytes));
-                NEMPC_HIP(hipMemsetAsync(w2.rlam, 0, Bn * m_r * e, s));     // (box rows of the handle keep zero multipliers)
-                // index tables.  x-slot k of s_tau is x_{tau-k} (index into [x0 ; states]), u-slot k is u_{tau-1-k}
-                const int wx = h.w * nx_r;
-                auto data_x = [&](int tau, int c) { return tau == 0 ? c : nx_r + (back + tau) * nx_r + c; };           // tau <= 0
-                auto data_u = [&](int tau, int c) { return nx_r + back * nx_r + (back + tau) * nu + c; };               // tau < 0
-                std::vector<int> src(n), src0(nx), prim(n_r, -1), isprim(n, 0), dcol(nin, -1), shift(nx, -1);
-                auto slot_source = [&](int tau_s, int i) {     // entry i of s_{tau_s}: caller variable or -(1 + data index)
-                    if (i < wx) {
-                        const int tau = tau_s - i / nx_r, c = i % nx_r;
-                        return tau >= 1 ? (tau - 1) * nx_r + c : -(1 + data_x(tau, c));
-                    }
-                    const int k = (i - wx) / nu, c = (i - wx) % nu, tau = tau_s - 1 - k;
-                    return tau >= 0 ? H * nx_r + tau * nu + c : -(1 + data_u(tau, c));
-                };
-                for (int i = 0; i < nx; ++i) src0[i] = slot_source(0, i);
-                for (int t = 0; t < H; ++t) {
-                    for (int i = 0; i < nx; ++i) {
-                        src[t * nx + i] = slot_source(t + 1, i);
-                        if (i < nx_r) { isprim[t * nx + i] = 1; prim[t * nx_r + i] = t * nx + i; }
-                    }
-                    for (int c = 0; c < nu; ++c) {
-                        const int k = H * nx + t * nu + c;
-                        src[k] = H * nx_r + t * nu + c; isprim[k] = 1; prim[H * nx_r + t * nu + c] = k;
-                    }
-                }
-                // window column d of step t (network input order, window_var in nempc_api.hip) -> column of (s_t, u_t)
-                for (int d = 0; d < nin_r; ++d) {
-                    int col;
-                    if (d < wx) {
-                        const int j = d / nx_r, c = d % nx_r;
-                        col = (h.rev ? j : back - j) * nx_r + c;                 // x_{t - k}: x-slot k of s_t
-                    } else {
-                        const int j = (d - wx) / nu, c = (d - wx) % nu, k = h.rev ? j : back - j;   // u_{t - k}
-                        col = k == 0 ? nx + c : wx + (k - 1) * nu + c;
-                    }
-                    dcol[col] = d;
-                }
-                // shift rows of s_{t+1}: x-slot k >= 1 copies x-slot k-1 of s_t; u-slot 0 copies u_t, u-slot k copies u-slot k-1
-                for (int i = nx_r; i < nx; ++i) {
-                    if (i < wx) shift[i] = i - nx_r;
-                    else { const int k = (i - wx) / nu, c = (i - wx) % nu; shift[i] = k == 0 ? nx + c : wx + (k - 1) * nu + c; }
-                }
-                struct { int** p; const std::vector<int>* v; } tb[] = {{&w2.rt.src, &src}, {&w2.rt.src0, &src0}, {&w2.rt.prim, &prim},
-                                                                       {&w2.rt.isprim, &isprim}, {&w2.rt.dcol, &dcol}, {&w2.rt.shift, &shift}};
-                for (auto& x : tb) {
-                    NEMPC_HIP(hipMalloc((void**)x.p, x.v->size() * sizeof(int)));
-                    NEMPC_HIP(hipMemcpy(*x.p, x.v->data(), x.v->size() * sizeof(int), hipMemcpyHostToDevice));
-                }
-                w2.prim_host = prim;
-            }
-            w2.cap = B;
-            w2.m = m; w2.n = n;
-            w2.ex_per = ex_per;
+    const bool rolling; const int H, nx_r, nu, nin_r, n_r, m_r, back, nx, nin, n, m;
+    const size_t ex_per; const unsigned gBn, gRn;      // grids of the element-wise kernels over the solver's / the caller's variables
+    const SolverKnobs kn = read_knobs();
+    ExtraBindingGuard extra_guard; SolverArgs a{}; bool has_bounds = false;
+    // plan_lq decides (besides fields of `a`): the kernel; stages wide enough to spread over a wave (matrix-core-bound
+    // iterations); LDS elements per problem (odd); LDS of a workgroup: the problems' blocks + one copy of the bounds (2 n)
+    void (*lqk)(SolverArgs) = nullptr; bool wave_wanted = false; int per_problem = 0; size_t wg_extra = 0, lds_budget = 0;
+    volatile int* hp = nullptr;   // the words the device publishes (SolverArgs::hpub)
+    int cur = 0;                  // buffer set of the working copies
+    int Bact;                     // slots [0, Bact) may still be unconverged; compaction keeps them in front
+    int last_nact;                // unconverged problems at the last convergence poll
+    int it = 0, nact = -1;        // nact: unconverged problems as this iteration's poll has them (-1: it did not poll)
+    bool finished = false;        // ... and the poll found none left (`it` is then the iteration at which that happened)
+    int pend_seq = 0;             // sequence number of the inner loop's acceptance launches (published with their count)
+    bool carry = false;           // deferred backtracking on a compiled shape: a trial evaluation is a full one, kept on acceptance
+    bool hess_trial = false;      // ... with the trial point's Lagrangian blocks from the launch that evaluates it
+    bool have_eval = false;       // the evaluation buffers hold every active problem's current iterate
+    bool have_blocks = false;     // ... and so does the block buffer
+    bool accept_pending = false;  // the last trial point has been evaluated, its acceptance test has not been launched
+    bool published_polls = false, trace = false, compact = false;
+    static SolverKnobs read_knobs() { static const ProcessKnobs once; return SolverKnobs{once}; }
+    static SolverWs& workspace(Handle& h) { return *static_cast<SolverWs*>(h.solver_ws ? h.solver_ws : (h.solver_ws = new SolverWs())); }
+    Solve(Handle& hh, int BB, const void* X0_, const nempc_solver_opts& oo, hipStream_t ss)
+        : h(hh), ws(workspace(hh)), o(oo), B(BB), X0(X0_), s(ss), rolling(h.w > 1), H(h.cfg.H), nx_r(h.cfg.nx), nu(h.cfg.nu),
+          nin_r(h.nin), n_r(h.n), m_r(h.m), back(h.w - 1), nx(rolling ? h.w * nx_r + back * nu : nx_r),
+          nin(rolling ? nx + nu : nin_r), n(rolling ? H * (nx + nu) : n_r), m(rolling ? H * nx : m_r), ex_per((size_t)H * h.ne),
+          gBn((unsigned)(((size_t)BB * std::max(n, std::max(m, nx)) + 255) / 256)),
+          gRn((unsigned)(((size_t)BB * n_r + 255) / 256)), extra_guard(hh), Bact(BB), last_nact(BB) {}
+    int run(void* Z, const double* lb, const double* ub, int32_t* status_dev, int32_t* iters_host) {
+        int rc;
+        if ((rc = ensure_workspace()) || (rc = upload_bounds(lb, ub)) || (rc = start(Z))) return rc;
+        for (; it < o.max_iter; ++it) {
+            a.B = Bact; a.cur_it = it; nact = -1;
+            if ((rc = evaluate_iterate())) return rc;       // defects, tiles, f, gradient, Lagrangian blocks
+            launch_lq();                                    // [acceptance of the last trial,] LQ solve, step, first trial point
+            if (!published_polls && (rc = poll_blocking())) return rc;
+            if (!finished && (rc = line_search())) return rc;            // trial evaluation(s) and their acceptance test
+            if (!finished && published_polls && (rc = poll_published())) return rc;
+            if (finished) break;            // (`it` is the iteration at which the last problem converged)
+            if ((rc = diagnostics())) return rc;
+            // once a quarter of the active slots has finished, shrink every launch to the unconverged problems
+            if (compact && nact >= 0 && nact < Bact - Bact / 4 && Bact > 64 && (rc = compact_batch())) return rc;
         }
+        return finish(Z, status_dev, iters_host);
     }
-    SolverWs& ws = *static_cast<SolverWs*>(h.solver_ws);
+    // index tables of a rolling-window model (RollTables, on the host).  x-slot k of s_tau is x_{tau-k} (index into
+    // [x0 ; states]), u-slot k is u_{tau-1-k}
+    RollTablesHost build_roll_tables() const {
+        const int wx = h.w * nx_r;
+        auto data_x = [&](int tau, int c) { return tau == 0 ? c : nx_r + (back + tau) * nx_r + c; };           // tau <= 0
+        auto data_u = [&](int tau, int c) { return nx_r + back * nx_r + (back + tau) * nu + c; };               // tau < 0
+        RollTablesHost t{std::vector<int>(n), std::vector<int>(nx), std::vector<int>(n_r, -1), std::vector<int>(n, 0),
+                         std::vector<int>(nin, -1), std::vector<int>(nx, -1)};
+        auto slot_source = [&](int tau_s, int i) {     // entry i of s_{tau_s}: caller variable or -(1 + data index)
+            if (i < wx) {
+                const int tau = tau_s - i / nx_r, c = i % nx_r;
+                return tau >= 1 ? (tau - 1) * nx_r + c : -(1 + data_x(tau, c));
+            }
+            const int k = (i - wx) / nu, c = (i - wx) % nu, tau = tau_s - 1 - k;
+            return tau >= 0 ? H * nx_r + tau * nu + c : -(1 + data_u(tau, c));
+        };
+        for (int i = 0; i < nx; ++i) t.src0[i] = slot_source(0, i);
+        for (int st = 0; st < H; ++st) {
+            for (int i = 0; i < nx; ++i) {
+                t.src[st * nx + i] = slot_source(st + 1, i);
+                if (i < nx_r) { t.isprim[st * nx + i] = 1; t.prim[st * nx_r + i] = st * nx + i; }
+            }
+            for (int c = 0; c < nu; ++c) {
+                const int k = H * nx + st * nu + c;
+                t.src[k] = H * nx_r + st * nu + c; t.isprim[k] = 1; t.prim[H * nx_r + st * nu + c] = k;
+            }
+        }
+        // window column d of step t (network input order, window_var in nempc_api.hip) -> column of (s_t, u_t)
+        for (int dw = 0; dw < nin_r; ++dw) {
+            int col;
+            if (dw < wx) {
+                const int j = dw / nx_r, c = dw % nx_r;
+                col = (h.rev ? j : back - j) * nx_r + c;                 // x_{t - k}: x-slot k of s_t
+            } else {
+                const int j = (dw - wx) / nu, c = (dw - wx) % nu, k = h.rev ? j : back - j;   // u_{t - k}
+                col = k == 0 ? nx + c : wx + (k - 1) * nu + c;
+            }
+            t.dcol[col] = dw;
+        }
+        // shift rows of s_{t+1}: x-slot k >= 1 copies x-slot k-1 of s_t; u-slot 0 copies u_t, u-slot k copies u-slot k-1
+        for (int i = nx_r; i < nx; ++i) {
+            if (i < wx) t.shift[i] = i - nx_r;
+            else { const int k = (i - wx) / nu, c = (i - wx) % nu; t.shift[i] = k == 0 ? nx + c : wx + (k - 1) * nu + c; }
+        }
+        return t;
+    }
+    // a workspace that holds B problems of these dimensions: kept when the handle has one, rebuilt otherwise
+    int ensure_workspace() {
+        if (ws.cap >= B && ws.ex_per == ex_per && ws.m == m && ws.n == n) return NEMPC_OK;
+        ws.release(); ws = SolverWs();
+        SolverWs& w = ws;
+        const size_t e = sizeof(T), Bn = (size_t)B;
+        struct Req { void** p; size_t bytes; };
+        std::vector<Req> al = {
+            {&w.Zt, Bn * n * e}, {&w.f, Bn * e}, {&w.ft, Bn * e}, {&w.grad, Bn * n * e}, {&w.g, Bn * m * e},
+            {&w.gt, Bn * m * e}, {&w.tiles, Bn * H * nx * nin * e}, {&w.lb, (size_t)n * e}, {&w.ub, (size_t)n * e},
+            {&w.alpha, Bn * e}, {&w.phi0, Bn * e},
+            {&w.dir, Bn * e}, {&w.hblk, Bn * H * nin * nin * e}, {&w.lamn, Bn * m * e},
+            {&w.sig, Bn * e}, {&w.dz, Bn * n * e}, {&w.Kst, Bn * H * nu * nx * e},
+            {&w.kst, Bn * H * nu * e}, {&w.Pst, Bn * H * nx * nx * e}, {&w.pst, Bn * H * nx * e},
+            {&w.tmp, Bn * lq_tmp_elems(nx, nu) * e}, {&w.dzl, Bn * n * e}, {&w.dzu, Bn * n * e}, {&w.alz, Bn * e},
+            {&w.bh, Bn * n * e}, {&w.tiles_t, Bn * H * nx * nin * e}, {&w.grad_t, Bn * n * e},
+            {&w.X0p, Bn * nx * e}, {&w.exp_, Bn * ex_per * e}, {&w.lam_t, Bn * m * e}, {&w.hblk_t, Bn * H * nin * nin * e},
+            {&w.Zsoc, Bn * n * e}, {&w.gsoc, Bn * m * e}};
+        for (int k = 0; k < 2; ++k)
+            al.insert(al.end(), {
+                {&w.Zc[k], Bn * n * e}, {&w.X0c[k], Bn * nx * e}, {&w.lamc[k], Bn * m * e}, {&w.muc[k], Bn * e},
+                {&w.nuc[k], Bn * e}, {&w.regc[k], Bn * e}, {&w.exc[k], Bn * ex_per * e}, {&w.infoc[k], Bn * INFO_N * e},
+                {&w.zlc[k], Bn * n * e}, {&w.zuc[k], Bn * n * e},
+                {(void**)&w.stc[k], Bn * sizeof(int)}, {(void**)&w.orig[k], Bn * sizeof(int)},
+                {(void**)&w.itc[k], Bn * sizeof(int)}});
+        al.insert(al.end(), {{(void**)&w.lsdone, Bn * sizeof(int)}, {(void**)&w.pend[0], Bn * sizeof(int)},
+                             {(void**)&w.pend[1], Bn * sizeof(int)},
+                             {(void**)&w.n_active, 8 * sizeof(int)},   // [unconverged, still backtracking, blocks done, -, unconverged (odd iterations)]
+                             {(void**)&w.perm, Bn * sizeof(int)}, {(void**)&w.count, sizeof(int)}});
+        if (rolling)
+            al.insert(al.end(), {
+                {&w.rZ, Bn * n_r * e}, {&w.rg, Bn * m_r * e}, {&w.rtiles, Bn * H * nx_r * nin_r * e},
+                {&w.rhblk, Bn * H * nin_r * nin_r * e}, {&w.rgrad, Bn * n_r * e}, {&w.rlam, Bn * m_r * e},
+                {&w.rZin, Bn * n * e}, {&w.rS0, Bn * nx * e}, {&w.rZout, Bn * n * e},
+                {&w.robj, (size_t)obj_offsets(H, nx, nu).total * e}});
+        for (const Req& x : al) if (int rc = w.alloc(x.p, x.bytes)) return rc;
+        NEMPC_HIP(hipMemset(w.n_active, 0, 8 * sizeof(int)));
+        if (int rc = w.alloc((void**)&w.hpoll, 4 * sizeof(int), hipHostMallocDefault)) return rc;
+        if (int rc = w.alloc((void**)&w.hpub, 8 * sizeof(int), hipHostMallocMapped)) return rc;
+        NEMPC_HIP(hipHostGetDevicePointer((void**)&w.hpub_dev, w.hpub, 0));
+        if (rolling) {
+            NEMPC_HIP(hipMemsetAsync(w.rlam, 0, Bn * m_r * e, s));     // (box rows of the handle keep zero multipliers)
+            const RollTablesHost t = build_roll_tables();
+            struct { int** p; const std::vector<int>* v; } tb[] = {{&w.rt.src, &t.src}, {&w.rt.src0, &t.src0}, {&w.rt.prim, &t.prim},
+                                                                   {&w.rt.isprim, &t.isprim}, {&w.rt.dcol, &t.dcol}, {&w.rt.shift, &t.shift}};
+            for (auto& x : tb) {
+                if (int rc = w.alloc((void**)x.p, x.v->size() * sizeof(int))) return rc;
+                NEMPC_HIP(hipMemcpy(*x.p, x.v->data(), x.v->size() * sizeof(int), hipMemcpyHostToDevice));
+            }
+            w.prim_host = t.prim;
+        }
+        w.cap = B; w.m = m; w.n = n; w.ex_per = ex_per;
+        return NEMPC_OK;
+    }
     // bounds -> device (dtype T); +-inf become +-max so that comparisons stay exact.  Box ROWS on the states
     // (nempc_set_box_rows; a Constraint's rows in the reference's glue, optimizer/ipopt.py:44-52) are bounds on the
     // state variables for this solver: intersected here, what controller.py:101-105 of this package does on the host.
-    const T big = std::numeric_limits<T>::max();
-    std::vector<T> hl(n, -big), hu(n, big);      // (rolling: the copies inside the window state carry no bounds of their own)
-    bool has_bounds = false;
-    for (int i = 0; i < n_r; ++i) {
-        double lo = lb ? lb[i] : -INFINITY, hi = ub ? ub[i] : INFINITY;
-        if (h.box && i < H * nx_r) {
-            lo = std::max(lo, h.box_lo[i % nx_r]);
-            hi = std::min(hi, h.box_hi[i % nx_r]);
+    int upload_bounds(const double* lb, const double* ub) {
+        const T big = std::numeric_limits<T>::max();
+        std::vector<T> hl(n, -big), hu(n, big);      // (rolling: the copies inside the window state carry no bounds of their own)
+        for (int i = 0; i < n_r; ++i) {
+            double lo = lb ? lb[i] : -INFINITY, hi = ub ? ub[i] : INFINITY;
+            if (h.box && i < H * nx_r) {
+                lo = std::max(lo, h.box_lo[i % nx_r]);
+                hi = std::min(hi, h.box_hi[i % nx_r]);
+            }
+            if (lo > hi) { set_error("nempc_solve: lb > ub"); return NEMPC_EINVAL; }
+            if (lo == hi) {
+                set_error("nempc_solve: lb == ub (a fixed variable has no interior for the barrier); eliminate it from the problem");
+                return NEMPC_EINVAL;
+            }
+            const int k = rolling ? ws.prim_host[i] : i;
+            hl[k] = std::isfinite(lo) ? (T)lo : -big;
+            hu[k] = std::isfinite(hi) ? (T)hi : big;
+            has_bounds = has_bounds || std::isfinite(lo) || std::isfinite(hi);
         }
-        if (lo > hi) { set_error("nempc_solve: lb > ub"); return NEMPC_EINVAL; }
-        if (lo == hi) {
-            set_error("nempc_solve: lb == ub (a fixed variable has no interior for the barrier); eliminate it from the problem");
-            return NEMPC_EINVAL;
-        }
-        const int k = rolling ? ws.prim_host[i] : i;
-        hl[k] = std::isfinite(lo) ? (T)lo : -big;
-        hu[k] = std::isfinite(hi) ? (T)hi : big;
-        has_bounds = has_bounds || std::isfinite(lo) || std::isfinite(hi);
-    }
-    // (an MPC loop solves with the same bounds every step: they are uploaded when they change)
-    {
+        // (an MPC loop solves with the same bounds every step: they are uploaded when they change)
         const size_t nb = (size_t)n * sizeof(T);
         if (ws.bounds_host.size() != 2 * nb || memcmp(ws.bounds_host.data(), hl.data(), nb) != 0 ||
             memcmp(ws.bounds_host.data() + nb, hu.data(), nb) != 0) {
@@ -2408,27 +2469,11 @@ static int solve_impl(Handle& h, int B, const void* X0, void* Z, const double* l
             memcpy(ws.bounds_host.data(), hl.data(), nb);
             memcpy(ws.bounds_host.data() + nb, hu.data(), nb);
         }
+        return NEMPC_OK;
     }
-
-    // ---- working copies in buffer set `cur`; the caller's Z / status are written once, at the end, in the caller's order
-    int cur = 0;
-    ExtraBindingGuard extra_guard(h);
-    if (ex_per) {
-        NEMPC_HIP(hipMemcpyAsync(ws.exc[0], h.d_extra, (size_t)B * ex_per * sizeof(T), hipMemcpyDeviceToDevice, s));
-        h.d_extra = ws.exc[0];
-        h.extra_B = B;
-    }
-    const unsigned gBn = (unsigned)(((size_t)B * std::max(n, std::max(m, nx)) + 255) / 256);
-    const void* Zstart = Z;
-    const void* X0start = X0;
-    const void* obj_dev = h.d_obj;
-    if (rolling) {
-        // the window state's start (augmented guess, s_0) and the objective table over the augmented stage: the caller's
-        // weights on the primary block of s, zeros on the copies
-        hipLaunchKernelGGL(roll_build_kernel<T>, dim3(gBn), dim3(256), 0, s, B, n, nx, n_r, nx_r, nu, back, ws.rt, (const T*)Z,
-                           (const T*)X0, (const T*)h.d_hist_x, (const T*)h.d_hist_u, (const T*)ws.lb, (const T*)ws.ub,
-                           (T)o.mu_init, has_bounds ? 1 : 0, (T*)ws.rZin, (T*)ws.rS0);
-        Zstart = ws.rZin; X0start = ws.rS0;
+    // rolling: the objective table over the augmented stage -- the caller's weights on the primary block of s, zeros on the
+    // copies (uploaded when it changes, like the bounds)
+    int upload_roll_objective() {
         const ObjOffsets ao = obj_offsets(H, nx, nu);
         const ObjHost& oh = h.obj_host;
         const std::vector<double>& QT = h.obj_QT.empty() ? oh.Q : h.obj_QT;
@@ -2461,256 +2506,222 @@ static int solve_impl(Handle& h, int B, const void* X0, void* Z, const double* l
             NEMPC_HIP(hipStreamSynchronize(s));   // tab is stack-owned
             ws.robj_host.assign((const unsigned char*)tab.data(), (const unsigned char*)tab.data() + tb);
         }
-        obj_dev = ws.robj;
+        return NEMPC_OK;
     }
-    hipLaunchKernelGGL(solver_init_kernel<T>, dim3(gBn), dim3(256), 0, s, B, n, (T*)ws.Zc[0], (const T*)ws.lb,
-                       (const T*)ws.ub, (T*)ws.muc[0], (T*)ws.nuc[0], (T*)ws.regc[0], ws.stc[0], ws.orig[0], ws.itc[0],
-                       (T*)ws.infoc[0], (T*)ws.zlc[0], (T*)ws.zuc[0], (T)o.mu_init, (T)o.reg, has_bounds ? 1 : 0,
-                       (const T*)Zstart, (const T*)X0start, (T*)ws.X0c[0], nx, (T*)ws.lamc[0], m);
-
-    SolverArgs a{};
-    a.H = H; a.nx = nx; a.nu = nu; a.nin = nin; a.n = n; a.m = m;
-    a.grad = ws.grad; a.g = ws.g; a.tiles = ws.tiles;
-    a.hblk = ws.hblk; a.lamn = ws.lamn;
-    a.obj = obj_dev; a.oo = obj_offsets(H, nx, nu);
-    a.lb = ws.lb; a.ub = ws.ub; a.alpha = ws.alpha; a.phi0 = ws.phi0;
-    a.dir = ws.dir; a.lsdone = ws.lsdone; a.n_active = ws.n_active; a.n_pending = ws.n_active + 1; a.n_done = ws.n_active + 2;
-    a.dz = ws.dz; a.Kst = ws.Kst;
-    a.dzl = ws.dzl; a.dzu = ws.dzu; a.alz = ws.alz; a.bh = ws.bh;
-    a.primal_dual = (has_bounds && o.barrier != 1) ? 1 : 0; a.kst = ws.kst; a.Pst = ws.Pst; a.pst = ws.pst;
-    a.tmp = ws.tmp; a.tmp_stride = (size_t)B;
-    auto point_at = [&](int k) {
-        a.Z = ws.Zc[k]; a.lam = ws.lamc[k]; a.mu = ws.muc[k]; a.pen = ws.nuc[k]; a.reg = ws.regc[k];
-        a.status = ws.stc[k]; a.iters_done = ws.itc[k]; a.info = ws.infoc[k]; a.zl = ws.zlc[k]; a.zu = ws.zuc[k];
-        if (ex_per) h.d_extra = ws.exc[k];
-    };
-    point_at(0);
-    static const int lq_attempts_env = [] { const char* e = getenv("NEMPC_LQ_ATTEMPTS"); return e ? atoi(e) : 0; }();   // A/B knob
-    a.lq_attempts = o.lq_attempts > 0 ? o.lq_attempts : (lq_attempts_env > 0 ? lq_attempts_env : 3);
-    const bool wave_wanted = o.lq_kernel != 1 && (o.lq_kernel == 2 || nx * (nx + nu) >= 12);
-    // thread-per-problem sweep: up to three damping levels side by side (lanes and LDS regions per problem)
-    const int lq_spec_env = [] { const char* e = getenv("NEMPC_LQ_SPEC"); return e ? atoi(e) : 0; }();   // A/B knob (tests)
-    a.spec = wave_wanted ? 1 : std::max(1, std::min(std::min(a.lq_attempts, lq_spec_env > 0 ? lq_spec_env : 3), 8));
-    a.att_elems = H * nu * nx + H * nu + H * nx * nx + H * nx + lq_tmp_elems(nx, nu);
-    // parallel-in-time solve (lq_scan_problem): 2/1 stages in double, a stage per lane
-    static const int lq_scan_env = [] { const char* e = getenv("NEMPC_LQ_SCAN"); return e ? atoi(e) : 1; }();   // A/B knob
-    const bool scan_fits = sizeof(T) == 8 && nx == 2 && nu == 1 && H + 1 <= 64;
-    if (o.lq_kernel == 3 && !scan_fits) {
-        set_error("nempc_solve: lq_kernel = 3 (scan) is built for 2-state / 1-control stages in fp64 with H <= 63");
-        return NEMPC_EUNSUPPORTED;
-    }
-    const bool lq_scan = scan_fits && (o.lq_kernel == 3 || (o.lq_kernel == 0 && lq_scan_env != 0));
-    if (lq_scan) {
-        a.spec = std::max(1, std::min(a.lq_attempts, 64 / (H + 1)));     // levels side by side: lane segments of H + 1
-        a.att_elems = 0;                                                    // (no per-attempt region: the scan lives in registers)
-    }
-    int per_problem;
-    // LDS of a workgroup: the problems' blocks + one copy of the bounds (2 n) behind them
-    const size_t wg_extra = (size_t)2 * n * sizeof(T);
-    const size_t lds_budget = (size_t)150 * 1024 > wg_extra ? (size_t)150 * 1024 - wg_extra : 0;
-    for (;; --a.spec) {
-        per_problem = 2 * n + 2 * H * nx + H * nx * nin + H * nin * nin + n + n + H * nx + 2 * n + a.spec * a.att_elems;
-        per_problem |= 1;   // odd stride: the ppw lanes of a sweep hit different LDS banks
-        if (a.spec == 1 || (size_t)per_problem * sizeof(T) <= lds_budget) break;   // (levels one after the other if not)
-    }
-    auto pick_ppw = [&](int Bact) {
-        int ppw = (int)(lds_budget / ((size_t)per_problem * sizeof(T)));
-        if (ppw > 16) ppw = 16;
+    int max_ppw() const { return (int)(lds_budget / ((size_t)per_problem * sizeof(T))); }
+    size_t lds_bytes(int ppw) const { return (size_t)ppw * per_problem * sizeof(T) + wg_extra; }
+    int pick_ppw(int nb) const {
+        int ppw = std::min(max_ppw(), 16);
         if (ppw * a.spec > 64) ppw = 64 / a.spec;       // the sweeping lanes are one wave
         // the sweep is one latency chain per lane whatever the number of active lanes: spread the batch over the CUs
-        const int spread = (Bact + h.num_cus - 1) / h.num_cus;
+        const int spread = (nb + h.num_cus - 1) / h.num_cus;
         if (ppw > spread) ppw = spread < 1 ? 1 : spread;
         // the wave-per-problem kernel runs one problem per wave of a 256-thread workgroup
         if (wave_wanted && ppw > 4) ppw = 4;
         return ppw;
-    };
-    a.ppw = pick_ppw(B);
-    a.use_lds = a.ppw >= 1;
-    a.lds_stride = per_problem;
-    a.tol_g = o.tol_constraint; a.tol_step = o.tol_step; a.mu_min = has_bounds ? o.mu_min : 0.0; a.mu_factor = o.mu_factor;
-    {
-        static const double slack_eps = [] { const char* e = getenv("NEMPC_SOLVER_SLACK_EPS"); return e ? atof(e) : 0.0; }();
-        a.armijo_slack = std::max(1e-12, slack_eps * (double)std::numeric_limits<T>::epsilon());
     }
-    a.max_ls = o.max_linesearch;
-    {
-        // NEMPC_SOLVER_NONMONO: 0 monotone Armijo test (rounds 1-3), 1 .. 4 merit values of previous iterates the test may
-        // refer to (default 4).  configs[2] dims, B = 1024, converged after 40 / 60 / 80 / 160 iterations
-        // (profiles/r04_solver_nonmonotone.txt): 664 / 825 / 918 / 1008 monotone, 722 / 854 / 932 / 1014 (1), 747 / 881 / 966 /
-        // 1020 (2), 766 / 906 / 974 / 1019 (3), 775 / 924 / 985 / 1021 (4); C2 dims 965 / 979 / 997 / 1015 -> 968 / 994 / 1011 / 1019
-        static const int nm_env = [] { const char* e = getenv("NEMPC_SOLVER_NONMONO"); return e ? atoi(e) : 4; }();
-        a.nonmono = nm_env < 0 ? 0 : (nm_env > 4 ? 4 : nm_env);
+    // the LQ solve of this shape: attempts and damping levels, LDS layout, problems per workgroup, the kernel
+    int plan_lq() {
+        a.lq_attempts = o.lq_attempts > 0 ? o.lq_attempts : (kn.lq_attempts > 0 ? kn.lq_attempts : 3);
+        wave_wanted = o.lq_kernel != 1 && (o.lq_kernel == 2 || nx * (nx + nu) >= 12);
+        // thread-per-problem sweep: up to three damping levels side by side (lanes and LDS regions per problem)
+        a.spec = wave_wanted ? 1 : std::max(1, std::min(std::min(a.lq_attempts, kn.lq_spec > 0 ? kn.lq_spec : 3), 8));
+        a.att_elems = H * nu * nx + H * nu + H * nx * nx + H * nx + lq_tmp_elems(nx, nu);
+        // parallel-in-time solve (lq_scan_problem): 2/1 stages in double, a stage per lane
+        const bool scan_fits = sizeof(T) == 8 && nx == 2 && nu == 1 && H + 1 <= 64;
+        if (o.lq_kernel == 3 && !scan_fits) {
+            set_error("nempc_solve: lq_kernel = 3 (scan) is built for 2-state / 1-control stages in fp64 with H <= 63");
+            return NEMPC_EUNSUPPORTED;
+        }
+        const bool lq_scan = scan_fits && (o.lq_kernel == 3 || (o.lq_kernel == 0 && kn.lq_scan != 0));
+        if (lq_scan) {
+            a.spec = std::max(1, std::min(a.lq_attempts, 64 / (H + 1)));     // levels side by side: lane segments of H + 1
+            a.att_elems = 0;                                                    // (no per-attempt region: the scan lives in registers)
+        }
+        wg_extra = (size_t)2 * n * sizeof(T);
+        lds_budget = (size_t)150 * 1024 > wg_extra ? (size_t)150 * 1024 - wg_extra : 0;
+        for (;; --a.spec) {
+            per_problem = 2 * n + 2 * H * nx + H * nx * nin + H * nin * nin + n + n + H * nx + 2 * n + a.spec * a.att_elems;
+            per_problem |= 1;   // odd stride: the ppw lanes of a sweep hit different LDS banks
+            if (a.spec == 1 || (size_t)per_problem * sizeof(T) <= lds_budget) break;   // (levels one after the other if not)
+        }
+        a.ppw = pick_ppw(B);
+        a.use_lds = a.ppw >= 1;
+        a.lds_stride = per_problem;
+        lqk = a.use_lds ? ((nx == 2 && nu == 1) ? solver_lq_kernel<T, 2, 1, true>
+                                                      : ((nx == 6 && nu == 3) ? solver_lq_kernel<T, 6, 3, true> : solver_lq_kernel<T, 0, 0, true>))
+                             : ((nx == 2 && nu == 1) ? solver_lq_kernel<T, 2, 1, false>
+                                                      : ((nx == 6 && nu == 3) ? solver_lq_kernel<T, 6, 3, false> : solver_lq_kernel<T, 0, 0, false>));
+        // wave-per-problem sweep when the working set is staged in LDS and a stage has enough entries to spread over a
+        // wave: 6/3 stages 6.5 k vs 5.0 k MPC solves/s at C3; 2/1 stages are 4 entries wide and stay on the
+        // thread-per-problem kernel (22.0 vs 23.1 ms per 40 iterations at C2).  nempc_solver_opts.lq_kernel forces one.
+        const bool lq_wave = a.use_lds && wave_wanted;
+        a.fuse_step = a.use_lds && !lq_wave && !kn.no_fuse_step;
+        a.f_it = ws.f; a.Zt_it = ws.Zt;
+        if (a.fuse_step) NEMPC_HIP(hipMemsetAsync(ws.n_active, 0, 8 * sizeof(int), s));
+        if (lq_wave)
+            lqk = (nx == 2 && nu == 1) ? solver_lqw_kernel<T, 2, 1>
+                                            : ((nx == 6 && nu == 3) ? solver_lqw_kernel<T, 6, 3> : solver_lqw_kernel<T, 0, 0>);
+        if constexpr (sizeof(T) == 8)
+            if (lq_scan && a.use_lds && !lq_wave) lqk = solver_lq_kernel<T, 2, 1, true, true>;
+        const size_t lds_max = a.use_lds ? lds_bytes(std::min(std::max(max_ppw(), 1), 16)) : 0;
+        NEMPC_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lqk), lds_max));
+        return NEMPC_OK;
+    }
+    void point_at(int k) {
+        a.Z = ws.Zc[k]; a.lam = ws.lamc[k]; a.mu = ws.muc[k]; a.pen = ws.nuc[k]; a.reg = ws.regc[k];
+        a.status = ws.stc[k]; a.iters_done = ws.itc[k]; a.info = ws.infoc[k]; a.zl = ws.zlc[k]; a.zu = ws.zuc[k];
+        if (ex_per) h.d_extra = ws.exc[k];
+    }
+    // ---- working copies in buffer set 0 (the caller's Z / status are written once, at the end, in the caller's order), the
+    //      kernels' arguments, the LQ plan and the routes this solve takes
+    int start(const void* Z) {
+        int rc;
+        if (ex_per) {
+            NEMPC_HIP(hipMemcpyAsync(ws.exc[0], h.d_extra, (size_t)B * ex_per * sizeof(T), hipMemcpyDeviceToDevice, s));
+            h.d_extra = ws.exc[0];
+            h.extra_B = B;
+        }
+        const void *Zstart = Z, *X0start = X0, *obj_dev = h.d_obj;
+        if (rolling) {
+            // the window state's start (augmented guess, s_0) and the objective table over the augmented stage
+            hipLaunchKernelGGL(roll_build_kernel<T>, dim3(gBn), dim3(256), 0, s, B, n, nx, n_r, nx_r, nu, back, ws.rt, (const T*)Z,
+                               (const T*)X0, (const T*)h.d_hist_x, (const T*)h.d_hist_u, (const T*)ws.lb, (const T*)ws.ub,
+                               (T)o.mu_init, has_bounds ? 1 : 0, (T*)ws.rZin, (T*)ws.rS0);
+            Zstart = ws.rZin; X0start = ws.rS0;
+            if ((rc = upload_roll_objective())) return rc;
+            obj_dev = ws.robj;
+        }
+        hipLaunchKernelGGL(solver_init_kernel<T>, dim3(gBn), dim3(256), 0, s, B, n, (T*)ws.Zc[0], (const T*)ws.lb,
+                           (const T*)ws.ub, (T*)ws.muc[0], (T*)ws.nuc[0], (T*)ws.regc[0], ws.stc[0], ws.orig[0], ws.itc[0],
+                           (T*)ws.infoc[0], (T*)ws.zlc[0], (T*)ws.zuc[0], (T)o.mu_init, (T)o.reg, has_bounds ? 1 : 0,
+                           (const T*)Zstart, (const T*)X0start, (T*)ws.X0c[0], nx, (T*)ws.lamc[0], m);
+        a.H = H; a.nx = nx; a.nu = nu; a.nin = nin; a.n = n; a.m = m;
+        a.grad = ws.grad; a.g = ws.g; a.tiles = ws.tiles;
+        a.hblk = ws.hblk; a.lamn = ws.lamn;
+        a.obj = obj_dev; a.oo = obj_offsets(H, nx, nu);
+        a.lb = ws.lb; a.ub = ws.ub; a.alpha = ws.alpha; a.phi0 = ws.phi0;
+        a.dir = ws.dir; a.lsdone = ws.lsdone; a.n_active = ws.n_active; a.n_pending = ws.n_active + 1; a.n_done = ws.n_active + 2;
+        a.dz = ws.dz; a.Kst = ws.Kst;
+        a.dzl = ws.dzl; a.dzu = ws.dzu; a.alz = ws.alz; a.bh = ws.bh;
+        a.primal_dual = (has_bounds && o.barrier != 1) ? 1 : 0; a.kst = ws.kst; a.Pst = ws.Pst; a.pst = ws.pst;
+        a.tmp = ws.tmp; a.tmp_stride = (size_t)B;
+        point_at(0);
+        if ((rc = plan_lq())) return rc;
+        a.tol_g = o.tol_constraint; a.tol_step = o.tol_step; a.mu_min = has_bounds ? o.mu_min : 0.0; a.mu_factor = o.mu_factor;
+        a.armijo_slack = std::max(1e-12, kn.slack_eps * (double)std::numeric_limits<T>::epsilon());
+        a.max_ls = o.max_linesearch;
+        a.nonmono = kn.nonmono < 0 ? 0 : (kn.nonmono > 4 ? 4 : kn.nonmono);
         // Piecewise-linear networks (relu, leaky_relu, relu6) have no second-order constraint violation for the relaxed test
         // to forgive; what it does there is let an iterate chatter across a kink without its step ever shrinking.  A
         // network with such a layer keeps the monotone test.
         for (int l = 0; l < h.nl; ++l)
             if (act_is_piecewise_linear(h.act[l])) a.nonmono = 0;
+        a.reg_relax = kn.reg_relax > 0.0 && kn.reg_relax < 1.0 ? kn.reg_relax : 0.31622776601683794;
+        a.reg_raise = kn.reg_raise > 1.0 && kn.reg_raise <= 100.0 ? kn.reg_raise : 3.1622776601683795;
+        const int lsm_carry = o.linesearch == 0 ? (wave_wanted ? 1 : 2) : o.linesearch;
+        carry = lsm_carry == 2 && !kn.no_carry && a.use_lds && h.variant == NEMPC_KERNEL_MFMA && h.cfg.integrator != NEMPC_RK4 &&
+                !rolling;
+        // the trial point's Lagrangian blocks from the launch that evaluates it (compiled shape): an iteration is then the LQ
+        // solve, ONE callback launch and the acceptance test
+        hess_trial = carry && a.fuse_step && kn.hess_trial != 0;
+        a.carry = 0; a.tiles_t = ws.tiles_t; a.grad_t = ws.grad_t; a.lam_t = nullptr; a.hblk_t = nullptr;
+        // the acceptance test inside the next iteration's LQ kernel (see SolverArgs::accept_first): two launches per iteration
+        a.accept_first = 0; a.n_active_prev = ws.n_active; a.gt_acc = ws.gt;
+        a.hpub = ws.hpub_dev; hp = ws.hpub;
+        for (int k = 0; k < 8; ++k) ws.hpub[k] = 0;       // (the previous solve on this handle ended with a synchronised stream)
+        published_polls = !wave_wanted;  // small stages (chains of latency-bound launches): no blocking polls, the host
+                                            // reads the counter the device publishes
+        trace = kn.trace_slot >= 0 && kn.trace_slot < B;
+        // rolling: the callbacks read the caller's x0 / history by problem index, so the batch keeps its order (a finished
+        // problem is skipped by every solver kernel; its callback rows are evaluated and ignored)
+        compact = o.compact != 0 && !trace && !rolling;
+        return NEMPC_OK;
     }
-    {
-        // The Levenberg term moves in half decades (round 5).  In whole decades -- x 10 when a sweep meets a pivot that is not
-        // positive, x 0.1 after a clean one -- a problem whose reduced Hessian needs a term of, say, 2 alternates between 1
-        // (fails, retried) and 10: it is damped five times harder than it has to be, and the slow problems of configs[2]'s dims
-        // crawled through a dozen iterations of 4e-2 steps that way (tools/c3_slow_trace.py).  sqrt(10) each way: converged
-        // after 40 / 60 / 80 iterations 994 / 1024 / 1024 of 1024 instead of 847 / 990 / 1021, the last problem through in
-        // 81 ms instead of 123; C2 dims unchanged (968 / 991 / 1010 / 1021 against 968 / 993 / 1010 / 1019);
-        // profiles/r05_solver_reg_steps.txt.  NEMPC_SOLVER_REG_RAISE / _RELAX are the A/B knobs.
-        static const double relax_env = [] { const char* e = getenv("NEMPC_SOLVER_REG_RELAX"); return e ? atof(e) : 0.31622776601683794; }();
-        a.reg_relax = relax_env > 0.0 && relax_env < 1.0 ? relax_env : 0.31622776601683794;
-        static const double raise_env = [] { const char* e = getenv("NEMPC_SOLVER_REG_RAISE"); return e ? atof(e) : 3.1622776601683795; }();
-        a.reg_raise = raise_env > 1.0 && raise_env <= 100.0 ? raise_env : 3.1622776601683795;
-    }
-    auto lqk = a.use_lds ? ((nx == 2 && nu == 1) ? solver_lq_kernel<T, 2, 1, true>
-                                                  : ((nx == 6 && nu == 3) ? solver_lq_kernel<T, 6, 3, true> : solver_lq_kernel<T, 0, 0, true>))
-                         : ((nx == 2 && nu == 1) ? solver_lq_kernel<T, 2, 1, false>
-                                                  : ((nx == 6 && nu == 3) ? solver_lq_kernel<T, 6, 3, false> : solver_lq_kernel<T, 0, 0, false>));
-    // wave-per-problem sweep when the working set is staged in LDS and a stage has enough entries to spread over a
-    // wave: 6/3 stages 6.5 k vs 5.0 k MPC solves/s at C3; 2/1 stages are 4 entries wide and stay on the
-    // thread-per-problem kernel (22.0 vs 23.1 ms per 40 iterations at C2).  nempc_solver_opts.lq_kernel forces one.
-    const bool lq_wave = a.use_lds && wave_wanted;
-    const int no_fuse_step = [] { const char* e = getenv("NEMPC_SOLVER_NO_FUSE_STEP"); return e ? atoi(e) : 0; }();   // (tests)
-    a.fuse_step = a.use_lds && !lq_wave && !no_fuse_step;
-    a.f_it = ws.f; a.Zt_it = ws.Zt;
-    if (a.fuse_step) NEMPC_HIP(hipMemsetAsync(ws.n_active, 0, 8 * sizeof(int), s));
-    if (lq_wave)
-        lqk = (nx == 2 && nu == 1) ? solver_lqw_kernel<T, 2, 1>
-                                   : ((nx == 6 && nu == 3) ? solver_lqw_kernel<T, 6, 3> : solver_lqw_kernel<T, 0, 0>);
-    if constexpr (sizeof(T) == 8)
-        if (lq_scan && a.use_lds && !lq_wave) lqk = solver_lq_kernel<T, 2, 1, true, true>;
-    {
-        const int ppw_max = (int)(lds_budget / ((size_t)per_problem * sizeof(T)));
-        const size_t lds_max = a.use_lds ? (size_t)std::min(std::max(ppw_max, 1), 16) * per_problem * sizeof(T) + wg_extra : 0;
-        NEMPC_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lqk), lds_max));
-    }
-
-    const int no_carry = [] { const char* e = getenv("NEMPC_SOLVER_NO_CARRY"); return e ? atoi(e) : 0; }();   // A/B knob (tests)
-    const int lsm_carry = o.linesearch == 0 ? (wave_wanted ? 1 : 2) : o.linesearch;
-    bool carry = lsm_carry == 2 && !no_carry && a.use_lds && h.variant == NEMPC_KERNEL_MFMA && h.cfg.integrator != NEMPC_RK4 &&
-                 !rolling;
-    int pend_seq = 0;             // sequence number of the inner loop's acceptance launches (published with their count)
-    bool have_eval = false;       // the evaluation buffers hold every active problem's current iterate
-    bool have_blocks = false;     // ... and so does the block buffer
-    // the trial point's Lagrangian blocks from the launch that evaluates it (compiled shape): an iteration is then the LQ
-    // solve, ONE callback launch and the acceptance test
-    const int hess_trial_env = [] { const char* e = getenv("NEMPC_SOLVER_HESS_TRIAL"); return e ? atoi(e) : 1; }();   // A/B knob (tests)
-    bool hess_trial = carry && a.fuse_step && hess_trial_env != 0;
-    a.carry = 0; a.tiles_t = ws.tiles_t; a.grad_t = ws.grad_t; a.lam_t = nullptr; a.hblk_t = nullptr;
-    // the acceptance test inside the next iteration's LQ kernel (see SolverArgs::accept_first): two launches per iteration
-    const int fuse_accept_env = [] { const char* e = getenv("NEMPC_SOLVER_FUSE_ACCEPT"); return e ? atoi(e) : 1; }();   // A/B knob (tests)
-    const bool fuse_accept = fuse_accept_env != 0;
-    static const bool stats_on = getenv("NEMPC_SOLVER_STATS") != nullptr;
-    bool accept_pending = false;       // the last trial point has been evaluated, its acceptance test has not been launched
-    a.accept_first = 0; a.n_active_prev = ws.n_active; a.gt_acc = ws.gt;
-    a.hpub = ws.hpub_dev;
-    for (int k = 0; k < 8; ++k) ws.hpub[k] = 0;       // (the previous solve on this handle ended with a synchronised stream)
-    const bool published_polls = !wave_wanted;  // small stages (chains of latency-bound launches): no blocking polls, the host
-                                                // reads the counter the device publishes
-    int Bact = B;                 // slots [0, Bact) may still be unconverged; compaction keeps them in front
-    int last_nact = B;            // unconverged problems at the last convergence poll
-    int it = 0, rc;
-    const int check = o.check_every > 0 ? o.check_every : 4;
-    static const int trace_slot = [] { const char* e = getenv("NEMPC_SOLVER_TRACE"); return e ? atoi(e) : -1; }();
-    const bool trace = trace_slot >= 0 && trace_slot < B;
-    // rolling: the callbacks read the caller's x0 / history by problem index, so the batch keeps its order (a finished
-    // problem is skipped by every solver kernel; its callback rows are evaluated and ignored)
-    const bool compact = o.compact != 0 && !trace && !rolling;
     // ---- callbacks.  Plain models: the handle's launches on the solver's buffers.  Rolling: gather the caller's
     //      variables, launch on them, spread the results into the window-state form (RollTables)
-    auto launch_rows = [&](int nb, const void* Zs, const void* X0s, void* g, void* tiles, void* tiles_scratch) -> int {
-        return h.variant != NEMPC_KERNEL_VALU ? launch_rows_mfma(h, nb, Zs, X0s, g, tiles, s)
-                                              : launch_rows_valu(h, nb, Zs, X0s, g, tiles ? tiles : tiles_scratch, s);
-    };
-    auto launch_blocks = [&](int nb, const void* Zs, const void* X0s, const void* lam, void* blocks) -> int {
-        return h.variant != NEMPC_KERNEL_VALU ? launch_rowhess_mfma(h, nb, Zs, X0s, lam, blocks, s)
-                                              : launch_rowhess_valu(h, nb, Zs, X0s, lam, blocks, s);
-    };
-    const unsigned gRn = (unsigned)(((size_t)B * n_r + 255) / 256);
-    // everything at an iterate: defects, tiles, f, gradient, Lagrangian blocks
-    auto roll_eval_iterate = [&](const void* Zaug, const void* lam_aug) -> int {
+    int launch_rows(int nb, const void* Zs, const void* X0s, void* g, void* tiles, void* tiles_scratch) {
+        if (h.variant != NEMPC_KERNEL_VALU) return launch_rows_mfma(h, nb, Zs, X0s, g, tiles, s);
+        return launch_rows_valu(h, nb, Zs, X0s, g, tiles ? tiles : tiles_scratch, s);
+    }
+    int launch_blocks(int nb, const void* Zs, const void* X0s, const void* lam, void* blocks) {
+        if (h.variant != NEMPC_KERNEL_VALU) return launch_rowhess_mfma(h, nb, Zs, X0s, lam, blocks, s);
+        return launch_rowhess_valu(h, nb, Zs, X0s, lam, blocks, s);
+    }
+    // everything at an iterate: defects, tiles, f, gradient, Lagrangian blocks (into the iterate's buffers); a trial point
+    // (lam_aug = null): defects only, into gt (the acceptance kernel evaluates the objective from the augmented table itself)
+    int roll_eval(const void* Zaug, const void* lam_aug) {
+        const bool full = lam_aug != nullptr;
         hipLaunchKernelGGL(roll_in_kernel<T>, dim3(gRn), dim3(256), 0, s, B, n, n_r, H, nx_r, nx, m_r, ws.rt, (const T*)Zaug,
-                           (T*)ws.rZ, (const T*)lam_aug, (T*)ws.rlam);
-        int r = launch_rows(B, ws.rZ, X0, ws.rg, ws.rtiles, nullptr);
+                           (T*)ws.rZ, (const T*)lam_aug, full ? (T*)ws.rlam : (T*)nullptr);
+        int r = launch_rows(B, ws.rZ, X0, ws.rg, full ? ws.rtiles : nullptr, h.d_tiles_ws);
         if (r) return r;
-        if ((r = launch_blocks(B, ws.rZ, X0, ws.rlam, ws.rhblk))) return r;
-        if ((r = launch_objective(h, B, ws.rZ, ws.f, ws.rgrad, s))) return r;
+        if (full && ((r = launch_blocks(B, ws.rZ, X0, ws.rlam, ws.rhblk)) || (r = launch_objective(h, B, ws.rZ, ws.f, ws.rgrad, s))))
+            return r;
         hipLaunchKernelGGL(roll_out_kernel<T>, dim3(B * H), dim3(256), 0, s, H, nx_r, nu, nx, nin_r, n_r, m_r, ws.rt,
-                           (const T*)Zaug, (const T*)ws.rS0, (const T*)ws.rg, (const T*)ws.rtiles, (const T*)ws.rhblk,
-                           (const T*)ws.rgrad, (T*)ws.g, (T*)ws.tiles, (T*)ws.hblk, (T*)ws.grad);
+                           (const T*)Zaug, (const T*)ws.rS0, (const T*)ws.rg, full ? (const T*)ws.rtiles : (const T*)nullptr,
+                           full ? (const T*)ws.rhblk : (const T*)nullptr, full ? (const T*)ws.rgrad : (const T*)nullptr,
+                           full ? (T*)ws.g : (T*)ws.gt, full ? (T*)ws.tiles : (T*)nullptr, full ? (T*)ws.hblk : (T*)nullptr,
+                           full ? (T*)ws.grad : (T*)nullptr);
         return NEMPC_OK;
-    };
-    // a trial point: defects only (the acceptance kernel evaluates the objective from the augmented table itself)
-    auto roll_eval_trial = [&](const void* Zaug) -> int {
-        hipLaunchKernelGGL(roll_in_kernel<T>, dim3(gRn), dim3(256), 0, s, B, n, n_r, H, nx_r, nx, m_r, ws.rt, (const T*)Zaug,
-                           (T*)ws.rZ, (const T*)nullptr, (T*)nullptr);
-        const int r = launch_rows(B, ws.rZ, X0, ws.rg, nullptr, h.d_tiles_ws);
-        if (r) return r;
-        hipLaunchKernelGGL(roll_out_kernel<T>, dim3(B * H), dim3(256), 0, s, H, nx_r, nu, nx, nin_r, n_r, m_r, ws.rt,
-                           (const T*)Zaug, (const T*)ws.rS0, (const T*)ws.rg, (const T*)nullptr, (const T*)nullptr,
-                           (const T*)nullptr, (T*)ws.gt, (T*)nullptr, (T*)nullptr, (T*)nullptr);
-        return NEMPC_OK;
-    };
+    }
     // (A block-wise mirrored convexification of the stage Hessians, for the problems whose sweep needed damping, was built and
     // measured in round 4 -- profiles/r04_solver_convexify_c3.txt: +3 - 5 % problems converged at 1.5 ms per iteration; removed
     // in round 5: indefiniteness is not what holds the configs[2] solves back, DESIGN "Batched solver".)
-    const bool soc_env = [] { const char* e = getenv("NEMPC_SOLVER_SOC"); return !(e && atoi(e) == 0); }();      // (read per solve)
-    for (; it < o.max_iter; ++it) {
-        a.B = Bact;
-        a.cur_it = it;
-        const size_t lds_need = a.use_lds ? (size_t)a.ppw * per_problem * sizeof(T) + wg_extra : 0;
-        const unsigned gAn = (unsigned)(((size_t)Bact * n + 255) / 256);
+    // callbacks at the iterate: defects + tiles (row kernel), f + grad (objective kernel)
+    // and the per-step Lagrangian blocks with the current multipliers (all zero on the first iterate:
+    // Gauss-Newton step).  The RK4 matrix-core pipeline produces defects, tiles and blocks from one row launch.
+    int evaluate_iterate() {
         void* Zc = ws.Zc[cur];
-        const void* X0c = ws.X0c[cur];
-        // callbacks at the iterate: defects + tiles (row kernel), f + grad (objective kernel)
-        // and the per-step Lagrangian blocks with the current multipliers (all zero on the first iterate:
-        // Gauss-Newton step).  The RK4 matrix-core pipeline produces defects, tiles and blocks from one row launch.
+        const void *X0c = ws.X0c[cur], *lam = ws.lamc[cur];
         const bool rk4_pipeline = h.variant != NEMPC_KERNEL_VALU && h.cfg.integrator == NEMPC_RK4;
         bool fused_eval = false;
+        int rc;
         if (rolling) {
             fused_eval = true;                  // (f and grad come with it)
-            rc = roll_eval_iterate(Zc, ws.lamc[cur]);
+            rc = roll_eval(Zc, lam);
         } else if (have_eval) {
             // deferred backtracking on a compiled shape: the trial evaluation of the last iteration was a full one and the
             // acceptance kernel kept, per problem, the evaluation of the point it stands on -- only the blocks are new, and
             // not even those when the trial launch computed them
             fused_eval = true;
-            rc = have_blocks ? NEMPC_OK
-                             : (h.variant != NEMPC_KERNEL_VALU ? launch_rowhess_mfma(h, Bact, Zc, X0c, ws.lamc[cur], ws.hblk, s)
-                                                               : launch_rowhess_valu(h, Bact, Zc, X0c, ws.lamc[cur], ws.hblk, s));
+            rc = have_blocks ? NEMPC_OK : launch_blocks(Bact, Zc, X0c, lam, ws.hblk);
         } else if (rk4_pipeline) {
-            rc = launch_rowhess_rk4_mfma(h, Bact, Zc, X0c, ws.lamc[cur], ws.hblk, s, ws.g, ws.tiles);
+            rc = launch_rowhess_rk4_mfma(h, Bact, Zc, X0c, lam, ws.hblk, s, ws.g, ws.tiles);
             if (rc == NEMPC_EUNSUPPORTED) {
                 // (a shape whose stage records would come from a wave-per-tile instantiation that is not used: rows through
                 //  the matrix-core entry point -- it falls back by itself -- and the blocks from the generic kernel)
                 if ((rc = launch_rows_mfma(h, Bact, Zc, X0c, ws.g, ws.tiles, s))) return rc;
-                rc = launch_rowhess_valu(h, Bact, Zc, X0c, ws.lamc[cur], ws.hblk, s);
+                rc = launch_rowhess_valu(h, Bact, Zc, X0c, lam, ws.hblk, s);
             }
         } else if (carry && hess_trial &&
-                   (rc = launch_rowhess_eval_mfma(h, Bact, Zc, X0c, ws.lamc[cur], ws.hblk, ws.g, ws.tiles, s)) != NEMPC_EUNSUPPORTED) {
+                   (rc = launch_rowhess_eval_mfma(h, Bact, Zc, X0c, lam, ws.hblk, ws.g, ws.tiles, s)) != NEMPC_EUNSUPPORTED) {
             // first iterate (and the one after a compaction) through the kernel the trial points go through -- the same
             // arithmetic whichever way an iterate's evaluation was obtained: blocks, defects, tiles; f and grad below
         } else {
             // compiled shapes: defects, tiles, f and grad from one launch
             fused_eval = h.variant == NEMPC_KERNEL_MFMA &&
                          (rc = launch_eval_fused(h, Bact, Zc, X0c, ws.g, ws.tiles, nullptr, ws.f, ws.grad, s)) != NEMPC_EUNSUPPORTED;
-            if (!fused_eval)
-                rc = h.variant != NEMPC_KERNEL_VALU ? launch_rows_mfma(h, Bact, Zc, X0c, ws.g, ws.tiles, s)
-                                                    : launch_rows_valu(h, Bact, Zc, X0c, ws.g, ws.tiles, s);
+            if (!fused_eval) rc = launch_rows(Bact, Zc, X0c, ws.g, ws.tiles, nullptr);
             if (rc) return rc;
-            rc = h.variant != NEMPC_KERNEL_VALU ? launch_rowhess_mfma(h, Bact, Zc, X0c, ws.lamc[cur], ws.hblk, s)
-                                                : launch_rowhess_valu(h, Bact, Zc, X0c, ws.lamc[cur], ws.hblk, s);
+            rc = launch_blocks(Bact, Zc, X0c, lam, ws.hblk);
         }
         if (rc) return rc;
-        if (!fused_eval && (rc = launch_objective(h, Bact, Zc, ws.f, ws.grad, s))) return rc;
+        return fused_eval ? NEMPC_OK : launch_objective(h, Bact, Zc, ws.f, ws.grad, s);
+    }
+    void launch_lq() {
         // bounds: barrier diagonal for the LQ model, barrier gradient folded into grad
-        if (!a.use_lds) hipLaunchKernelGGL(solver_barrier_kernel<T>, dim3(gAn), dim3(256), 0, s, a);
+        if (!a.use_lds)
+            hipLaunchKernelGGL(solver_barrier_kernel<T>, dim3((unsigned)(((size_t)Bact * n + 255) / 256)), dim3(256), 0, s, a);
         a.lam_t = carry && hess_trial ? ws.lam_t : nullptr;
         // this iteration's convergence counter; the pending acceptance (if any) publishes and clears the other word
-        a.n_active = fuse_accept && a.fuse_step ? ws.n_active + (it & 1) * 4 : ws.n_active;
+        a.n_active = kn.fuse_accept != 0 && a.fuse_step ? ws.n_active + (it & 1) * 4 : ws.n_active;
         a.n_active_prev = ws.n_active + ((it & 1) ^ 1) * 4;
         a.accept_first = accept_pending ? 1 : 0;
         accept_pending = false;
         // LDS mode: four waves stage the working set, the first ppw lanes run the sweeps
         hipLaunchKernelGGL(lqk, dim3(a.use_lds ? (Bact + a.ppw - 1) / a.ppw : (Bact + 63) / 64), dim3(a.use_lds ? 256 : 64),
-                           lds_need, s, a);
+                           a.use_lds ? lds_bytes(a.ppw) : 0, s, a);
 #ifdef NEMPC_LQ_STAMPS
         if (it == 3) {
             long long st[16];
@@ -2722,60 +2733,65 @@ static int solve_impl(Handle& h, int B, const void* X0, void* Z, const double* l
         }
 #endif
         if (!a.fuse_step)
-            hipLaunchKernelGGL(solver_step_kernel<T>, dim3(Bact), dim3(64), 0, s, a, (const T*)ws.f, (const T*)Zc, (T*)ws.Zt);
-        // Convergence poll.  Matrix-core-bound stages: a blocking copy every `check` iterations (an iteration is milliseconds,
-        // a drained stream costs nothing next to iterations at a stale batch size).  Small stages: see after the
-        // backtracking launches below.
-        bool polled = false;
-        int nact = Bact;
-        if (!published_polls && ((it + 1) % check == 0 || it + 1 == o.max_iter)) {
-            NEMPC_HIP(hipMemcpyAsync(ws.hpoll, ws.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
-            NEMPC_HIP(hipStreamSynchronize(s));
-            nact = ws.hpoll[0];
-            polled = true;
-            last_nact = nact;
-            // (report the iteration at which the last problem converged, as the published counter has it, not the poll's)
-            if (nact == 0) { it = ws.hpub[2] > 0 ? ws.hpub[2] : it + 1; break; }
+            hipLaunchKernelGGL(solver_step_kernel<T>, dim3(Bact), dim3(64), 0, s, a, (const T*)ws.f, (const T*)ws.Zc[cur], (T*)ws.Zt);
+    }
+    // Convergence poll.  Matrix-core-bound stages: a blocking copy every `check` iterations (an iteration is milliseconds,
+    // a drained stream costs nothing next to iterations at a stale batch size).  Small stages: poll_published, after the
+    // backtracking launches.
+    int poll_blocking() {
+        if ((it + 1) % (o.check_every > 0 ? o.check_every : 4) != 0 && it + 1 != o.max_iter) return NEMPC_OK;
+        NEMPC_HIP(hipMemcpyAsync(ws.hpoll, ws.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
+        NEMPC_HIP(hipStreamSynchronize(s));
+        last_nact = nact = ws.hpoll[0];
+        // (report the iteration at which the last problem converged, as the published counter has it, not the poll's)
+        if (nact == 0) { it = ws.hpub[2] > 0 ? ws.hpub[2] : it + 1; finished = true; }
+        return NEMPC_OK;
+    }
+    // wait until the device has published a value of hp[word] that satisfies `reached` (what, which: the error's words)
+    template <typename F> int wait_published(int word, F reached, const char* what, int which) {
+        const auto t0 = std::chrono::steady_clock::now();
+        long spins = 0;
+        while (!reached(hp[word])) {
+            cpu_relax();
+            if ((++spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(5)) {
+                NEMPC_HIP(hipStreamSynchronize(s));      // a device fault surfaces here instead of a hang
+                if (!reached(hp[word])) {
+                    set_error("nempc_solve: iteration " + std::to_string(it) + ": " + what + std::to_string(which) +
+                              " was never published (stream drained, word still " + std::to_string(hp[word]) + ")");
+                    return NEMPC_EHIP;
+                }
+            }
         }
-        // Backtracking in a lock-step batch.  An inner loop makes every problem pay for the one that needs six halvings
-        // (measured: 5.7 trial evaluations per iteration at B=1024, C2 dims, 70 % of the solve time).  DEFERRED (2): one
-        // trial per iteration; a problem whose trial is rejected stands still and retries the same direction at half the
-        // length next iteration.  ADAPTIVE (3): after the first trial, if fewer than a quarter of the active problems
-        // are still searching they are deferred, otherwise the loop goes on.  auto: matrix-core-bound iterations (6/3
-        // 3x128: a trial is 5 % of an iteration) keep the inner loop; small stages defer -- at equal wall time deferral
-        // converges more problems at every budget measured (2/1 2x64, B=1024: 1014 converged in 24.8 ms against 1004 in
-        // 24.9 ms), in the wide phase because a trial evaluation costs real time and among the stragglers because each
-        // extra trial is a latency-bound launch chain plus a host poll.  It spends more ITERATIONS on a hard problem
-        // (a retry is an iteration), so max_iter budgets are larger than with the inner loop.
-        // (rolling: one trial per iteration whatever was asked for -- the dense trial lists of the inner loop would need the
-        //  callbacks' x0 / history gathered per list)
+        return NEMPC_OK;
+    }
+    // the acceptance kernel publishes the number of problems still searching under a sequence number: wait for it
+    int poll_pending(int seq, int* out) {
+        const int rc = wait_published(4, [seq](int v) { return v == seq; }, "the backtracking counter of trial ", seq);
+        if (!rc) *out = hp[5];
+        return rc;
+    }
+    // Backtracking in a lock-step batch.  An inner loop makes every problem pay for the one that needs six halvings
+    // (measured: 5.7 trial evaluations per iteration at B=1024, C2 dims, 70 % of the solve time).  DEFERRED (2): one
+    // trial per iteration; a problem whose trial is rejected stands still and retries the same direction at half the
+    // length next iteration.  ADAPTIVE (3): after the first trial, if fewer than a quarter of the active problems
+    // are still searching they are deferred, otherwise the loop goes on.  auto: matrix-core-bound iterations (6/3
+    // 3x128: a trial is 5 % of an iteration) keep the inner loop; small stages defer -- at equal wall time deferral
+    // converges more problems at every budget measured (2/1 2x64, B=1024: 1014 converged in 24.8 ms against 1004 in
+    // 24.9 ms), in the wide phase because a trial evaluation costs real time and among the stragglers because each
+    // extra trial is a latency-bound launch chain plus a host poll.  It spends more ITERATIONS on a hard problem
+    // (a retry is an iteration), so max_iter budgets are larger than with the inner loop.
+    // (rolling: one trial per iteration whatever was asked for -- the dense trial lists of the inner loop would need the
+    //  callbacks' x0 / history gathered per list)
+    int line_search() {
+        void* Zc = ws.Zc[cur];
+        const void* X0c = ws.X0c[cur];
         const int lsm = rolling ? 2 : (o.linesearch == 0 ? (wave_wanted ? 1 : 2) : o.linesearch);
         // second-order correction of rejected full steps: inner-loop backtracking only (the deferred form accepts inside the
         // next LQ kernel); NEMPC_SOLVER_SOC=0 switches it off (A/B, tests)
-        const bool soc_on = lsm != 2 && !rolling && soc_env;
-        int pending = 0;
+        const bool soc_on = lsm != 2 && !rolling && kn.soc;
+        int pending = 0, rc = NEMPC_OK;
         int pflip = 0;          // which of the two lists of searching problems is read next (the correction stage swaps them)
-        const void* const extra_all = h.d_extra;
-        // the acceptance kernel publishes the number of problems still searching under a sequence number: wait for it
-        auto poll_pending = [&](int seq, int* out) -> int {
-            volatile int* hp = ws.hpub;
-            const auto t0 = std::chrono::steady_clock::now();
-            long spins = 0;
-            while (hp[4] != seq) {
-                cpu_relax();
-                if ((++spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(5)) {
-                    NEMPC_HIP(hipStreamSynchronize(s));      // a device fault surfaces here instead of a hang
-                    if (hp[4] != seq) {
-                        set_error("nempc_solve: iteration " + std::to_string(it) + ": the backtracking counter of trial " +
-                                  std::to_string(seq) + " was never published (stream drained, word still " +
-                                  std::to_string(hp[4]) + ")");
-                        return NEMPC_EHIP;
-                    }
-                }
-            }
-            *out = hp[5];
-            return NEMPC_OK;
-        };
+        const void* const extra_all = h.d_extra;      // (h.d_extra points at a dense list's extras around its launches only)
         for (int ls = 0; ls < o.max_linesearch; ++ls) {
             // the first trial point comes from solver_step_kernel (or the Riccati kernel), for every active problem; later
             // ones (inner-loop backtracking) are built here for the problems still searching ONLY, densely: their
@@ -2808,7 +2824,7 @@ static int solve_impl(Handle& h, int B, const void* X0, void* Z, const double* l
             }
             if (trial_done) {
             } else if (rolling) {
-                rc = roll_eval_trial(ws.Zt);
+                rc = roll_eval(ws.Zt, nullptr);
             } else {
                 if (!fused_trial)
                     fused_trial = h.variant == NEMPC_KERNEL_MFMA &&
@@ -2821,8 +2837,8 @@ static int solve_impl(Handle& h, int B, const void* X0, void* Z, const double* l
             // Deferred backtracking with the trial point's blocks in hand: the test runs at the start of the next LQ kernel,
             // unless this is the last iteration of the budget or somebody reads the iterate before that kernel (diagnostics;
             // a compaction launches it below)
-            accept_pending = fuse_accept && a.fuse_step && trial_done && lsm == 2 && published_polls && it + 1 < o.max_iter && !trace &&
-                             !stats_on;
+            accept_pending = kn.fuse_accept != 0 && a.fuse_step && trial_done && lsm == 2 && published_polls && it + 1 < o.max_iter && !trace &&
+                             !kn.stats;
             if (!accept_pending)
                 hipLaunchKernelGGL(solver_merit_kernel<T>, dim3(nb), dim3(64), 0, s, a, (const T*)ws.Zt,
                                    (const T*)ws.gt, fused_trial ? (const T*)ws.ft : (const T*)nullptr, (T*)Zc,
@@ -2858,41 +2874,28 @@ static int solve_impl(Handle& h, int B, const void* X0, void* Z, const double* l
                 break;
             }
         }
-        if (published_polls) {
-            // Small stages: an iteration is a chain of latency-bound launches, and a blocking poll drains the stream (10
-            // polls of ~25 us in a 5.5 ms solve).  The acceptance kernel PUBLISHES the iteration's counter to pinned host
-            // memory; the host only makes sure it never runs more than two iterations ahead of the device (it would
-            // otherwise queue its whole budget before the first problem converges) and takes whatever the slot holds:
-            // a count a couple of iterations old is an upper bound of the unconverged problems (they only ever leave),
-            // which is all compaction needs, and "none left" is reported with the iteration at which it happened.
-            volatile int* hp = ws.hpub;
-            const int want = it + 1 - 2;
-            if (want > 0) {
-                const auto t0 = std::chrono::steady_clock::now();
-                long spins = 0;
-                while (hp[0] < want) {
-                    cpu_relax();
-                    if ((++spins & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(5)) {
-                        NEMPC_HIP(hipStreamSynchronize(s));      // a device fault surfaces here instead of a hang
-                        if (hp[0] < want) {
-                            set_error("nempc_solve: iteration " + std::to_string(it) + ": the convergence counter of iteration " +
-                                      std::to_string(want) + " was never published (stream drained, word still " +
-                                      std::to_string(hp[0]) + ")");
-                            return NEMPC_EHIP;
-                        }
-                    }
-                }
-            }
-            if (hp[0] > 0) {
-                if (hp[2] > 0) { it = hp[2]; break; }      // every problem had converged at that iteration
-                nact = hp[1];
-                polled = true;
-                last_nact = nact;
-            }
+        return NEMPC_OK;
+    }
+    // Small stages: an iteration is a chain of latency-bound launches, and a blocking poll drains the stream (10
+    // polls of ~25 us in a 5.5 ms solve).  The acceptance kernel PUBLISHES the iteration's counter to pinned host
+    // memory; the host only makes sure it never runs more than two iterations ahead of the device (it would
+    // otherwise queue its whole budget before the first problem converges) and takes whatever the slot holds:
+    // a count a couple of iterations old is an upper bound of the unconverged problems (they only ever leave),
+    // which is all compaction needs, and "none left" is reported with the iteration at which it happened.
+    int poll_published() {
+        const int want = it + 1 - 2;
+        if (want > 0)
+            if (const int rc = wait_published(0, [want](int v) { return v >= want; }, "the convergence counter of iteration ", want))
+                return rc;
+        if (hp[0] > 0) {
+            if (hp[2] > 0) { it = hp[2]; finished = true; return NEMPC_OK; }      // every problem had converged at that iteration
+            last_nact = nact = hp[1];
         }
-        if (stats_on) {   // NEMPC_SOLVER_STATS=1: Riccati restarts per iteration over the active slots (diagnostic, synchronises)
-            std::vector<T> inf((size_t)Bact * INFO_N);
-            std::vector<T> rg((size_t)Bact);
+        return NEMPC_OK;
+    }
+    int diagnostics() {
+        if (kn.stats) {   // NEMPC_SOLVER_STATS=1: Riccati restarts per iteration over the active slots (diagnostic, synchronises)
+            std::vector<T> inf((size_t)Bact * INFO_N), rg((size_t)Bact);
             NEMPC_HIP(hipStreamSynchronize(s));
             NEMPC_HIP(hipMemcpy(inf.data(), a.info, inf.size() * sizeof(T), hipMemcpyDeviceToHost));
             NEMPC_HIP(hipMemcpy(rg.data(), a.reg, rg.size() * sizeof(T), hipMemcpyDeviceToHost));
@@ -2907,91 +2910,91 @@ static int solve_impl(Handle& h, int B, const void* X0, void* Z, const double* l
         if (trace) {   // NEMPC_SOLVER_TRACE=<slot>: one line per iteration for that slot (diagnostic, synchronises)
             T inf[INFO_N], muv, alv, regv, penv; int st, lsd;
             NEMPC_HIP(hipStreamSynchronize(s));
-            NEMPC_HIP(hipMemcpy(inf, (const T*)a.info + (size_t)trace_slot * INFO_N, sizeof(inf), hipMemcpyDeviceToHost));
-            NEMPC_HIP(hipMemcpy(&muv, (const T*)a.mu + trace_slot, sizeof(T), hipMemcpyDeviceToHost));
-            NEMPC_HIP(hipMemcpy(&alv, (const T*)a.alpha + trace_slot, sizeof(T), hipMemcpyDeviceToHost));
-            NEMPC_HIP(hipMemcpy(&regv, (const T*)a.reg + trace_slot, sizeof(T), hipMemcpyDeviceToHost));
-            NEMPC_HIP(hipMemcpy(&penv, (const T*)a.pen + trace_slot, sizeof(T), hipMemcpyDeviceToHost));
-            NEMPC_HIP(hipMemcpy(&st, a.status + trace_slot, sizeof(int), hipMemcpyDeviceToHost));
-            NEMPC_HIP(hipMemcpy(&lsd, a.lsdone + trace_slot, sizeof(int), hipMemcpyDeviceToHost));
+            NEMPC_HIP(hipMemcpy(inf, (const T*)a.info + (size_t)kn.trace_slot * INFO_N, sizeof(inf), hipMemcpyDeviceToHost));
+            NEMPC_HIP(hipMemcpy(&muv, (const T*)a.mu + kn.trace_slot, sizeof(T), hipMemcpyDeviceToHost));
+            NEMPC_HIP(hipMemcpy(&alv, (const T*)a.alpha + kn.trace_slot, sizeof(T), hipMemcpyDeviceToHost));
+            NEMPC_HIP(hipMemcpy(&regv, (const T*)a.reg + kn.trace_slot, sizeof(T), hipMemcpyDeviceToHost));
+            NEMPC_HIP(hipMemcpy(&penv, (const T*)a.pen + kn.trace_slot, sizeof(T), hipMemcpyDeviceToHost));
+            NEMPC_HIP(hipMemcpy(&st, a.status + kn.trace_slot, sizeof(int), hipMemcpyDeviceToHost));
+            NEMPC_HIP(hipMemcpy(&lsd, a.lsdone + kn.trace_slot, sizeof(int), hipMemcpyDeviceToHost));
             fprintf(stderr, "[solver it %3d slot %d] mu %.2e step %.2e ginf %.2e lam %.2e amax %.2e alpha %.2e reg %.1e pen %.2e restarts %.0f status %d lsdone %d\n",
-                    it, trace_slot, (double)muv, (double)inf[INFO_STEP], (double)inf[INFO_GINF], (double)inf[INFO_LAM],
+                    it, kn.trace_slot, (double)muv, (double)inf[INFO_STEP], (double)inf[INFO_GINF], (double)inf[INFO_LAM],
                     (double)inf[INFO_AMAX], (double)alv, (double)regv, (double)penv, (double)inf[INFO_RESTARTS], st, lsd);
         }
-        // ---- compaction: once a quarter of the active slots has finished, gather the unconverged problems to the
-        //      front of the other buffer set and shrink every launch to them
-        if (compact && polled && nact < Bact - Bact / 4 && Bact > 64) {
-            if (accept_pending) {       // the gather below reads the iterate: the trial's acceptance test now, in a launch of its own
-                hipLaunchKernelGGL(solver_merit_kernel<T>, dim3(Bact), dim3(64), 0, s, a, (const T*)ws.Zt, (const T*)ws.gt,
-                                   (const T*)nullptr, (T*)Zc, 2, (const int*)nullptr, ws.pend[1], 1, 0);
-                accept_pending = false;
-            }
-            const int nxt = cur ^ 1;
-            hipLaunchKernelGGL(solver_partition_kernel, dim3(1), dim3(1024), 0, s, Bact, (const int*)ws.stc[cur], ws.perm,
-                               ws.count);
-            CompactArrays ca{};
-            int k = 0;
-            auto add = [&](const void* src, void* dst, int per, int esz) {
-                ca.src[k] = src; ca.dst[k] = dst; ca.per[k] = per; ca.esz[k] = esz; ++k;
-            };
-            add(ws.Zc[cur], ws.Zc[nxt], n, sizeof(T));
-            add(ws.X0c[cur], ws.X0c[nxt], nx, sizeof(T));
-            add(ws.lamc[cur], ws.lamc[nxt], m, sizeof(T));
-            add(ws.muc[cur], ws.muc[nxt], 1, sizeof(T));
-            add(ws.nuc[cur], ws.nuc[nxt], 1, sizeof(T));
-            add(ws.regc[cur], ws.regc[nxt], 1, sizeof(T));
-            add(ws.stc[cur], ws.stc[nxt], 1, sizeof(int));
-            add(ws.orig[cur], ws.orig[nxt], 1, sizeof(int));
-            add(ws.itc[cur], ws.itc[nxt], 1, sizeof(int));
-            add(ws.infoc[cur], ws.infoc[nxt], INFO_N, sizeof(T));
-            add(ws.zlc[cur], ws.zlc[nxt], n, sizeof(T));
-            add(ws.zuc[cur], ws.zuc[nxt], n, sizeof(T));
-            if (ex_per) add(ws.exc[cur], ws.exc[nxt], (int)ex_per, sizeof(T));
-            ca.n = k;
-            hipLaunchKernelGGL(solver_gather_kernel, dim3(Bact), dim3(256), 0, s, Bact, (const int*)ws.perm, ca);
-            // slots [Bact, B) hold problems that finished before earlier compactions: carry them over unchanged
-            if (Bact < B) {
-                const size_t rest = (size_t)(B - Bact);
-                NEMPC_HIP(hipMemcpyAsync((T*)ws.Zc[nxt] + (size_t)Bact * n, (const T*)ws.Zc[cur] + (size_t)Bact * n,
-                                         rest * n * sizeof(T), hipMemcpyDeviceToDevice, s));
-                NEMPC_HIP(hipMemcpyAsync(ws.stc[nxt] + Bact, ws.stc[cur] + Bact, rest * sizeof(int), hipMemcpyDeviceToDevice, s));
-                NEMPC_HIP(hipMemcpyAsync(ws.orig[nxt] + Bact, ws.orig[cur] + Bact, rest * sizeof(int), hipMemcpyDeviceToDevice, s));
-                NEMPC_HIP(hipMemcpyAsync(ws.itc[nxt] + Bact, ws.itc[cur] + Bact, rest * sizeof(int), hipMemcpyDeviceToDevice, s));
-            }
-            // the unconverged problems now sit in front.  Their exact number is on the device; the host shrinks the
-            // launches to the counter it has just read -- taken a period earlier, so an upper bound (problems only ever
-            // leave the active set): a few finished problems ride along in the active prefix and are skipped by every
-            // kernel, and no stream synchronisation is needed to learn the exact count
-            cur = nxt;
-            point_at(cur);
-            have_eval = false;            // (the evaluation buffers are not gathered: one launch after a compaction)
-            have_blocks = false;
-            if (published_polls) {
-                Bact = nact > 0 ? (nact < Bact ? nact : Bact) : 1;
-            } else {
-                NEMPC_HIP(hipMemcpyAsync(ws.hpoll, ws.count, sizeof(int), hipMemcpyDeviceToHost, s));
-                NEMPC_HIP(hipStreamSynchronize(s));
-                Bact = ws.hpoll[0] > 0 ? ws.hpoll[0] : 1;
-            }
-            a.ppw = pick_ppw(Bact);
-        }
+        return NEMPC_OK;
     }
-    if (accept_pending) {           // (the loop was left with a trial point evaluated and not yet tested)
+    // the acceptance test of a trial point that was left to the next LQ kernel, in a launch of its own
+    void accept_now() {
         hipLaunchKernelGGL(solver_merit_kernel<T>, dim3(a.B), dim3(64), 0, s, a, (const T*)ws.Zt, (const T*)ws.gt,
                            (const T*)nullptr, (T*)ws.Zc[cur], 2, (const int*)nullptr, ws.pend[1], 1, 0);
         accept_pending = false;
     }
-    hipLaunchKernelGGL(solver_scatter_kernel<T>, dim3(B), dim3(256), 0, s, B, n, (const T*)ws.Zc[cur],
-                       (const int*)ws.stc[cur], (const int*)ws.orig[cur], (const int*)ws.itc[cur],
-                       rolling ? (T*)ws.rZout : (T*)Z, status_dev, (int*)o.iters_out);
-    if (rolling)      // the caller's variables are the primary copies
-        hipLaunchKernelGGL(roll_in_kernel<T>, dim3(gRn), dim3(256), 0, s, B, n, n_r, H, nx_r, nx, m_r, ws.rt, (const T*)ws.rZout,
-                           (T*)Z, (const T*)nullptr, (T*)nullptr);
-    NEMPC_HIP(hipGetLastError());
-    NEMPC_HIP(hipStreamSynchronize(s));
-    if (iters_host) *iters_host = it;
-    return NEMPC_OK;
-}
+    // ---- compaction: gather the unconverged problems to the front of the other buffer set
+    int compact_batch() {
+        if (accept_pending) accept_now();       // the gather below reads the iterate
+        const int nxt = cur ^ 1;
+        hipLaunchKernelGGL(solver_partition_kernel, dim3(1), dim3(1024), 0, s, Bact, (const int*)ws.stc[cur], ws.perm,
+                           ws.count);
+        CompactArrays ca{};
+        int k = 0;
+        auto add = [&](const void* src, void* dst, int per, int esz) { ca.src[k] = src; ca.dst[k] = dst; ca.per[k] = per; ca.esz[k] = esz; ++k; };
+        add(ws.Zc[cur], ws.Zc[nxt], n, sizeof(T));
+        add(ws.X0c[cur], ws.X0c[nxt], nx, sizeof(T));
+        add(ws.lamc[cur], ws.lamc[nxt], m, sizeof(T));
+        add(ws.muc[cur], ws.muc[nxt], 1, sizeof(T));
+        add(ws.nuc[cur], ws.nuc[nxt], 1, sizeof(T));
+        add(ws.regc[cur], ws.regc[nxt], 1, sizeof(T));
+        add(ws.stc[cur], ws.stc[nxt], 1, sizeof(int));
+        add(ws.orig[cur], ws.orig[nxt], 1, sizeof(int));
+        add(ws.itc[cur], ws.itc[nxt], 1, sizeof(int));
+        add(ws.infoc[cur], ws.infoc[nxt], INFO_N, sizeof(T));
+        add(ws.zlc[cur], ws.zlc[nxt], n, sizeof(T));
+        add(ws.zuc[cur], ws.zuc[nxt], n, sizeof(T));
+        if (ex_per) add(ws.exc[cur], ws.exc[nxt], (int)ex_per, sizeof(T));
+        ca.n = k;
+        hipLaunchKernelGGL(solver_gather_kernel, dim3(Bact), dim3(256), 0, s, Bact, (const int*)ws.perm, ca);
+        // slots [Bact, B) hold problems that finished before earlier compactions: carry them over unchanged
+        if (Bact < B) {
+            const size_t rest = (size_t)(B - Bact);
+            NEMPC_HIP(hipMemcpyAsync((T*)ws.Zc[nxt] + (size_t)Bact * n, (const T*)ws.Zc[cur] + (size_t)Bact * n,
+                                     rest * n * sizeof(T), hipMemcpyDeviceToDevice, s));
+            NEMPC_HIP(hipMemcpyAsync(ws.stc[nxt] + Bact, ws.stc[cur] + Bact, rest * sizeof(int), hipMemcpyDeviceToDevice, s));
+            NEMPC_HIP(hipMemcpyAsync(ws.orig[nxt] + Bact, ws.orig[cur] + Bact, rest * sizeof(int), hipMemcpyDeviceToDevice, s));
+            NEMPC_HIP(hipMemcpyAsync(ws.itc[nxt] + Bact, ws.itc[cur] + Bact, rest * sizeof(int), hipMemcpyDeviceToDevice, s));
+        }
+        // the unconverged problems now sit in front.  Their exact number is on the device; the host shrinks the
+        // launches to the counter it has just read -- taken a period earlier, so an upper bound (problems only ever
+        // leave the active set): a few finished problems ride along in the active prefix and are skipped by every
+        // kernel, and no stream synchronisation is needed to learn the exact count
+        cur = nxt;
+        point_at(cur);
+        have_eval = have_blocks = false;            // (the evaluation buffers are not gathered: one launch after a compaction)
+        if (published_polls) {
+            Bact = nact > 0 ? (nact < Bact ? nact : Bact) : 1;
+        } else {
+            NEMPC_HIP(hipMemcpyAsync(ws.hpoll, ws.count, sizeof(int), hipMemcpyDeviceToHost, s));
+            NEMPC_HIP(hipStreamSynchronize(s));
+            Bact = ws.hpoll[0] > 0 ? ws.hpoll[0] : 1;
+        }
+        a.ppw = pick_ppw(Bact);
+        return NEMPC_OK;
+    }
+    // results back in the caller's order
+    int finish(void* Z, int32_t* status_dev, int32_t* iters_host) {
+        if (accept_pending) accept_now();           // (the loop was left with a trial point evaluated and not yet tested)
+        hipLaunchKernelGGL(solver_scatter_kernel<T>, dim3(B), dim3(256), 0, s, B, n, (const T*)ws.Zc[cur],
+                           (const int*)ws.stc[cur], (const int*)ws.orig[cur], (const int*)ws.itc[cur],
+                           rolling ? (T*)ws.rZout : (T*)Z, status_dev, (int*)o.iters_out);
+        if (rolling)      // the caller's variables are the primary copies
+            hipLaunchKernelGGL(roll_in_kernel<T>, dim3(gRn), dim3(256), 0, s, B, n, n_r, H, nx_r, nx, m_r, ws.rt, (const T*)ws.rZout,
+                               (T*)Z, (const T*)nullptr, (T*)nullptr);
+        NEMPC_HIP(hipGetLastError());
+        NEMPC_HIP(hipStreamSynchronize(s));
+        if (iters_host) *iters_host = it;
+        return NEMPC_OK;
+    }
+};
+}  // namespace
 
 // Every exit of a failed solve leaves the handle as a finished one does: kernels that still write the published words
 // (hpub) and the device counters may be queued when an error return is taken from inside the iteration loop, and the
@@ -2999,7 +3002,7 @@ static int solve_impl(Handle& h, int B, const void* X0, void* Z, const double* l
 template <typename T>
 static int solve_typed(Handle& h, int B, const void* X0, void* Z, const double* lb, const double* ub,
                        const nempc_solver_opts& o, int32_t* status_dev, int32_t* iters_host, hipStream_t s) {
-    const int rc = solve_impl<T>(h, B, X0, Z, lb, ub, o, status_dev, iters_host, s);
+    const int rc = Solve<T>(h, B, X0, o, s).run(Z, lb, ub, status_dev, iters_host);
     if (rc != NEMPC_OK) {
         (void)hipStreamSynchronize(s);
         if (SolverWs* w = static_cast<SolverWs*>(h.solver_ws)) {
