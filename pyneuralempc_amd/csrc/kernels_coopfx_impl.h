@@ -13,6 +13,8 @@
 // kernels_coop_impl.h); results agree with it to rounding (the K-split partial sums are added in the same order).
 #pragma once
 
+#include <cstddef>
+
 #include "kernels_coop_impl.h"
 #include "kernels_obj_impl.h"
 
@@ -35,6 +37,26 @@
 #else
 #define FX_STAMP_PASS(p, i) COOP_WGSTAMP(p, i)
 #define FX_STAMP_PRO(p, i) do { } while (0)
+#endif
+// The timeline pointer is a late argument (FxArgs::dbg): read at entry, its scalar load and the wait for it stood in
+// front of every load of the prologue, and the stamps measured a wait the shipped kernel does not have.  The stamps taken
+// before the last load is issued are held in registers (FX_TAKE*) and written once the pointer has been fetched behind it.
+#if defined(NEMPC_STAMPS) && !defined(NEMPC_STAMPS_NO_FX)
+#define FX_TAKE(i)                                     \
+    do {                                               \
+        __builtin_amdgcn_sched_barrier(0);             \
+        pro_t[i] = (long long)__builtin_amdgcn_s_memtime(); \
+        __builtin_amdgcn_sched_barrier(0);             \
+    } while (0)
+#else
+#define FX_TAKE(i) do { } while (0)
+#endif
+#ifdef NEMPC_STAMPS_PRO
+#define FX_TAKE_PASS(i) do { } while (0)
+#define FX_TAKE_PRO(i) FX_TAKE(i)
+#else
+#define FX_TAKE_PASS(i) FX_TAKE(i)
+#define FX_TAKE_PRO(i) do { } while (0)
 #endif
 
 // (Raised wave priority -- s_setprio -- over the matrix-instruction blocks was measured in round 4: 15.89 / 15.93 us against
@@ -118,7 +140,14 @@ struct FxArgs {   // host-prepared; the fields the first loads need come first
 // into vector lanes: a cold round trip (0.3-0.5 us) in front of the very first vector load.  What the prologue needs
 // travels in the preloaded leading arguments; the rest -- output pointers, m, box, ... -- is only used by a pass's
 // epilogue and is read THERE through the kernarg segment pointer (the empty asm pins the earliest point).
-constexpr int FX_ARGS_KERNARG_OFFSET = 64;      // five pointers, four dwords and the dense-matrix pointer precede the FxArgs argument
+// (the kernel's leading arguments as the kernarg segment lays them out; the kernel static_asserts the two offsets against it)
+struct FxLeadArgs {
+    const void *Z, *X0, *small, *wslice, *P;
+    unsigned pack, R, invH, Hgrid;
+    void* jac;
+};
+constexpr int FX_ARGS_KERNARG_OFFSET = 64;      // the FxArgs argument follows the leading ones
+constexpr int FX_PJAC_KERNARG_OFFSET = 56;      // the dense-matrix pointer, the first leading argument beyond the preloaded ones
 typedef const FxArgs __attribute__((address_space(4)))* FxArgsK;
 __device__ __forceinline__ FxArgsK fx_late_args() {
     const char __attribute__((address_space(4)))* kp =
@@ -708,9 +737,14 @@ template <typename T, int WP, int NH, int TPW, int NX, int NU, bool FUSE, int AC
 __global__ __launch_bounds__((WP / 16) * 64, 2) void rows_coopfx_kernel(
     // what the prologue's loads depend on, as plain arguments: with -amdgpu-kernarg-preload-count the leading 14 dwords are
     // in scalar registers when the wave starts instead of behind a scalar-load round trip (the struct carries the rest;
-    // n and the objective table's offsets follow from H and the compiled shape)
+    // n and the objective table's offsets follow from H and the compiled shape).  The 14 are full: the horizon and the
+    // grid size share the last one (pHgrid = H | grid << 16), and pjac, the 15th / 16th dword, is a scalar load
     const void* pZ, const void* pX0, const void* psmall, const void* pwslice, const void* pP, unsigned ppack, unsigned pR,
-    unsigned pinvH, int pH, void* pjac, FxArgs a) {
+    unsigned pinvH, unsigned pHgrid, void* pjac, FxArgs a) {
+    static_assert(offsetof(FxLeadArgs, jac) == FX_PJAC_KERNARG_OFFSET && sizeof(FxLeadArgs) == FX_ARGS_KERNARG_OFFSET,
+                  "the kernarg offsets read by hand (fx_late_args, pjac) follow the leading arguments: keep FxLeadArgs in step");
+    const int pH = (int)(pHgrid & 0xffffu);
+    const unsigned pgrid = pHgrid >> 16;
     // `a` itself is never read here (see fx_late_args); a local block holds what the preloaded arguments say
     struct {
         const void *Z, *X0, *small, *wslice, *P;
@@ -732,17 +766,12 @@ __global__ __launch_bounds__((WP / 16) * 64, 2) void rows_coopfx_kernel(
     pa.R = pR; pa.invH = pinvH; pa.H = pH; pa.n = pH * (NX + NU);
     pa.oo = obj_offsets(pH, NX, NU);
     pa.p_elems = FUSE ? pa.oo.total : 0;
-#ifdef NEMPC_STAMPS
-    pa.dbg = a.dbg;
-#else
     pa.dbg = nullptr;
     (void)a;
-#endif
-    COOP_WGSTAMP(pa.dbg, 0);
 #if defined(NEMPC_STAMPS) && !defined(NEMPC_STAMPS_NO_FX)
-    if (pa.dbg && threadIdx.x == 0 && blockIdx.x < 4096)
-        pa.dbg[1024 + blockIdx.x * 16 + 15] = ((long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned)__builtin_amdgcn_s_getreg(63492);
+    long long pro_t[5] = {0, 0, 0, 0, 0};
 #endif
+    FX_TAKE(0);
     using L = FxLayout<T, WP, NH, TPW, NX, NU>;
     constexpr int MT = WP / 16;
     constexpr int NTHREADS = MT * 64;
@@ -760,7 +789,8 @@ __global__ __launch_bounds__((WP / 16) * 64, 2) void rows_coopfx_kernel(
     cx.Z = static_cast<const T*>(pa.Z);
     cx.X0 = static_cast<const T*>(pa.X0);
     cx.R = pa.R; cx.invH = pa.invH; cx.H = pa.H; cx.n = pa.n; cx.rev = want_rev;
-    cx.jac = FUSE ? static_cast<T*>(pjac) : nullptr;
+    cx.jac = nullptr;       // (FUSE: fetched behind the prologue's last vector load)
+    (void)pjac;
     cx.box = has_box;
 
     const int t_begin = blockIdx.x * pa.tiles_per_wg + ((int)blockIdx.x < pa.tiles_rem ? (int)blockIdx.x : pa.tiles_rem);
@@ -771,7 +801,7 @@ __global__ __launch_bounds__((WP / 16) * 64, 2) void rows_coopfx_kernel(
     FxStage<T, TPW, NTHREADS, NCOL> sr;
     int t0 = t_begin;
     fx_stage_load<T, WP, NH, TPW, NX, NU, TPW>(cx, t0, tid, sr);
-    FX_STAMP_PRO(pa.dbg, 1);
+    FX_TAKE_PRO(1);
     constexpr int SMALL_VECS = (L::SMALL_END + VEC - 1) / VEC;
     constexpr int SMALL_PER_THREAD = (SMALL_VECS + NTHREADS - 1) / NTHREADS;
     vecT sm[SMALL_PER_THREAD];
@@ -783,7 +813,7 @@ __global__ __launch_bounds__((WP / 16) * 64, 2) void rows_coopfx_kernel(
             if (idx < SMALL_VECS) sm[u] = gs[idx];
         }
     }
-    FX_STAMP_PRO(pa.dbg, 2);
+    FX_TAKE_PRO(2);
     // fused evaluation: the objective.  A problem belongs to the workgroup whose tile range holds its first row.  WHO
     // evaluates it: the two workgroups of a CU do not interleave -- the one dispatched first (the first half of the grid)
     // runs its passes at nearly full speed and is done ~1.5 us before the other, which fills gaps and finishes last
@@ -793,11 +823,13 @@ __global__ __launch_bounds__((WP / 16) * 64, 2) void rows_coopfx_kernel(
     // evaluate at their END the problems of BOTH members of a pair (i, i + ceil(grid / 2)); the second half evaluates
     // none.  Both ranges' variables -- two contiguous pieces of Z -- are fetched in the prologue and parked in LDS next
     // to the objective's table (evaluated from global memory it cost a round trip of its own wherever it stood).
-    // Everything these loads need is among the preloaded arguments, so they go out without waiting for the argument block.
+    // Everything these loads need is among the preloaded arguments, so they go out without waiting for the argument block
+    // -- the grid size included: read from the dispatch (gridDim.x) it was a scalar load whose cold round trip stood in
+    // front of these loads and of the weight slices behind them.
     // (the ranges are recomputed where they are used, at the end of the kernel: kept live across the passes they cost
     // scalar registers the pass code then spills)
     auto obj_range = [&](int side, unsigned& lo, unsigned& hi, int& nlds) {
-        const unsigned half_lo = gridDim.x / 2u, half_hi = gridDim.x - half_lo;
+        const unsigned half_lo = pgrid / 2u, half_hi = pgrid - half_lo;
         const unsigned Hh = (unsigned)pa.H;
         const unsigned wg = side == 0 ? blockIdx.x : blockIdx.x + half_hi;       // the partner's index
         const bool have = blockIdx.x < half_hi && (side == 0 || blockIdx.x < half_lo);
@@ -842,7 +874,7 @@ __global__ __launch_bounds__((WP / 16) * 64, 2) void rows_coopfx_kernel(
             pv[u] = idx < pa.p_elems ? gp[idx] : T(0);
         }
     }
-    FX_STAMP_PRO(pa.dbg, 3);
+    FX_TAKE_PRO(3);
     constexpr int NFRAG = (NH - 1) * 2 * MT * 4 + 8;
     constexpr int NLOAD = (NFRAG + VEC - 1) / VEC;
     vecT wv[NLOAD];
@@ -851,8 +883,30 @@ __global__ __launch_bounds__((WP / 16) * 64, 2) void rows_coopfx_kernel(
 #pragma unroll
         for (int k = 0; k < NLOAD; ++k) wv[k] = ws[k * 64];
     }
-    FX_STAMP_PASS(pa.dbg, 1);
-    FX_STAMP_PRO(pa.dbg, 4);
+    FX_TAKE_PASS(1);
+    FX_TAKE_PRO(4);
+    if constexpr (FUSE) {
+        // pjac, first used behind layer 0 (fx_zero_rows), is the one scalar load of the prologue.  Left to the compiler
+        // it was issued, and waited for, between the LDS stores and the first barrier: a second cold round trip behind
+        // the vector loads' one.  Asked for here, behind the last vector load, it returns while those are in flight.
+        // (Read through the pinned segment pointer: as the plain argument its load has no place of its own, and the
+        // scheduler puts it between the vector loads.)
+        const char __attribute__((address_space(4)))* kp =
+            (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kp)::"memory");
+        T* const jac = *(T* const __attribute__((address_space(4)))*)(kp + FX_PJAC_KERNARG_OFFSET);
+        asm volatile("" ::"s"(jac) : "memory");
+        cx.jac = jac;
+    }
+#if defined(NEMPC_STAMPS) && !defined(NEMPC_STAMPS_NO_FX)
+    pa.dbg = fx_late_args()->dbg;
+    if (pa.dbg && threadIdx.x == 0 && blockIdx.x < 4096) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i)
+            if (pro_t[i]) pa.dbg[1024 + blockIdx.x * 16 + i] = pro_t[i];
+        pa.dbg[1024 + blockIdx.x * 16 + 15] = ((long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned)__builtin_amdgcn_s_getreg(63492);
+    }
+#endif
     cx.dbg = pa.dbg;
     {
         vecT* ls = reinterpret_cast<vecT*>(lds + L::W0F);
@@ -930,7 +984,7 @@ __global__ __launch_bounds__((WP / 16) * 64, 2) void rows_coopfx_kernel(
         parity ^= 1;
     }
     if constexpr (FUSE) {
-        if (want_obj && blockIdx.x < gridDim.x - gridDim.x / 2u) {
+        if (want_obj && blockIdx.x < pgrid - pgrid / 2u) {
             const FxArgsK ka = fx_late_args();
             T* const o_f = static_cast<T*>(ka->f);
             T* const o_grad = static_cast<T*>(ka->grad);

@@ -144,13 +144,15 @@ int launch_coopfx(const MfmaParams& p, hipStream_t s) {
             return NEMPC_EUNSUPPORTED;
     }
     // the leading arguments (preloaded into scalar registers) repeat what the prologue's loads depend on; three small
-    // integers and the two "objective wanted" bits share a dword
-    if (a.tiles_per_wg > 0xff || a.tiles_rem > 0x3ff || a.zp_max > 0x3ff || a.n != p.H * (NX + NU)) return NEMPC_EUNSUPPORTED;
+    // integers and the two "objective wanted" bits share a dword, the horizon and the grid size another (the kernel pairs
+    // workgroup i with i + ceil(grid / 2) for the objective and must not wait for the dispatch's own copy of the grid size)
+    if (a.tiles_per_wg > 0xff || a.tiles_rem > 0x3ff || a.zp_max > 0x3ff || a.n != p.H * (NX + NU) || p.H > 0xffff || grid > 0xffff)
+        return NEMPC_EUNSUPPORTED;
     const unsigned pack = (unsigned)a.tiles_per_wg | ((unsigned)a.tiles_rem << 8) | ((unsigned)a.zp_max << 18) |
                           (a.f ? 1u << 28 : 0u) | (a.grad ? 1u << 29 : 0u) | ((a.tiles || a.jac || a.jac_sp || GN) ? 1u << 30 : 0u) |
                           (a.box ? 1u << 31 : 0u);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(MT * 64), bytes, s, a.Z, a.X0, a.small, a.wslice, a.P, pack, a.R, a.invH, a.H,
-                       FUSE ? a.jac : nullptr, a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(MT * 64), bytes, s, a.Z, a.X0, a.small, a.wslice, a.P, pack, a.R, a.invH,
+                       (unsigned)a.H | ((unsigned)grid << 16), FUSE ? a.jac : nullptr, a);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
 }
