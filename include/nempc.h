@@ -103,9 +103,13 @@ extern "C" {
 #define NEMPC_KERNEL_MFMA_TILE 3 /* force the wave-per-tile matrix-core kernel (A/B measurements) */
 #define NEMPC_KERNEL_LAYERED 4 /* layer-at-a-time matrix-core path: one GEMM launch per dense layer over all B*H rows, any
                                   activation per layer (output layer included), hidden widths <= 1024, up to 8 layers,
-                                  w*(nx+nu) <= 32, nx <= 16 -- what any feed-forward Keras model the reference wraps
-                                  (model/tensorflow.py:8-29) that NEMPC_KERNEL_MFMA does not take runs on under AUTO.
-                                  Rows and Lagrangian blocks (Discret / Unity / RK4), hence the batched solver too */
+                                  w*(nx+nu) <= 128 decision inputs (extra inputs do not count), nx <= 64 -- what any
+                                  feed-forward Keras model the reference wraps (model/tensorflow.py:8-29) that
+                                  NEMPC_KERNEL_MFMA does not take runs on under AUTO.  Rows and Lagrangian blocks (Discret /
+                                  Unity / RK4), hence the batched solver too.  One exception: the RK4 Lagrangian blocks of a
+                                  shape whose congruence step (8 nin^2 + 3 nx nin elements per row, nin = nx+nu) does not
+                                  fit the device's LDS -- fp64 beyond about 45 inputs at 160 KB -- come from the generic
+                                  kernel (nempc_last_hess_kernel: 1); the rows of such a model stay on this path */
 
 typedef struct nempc_handle_s* nempc_handle;
 

@@ -25,7 +25,9 @@
 // chunk c).  Per chunk and wave: 16 matrix instructions (1024 cycles in fp64), 16 ds_read, 8 global loads.  A v_mfma_f64
 // holds the vector pipe for its 64 cycles, so the bound is the matrix pipe; arbitrary M, N, K (edge tiles are
 // zero-filled on load and masked on store).
+#include <algorithm>
 #include <cstdlib>
+#include <utility>
 #include <type_traits>
 
 #include "activations.h"
@@ -920,7 +922,10 @@ bool lg_first_on() {
 // A block is 64 columns x 4 waves; wave w sums k = w, w + 4, ... with sixteen loads in flight per lane, the four partial
 // sums meet in LDS.  (A thread per column walking all of K alone was a chain of K dependent-latency loads: 141 us for
 // K = 256; eight loads in flight and 32 accumulators for 3 outputs: 60 us, 1.4 TB/s; this form: ~30 us.)  NMAX = 4 | 16 | 32
-// keeps the accumulator count -- and with it the occupancy -- at what the layer needs.
+// keeps the accumulator count -- and with it the occupancy -- at what the layer needs.  More than 32 outputs (nx > 32 in the
+// output step, nin > 32 in the last reverse step): blockIdx.y walks them in blocks of 32 -- every output is still summed by
+// wave w over k = w, w + 4, ... and the four partial sums are added in wave order, so an output's bits do not depend on the
+// block it sits in; red[3][32][64] stays 48 KB in fp64.
 template <typename T, int NMAX>
 __global__ __launch_bounds__(256) void layered_skinny_kernel(const T* __restrict__ A, long long lda, const T* __restrict__ Bw, int ldb,
                                                              int K, int N, long long M, T* __restrict__ out, long long ldo,
@@ -932,6 +937,8 @@ __global__ __launch_bounds__(256) void layered_skinny_kernel(const T* __restrict
     const long long m = (long long)blockIdx.x * 64 + lane;
     const bool live = m < M;
     const long long mc = live ? m : M - 1;          // (clamped: the loads stay in range, the result is not stored)
+    const int n0 = blockIdx.y * NMAX;               // (one block -- n0 = 0 -- up to 32 outputs)
+    const int Nb = N - n0 < NMAX ? N - n0 : NMAX;
     T acc[NMAX];
 #pragma unroll
     for (int n = 0; n < NMAX; ++n) acc[n] = T(0);
@@ -946,32 +953,33 @@ __global__ __launch_bounds__(256) void layered_skinny_kernel(const T* __restrict
         for (int u = 0; u < UN; ++u) {
             const int k = k0 + 4 * u;
             if (k < K) {
-                const T* wrow = Bw + (size_t)k * ldb;
+                const T* wrow = Bw + (size_t)k * ldb + n0;
 #pragma unroll
                 for (int n = 0; n < NMAX; ++n)
-                    if (n < N) acc[n] = fma(x[u], wrow[n], acc[n]);
+                    if (n < Nb) acc[n] = fma(x[u], wrow[n], acc[n]);
             }
         }
     }
     if (w > 0) {
 #pragma unroll
         for (int n = 0; n < NMAX; ++n)
-            if (n < N) red[w - 1][n][lane] = acc[n];
+            if (n < Nb) red[w - 1][n][lane] = acc[n];
     }
     __syncthreads();
     if (w == 0 && live) {
 #pragma unroll
         for (int n = 0; n < NMAX; ++n)
-            if (n < N) {
+            if (n < Nb) {
                 const T v = ((acc[n] + red[0][n][lane]) + red[1][n][lane]) + red[2][n][lane];
+                const size_t at = (size_t)(n0 + n) * ldo + m;
                 if (mode == 0) {
                     T x, d1, e;
-                    lg_act_all<T>(act, v + bias[n], actp, eout != nullptr, x, d1, e);
-                    out[(size_t)n * ldo + m] = x;
-                    dout[(size_t)n * ldo + m] = d1;
-                    if (eout) eout[(size_t)n * ldo + m] = e;
+                    lg_act_all<T>(act, v + bias[n0 + n], actp, eout != nullptr, x, d1, e);
+                    out[at] = x;
+                    dout[at] = d1;
+                    if (eout) eout[at] = e;
                 } else {
-                    out[(size_t)n * ldo + m] = v;
+                    out[at] = v;
                 }
             }
     }
@@ -980,7 +988,7 @@ __global__ __launch_bounds__(256) void layered_skinny_kernel(const T* __restrict
 template <typename T>
 int skinny(hipStream_t s, const T* A, long long lda, const T* Bw, int ldb, int K, int N, long long M, T* out, long long ldo,
            const T* bias, int mode, int act, T* dout, T actp, T* eout = nullptr) {
-    const dim3 grid((unsigned)((M + 63) / 64)), block(256);
+    const dim3 grid((unsigned)((M + 63) / 64), (unsigned)(N <= 32 ? 1 : (N + 31) / 32)), block(256);
     if (N <= 4) hipLaunchKernelGGL((layered_skinny_kernel<T, 4>), grid, block, 0, s, A, lda, Bw, ldb, K, N, M, out, ldo, bias, mode, act, dout, actp, eout);
     else if (N <= 16) hipLaunchKernelGGL((layered_skinny_kernel<T, 16>), grid, block, 0, s, A, lda, Bw, ldb, K, N, M, out, ldo, bias, mode, act, dout, actp, eout);
     else hipLaunchKernelGGL((layered_skinny_kernel<T, 32>), grid, block, 0, s, A, lda, Bw, ldb, K, N, M, out, ldo, bias, mode, act, dout, actp, eout);
@@ -1030,6 +1038,48 @@ __global__ void layered_rk4_kernel(int stage, int nx, int nin, T cdt, T wgt, con
     }
 }
 
+// ... for wide states (nx > 16 or nin > 32): a thread per (row, state i, input d) -- blockIdx.y = i, blockIdx.z = d.  As a thread
+// per row the stage is a chain of nx nin nx dependent strided loads (400 k multiply-adds per thread at 64/32); here a thread
+// walks the nx terms of ONE element, eight loads in flight at a time, the sum over e in index order.  dk_{s-1} is read by the
+// threads of every state, so dk_s goes to a second buffer (the host swaps the two between the stages) and the weighted sum is
+// updated in the same pass; the threads of d = 0 carry k_s.
+template <typename T>
+__global__ __launch_bounds__(256) void layered_rk4_wide_kernel(int stage, int nx, int nin, T cdt, T wgt, const T* __restrict__ f,
+                                                               const T* __restrict__ J, int R, long long Rp, T* __restrict__ kprev,
+                                                               T* __restrict__ acck, const T* __restrict__ dkp, T* __restrict__ dkn,
+                                                               T* __restrict__ accdk) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const int i = blockIdx.y, d = blockIdx.z;
+    const size_t ldj = (size_t)nx * Rp;
+    const T* Ji = J + (size_t)i * Rp + r;           // J^T[e][i Rp + r] = dPhi_i / dxi_e of row r, e = 0 .. nin - 1
+    const size_t at = (size_t)(i * nin + d) * Rp + r;
+    T v = Ji[(size_t)d * ldj];
+    if (stage > 0) {
+        const T* dp = dkp + (size_t)d * Rp + r;     // dk_{s-1}[e][d] of row r, e apart by nin Rp
+        const size_t ldk = (size_t)nin * Rp;
+        T s = T(0);
+        int e = 0;
+        for (; e + 7 < nx; e += 8) {
+            T a[8], b[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { a[u] = Ji[(size_t)(e + u) * ldj]; b[u] = dp[(size_t)(e + u) * ldk]; }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s = fma(a[u], b[u], s);
+        }
+        for (; e < nx; ++e) s = fma(Ji[(size_t)e * ldj], dp[(size_t)e * ldk], s);
+        v = v + cdt * s;
+    }
+    dkn[at] = v;
+    accdk[at] = stage == 0 ? v : fma(wgt, v, accdk[at]);
+    if (d == 0) {
+        const size_t ai = (size_t)i * Rp + r;
+        const T kv = f[ai];
+        kprev[ai] = kv;
+        acck[ai] = stage == 0 ? kv : fma(wgt, kv, acck[ai]);
+    }
+}
+
 // RK4 Hessian pipeline (kernels_rk4hess.hip): the record of (row, stage) = [xi_s | J_s (nx, nin) | dk_{s-1} (nx, nin)], written
 // between the stage's reverse sweep and its bookkeeping (dk still holds dk_{s-1})
 template <typename T>
@@ -1044,6 +1094,22 @@ __global__ void layered_stage_record_kernel(int stage, int nx, int nin, long lon
             rec[nin + i * nin + d] = J[(size_t)d * (nx * Rp) + (size_t)i * Rp + r];
             rec[nin + nx * nin + i * nin + d] = stage > 0 ? dk[(size_t)(i * nin + d) * Rp + r] : T(0);
         }
+}
+
+// ... for wide states: a thread per (row, state i) -- blockIdx.y = i; the threads of i = 0 also write xi
+template <typename T>
+__global__ void layered_stage_record_wide_kernel(int stage, int nx, int nin, long long r0, int R, long long Rp, const T* __restrict__ xi,
+                                                 const T* __restrict__ J, const T* __restrict__ dk, T* __restrict__ out, int stride) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const int i = blockIdx.y;
+    T* rec = out + ((size_t)(r0 + r) * 4 + stage) * stride;
+    if (i == 0)
+        for (int d = 0; d < nin; ++d) rec[d] = xi[(size_t)d * Rp + r];
+    for (int d = 0; d < nin; ++d) {
+        rec[nin + i * nin + d] = J[(size_t)d * (nx * Rp) + (size_t)i * Rp + r];
+        rec[nin + nx * nin + i * nin + d] = stage > 0 ? dk[(size_t)(i * nin + d) * Rp + r] : T(0);
+    }
 }
 
 // sum of `nb` partial sums `stride` elements apart, in block order, up to four loads in flight
@@ -1115,6 +1181,10 @@ __global__ void layered_finish_kernel(RowGather gk, int kind, T DT, int nin, con
     }
 }
 
+// The forms built for wide states: nx > 16 or more than 32 decision inputs.  Shapes inside those limits launch exactly what they
+// launched before the limits were lifted to 64 / 128 (same kernels, same arguments, same chunking).
+inline bool lg_wide(const Handle& h) { return h.cfg.nx > 16 || h.nin > 32; }
+
 struct LayeredWs {      // element offsets into the chunk workspace (times nothing: already multiplied by Rp)
     size_t xi, x0, x1, d[NEMPC_MAX_LAYERS], f, dl, g0, g1, j, kprev, acck, dk, dkn, accdk, total;
 };
@@ -1129,8 +1199,11 @@ LayeredWs layered_offsets(const Handle& h, size_t Rp) {
     for (int l = 0; l < h.nl - 1; ++l) { o.d[l] = p; p += (size_t)h.dout[l] * Rp; }
     o.f = p; p += (size_t)nx * Rp;
     o.dl = p; p += (size_t)nx * Rp;
-    o.g0 = p; p += (size_t)h.maxw * nx * Rp;
-    o.g1 = p; p += (size_t)h.maxw * nx * Rp;
+    // the cotangent buffers: maxw rows of nx Rp columns -- and room for the last reverse product's partial sums of J, nin rows
+    // per 64-feature block of layer 0 (never more than the width up to 32 inputs; up to 2 w + 128 rows at 128)
+    const size_t grows = std::max((size_t)h.maxw, (size_t)((h.dout[0] + 63) / 64) * nin);
+    o.g0 = p; p += grows * nx * Rp;
+    o.g1 = p; p += grows * nx * Rp;
     o.j = p; p += (size_t)nin * nx * Rp;
     if (h.cfg.integrator == NEMPC_RK4) {
         o.kprev = p; p += (size_t)nx * Rp;
@@ -1301,6 +1374,7 @@ int run_layered(Handle& h, int B, const void* Zv, const void* X0v, void* gv, voi
     T* ws = static_cast<T*>(h.d_layered_ws);
     const RowGather gk = h.gather();
     const bool rk4 = h.cfg.integrator == NEMPC_RK4;
+    const bool wide = lg_wide(h);
     const int nstages = rk4 ? 4 : 1;
     const T DT = (T)h.cfg.DT;
     int rc;
@@ -1318,6 +1392,8 @@ int run_layered(Handle& h, int B, const void* Zv, const void* X0v, void* gv, voi
         const T* fsrc = nullptr;            // the network output likewise (lin_skip: partial sums of a linear output layer)
         int fblk = 0;
         long long fstride = 0;
+        T* dkc = rk4 ? ws + o.dk : nullptr;     // wide RK4 states: dk_{s-1} and dk_s alternate between the two buffers
+        T* dkn = rk4 ? ws + o.dkn : nullptr;
         for (int st = 0; st < nstages; ++st) {
             const T cdt = st == 0 ? T(0) : (st == 3 ? DT : T(0.5) * DT);
             const bool fuse_out = layered_fuse();
@@ -1469,11 +1545,22 @@ int run_layered(Handle& h, int B, const void* Zv, const void* X0v, void* gv, voi
             }
             }
             if (rk4 && stage_out) {
-                hipLaunchKernelGGL(layered_stage_record_kernel<T>, rg, rb, 0, s, st, nx, nin, r0, R, Rp, ws + o.xi, ws + o.j, ws + o.dk,
-                                   static_cast<T*>(stage_out), stage_stride);
+                if (wide)
+                    hipLaunchKernelGGL(layered_stage_record_wide_kernel<T>, dim3(rg.x, (unsigned)nx), rb, 0, s, st, nx, nin, r0, R, Rp,
+                                       ws + o.xi, ws + o.j, dkc, static_cast<T*>(stage_out), stage_stride);
+                else
+                    hipLaunchKernelGGL(layered_stage_record_kernel<T>, rg, rb, 0, s, st, nx, nin, r0, R, Rp, ws + o.xi, ws + o.j, ws + o.dk,
+                                       static_cast<T*>(stage_out), stage_stride);
                 NEMPC_HIP(hipGetLastError());
             }
-            if (rk4) {
+            if (rk4 && wide) {
+                // (dk_s into the other buffer: the threads of every state read dk_{s-1})
+                hipLaunchKernelGGL(layered_rk4_wide_kernel<T>, dim3(rg.x, (unsigned)nx, (unsigned)nin), rb, 0, s, st, nx, nin, cdt,
+                                   (st == 0 || st == 3) ? T(1) : T(2), ws + o.f, ws + o.j, R, Rp, ws + o.kprev, ws + o.acck, dkc, dkn,
+                                   ws + o.accdk);
+                NEMPC_HIP(hipGetLastError());
+                std::swap(dkc, dkn);
+            } else if (rk4) {
                 hipLaunchKernelGGL(layered_rk4_kernel<T>, rg, rb, 0, s, st, nx, nin, cdt, (st == 0 || st == 3) ? T(1) : T(2), ws + o.f,
                                    ws + o.j, R, Rp, ws + o.kprev, ws + o.acck, ws + o.dk, ws + o.dkn, ws + o.accdk);
                 NEMPC_HIP(hipGetLastError());
@@ -1917,17 +2004,31 @@ int run_layered_hess(Handle& h, int B, const void* Zv, const void* X0v, const vo
 
 }  // namespace
 
-// Which networks take this path: at least one hidden layer, decision + extra inputs within the skinny kernel's 32
-// accumulators, nx within 16, plain or rolling-window models (the gather handles both); everything the register-resident
-// matrix-core kernels (mfma_supported) do not take.
+// Which networks take this path: at least one hidden layer, up to 128 decision inputs (the window times nx + nu; extra inputs
+// do not count) and 64 states, plain or rolling-window models (the gather handles both); everything the register-resident
+// matrix-core kernels (mfma_supported) do not take.  (The limits are where the workspaces -- nx and nin cotangent / tangent
+// columns per row -- and the per-pair Hessian launches were sized and tested; nothing in the kernels is tied to them.)
 bool layered_supported(const Handle& h) {
     if (h.nl < 2 || h.nl > NEMPC_MAX_LAYERS) return false;
-    if (h.nin > 32 || h.cfg.nx > 16 || h.maxw > 1024) return false;
+    if (h.nin > 128 || h.cfg.nx > 64 || h.maxw > 1024) return false;
     return true;
 }
 
 // NEMPC_LAYERED_CHUNK_ROWS: rows per chunk of both workspaces below (tests of the chunk loop; read at every sizing)
 static int layered_chunk_rows_env() { return env_int("NEMPC_LAYERED_CHUNK_ROWS", 0); }
+
+// rows per chunk from what 6 GB hold: at most 65536, whole GEMM blocks.  At least 4096 up to 16 states / 32 inputs (3.2 GB for
+// the Hessian sweeps of 1024 x 32 in fp64 -- the same floor at 1024 x 128 would be 13 GB); wide states -- whose workspaces grow with nx maxw and
+// nin maxw per row -- go down to one block of 64 rows instead: a reverse or tangent product's M is nx or nin times the chunk,
+// so a short chunk of a wide shape is still a large launch.
+static size_t layered_chunk_rows(const Handle& h, size_t rc_rows, size_t cap) {
+    if (rc_rows > 65536) rc_rows = 65536;
+    if (lg_wide(h)) rc_rows = rc_rows < LG_BM ? LG_BM : rc_rows / LG_BM * LG_BM;
+    else if (rc_rows < 4096) rc_rows = 4096;
+    if (const int v = layered_chunk_rows_env(); v > 0) rc_rows = (size_t)v;
+    if (rc_rows > cap) rc_rows = cap;
+    return (rc_rows + LG_BM - 1) / LG_BM * LG_BM;
+}
 
 // chunk workspace: rows per chunk so that the whole workspace stays near 6 GB (of 288), between 4096 and 65536 rows -- the
 // larger the products, the smaller the share of their launch tails (4 x 512, 6/3, B*H = 30720 in fp64 is one chunk of 2.3 GB)
@@ -1935,11 +2036,7 @@ int layered_prepare(Handle& h) {
     const size_t cap = (size_t)h.cfg.max_batch * h.cfg.H;
     const LayeredWs per = layered_offsets(h, 1);
     size_t rc_rows = ((size_t)6144 << 20) / (per.total * h.esz);
-    if (rc_rows > 65536) rc_rows = 65536;
-    if (rc_rows < 4096) rc_rows = 4096;
-    if (const int v = layered_chunk_rows_env(); v > 0) rc_rows = (size_t)v;
-    if (rc_rows > cap) rc_rows = cap;
-    rc_rows = (rc_rows + LG_BM - 1) / LG_BM * LG_BM;
+    rc_rows = layered_chunk_rows(h, rc_rows, cap);
     if (h.d_layered_ws && h.layered_chunk_rows == (long long)rc_rows) return NEMPC_OK;
     if (h.d_layered_ws) (void)hipFree(h.d_layered_ws);
     h.d_layered_ws = nullptr;
@@ -1967,11 +2064,7 @@ int layered_hess_prepare(Handle& h) {
     const size_t cap = (size_t)h.cfg.max_batch * h.cfg.H;
     const LayeredHws per = layered_hess_offsets(h, 1);
     size_t rc_rows = ((size_t)6144 << 20) / (per.total * h.esz);
-    if (rc_rows > 65536) rc_rows = 65536;
-    if (rc_rows < 4096) rc_rows = 4096;
-    if (const int v = layered_chunk_rows_env(); v > 0) rc_rows = (size_t)v;
-    if (rc_rows > cap) rc_rows = cap;
-    rc_rows = (rc_rows + LG_BM - 1) / LG_BM * LG_BM;
+    rc_rows = layered_chunk_rows(h, rc_rows, cap);
     if (h.d_layered_hws && h.layered_hess_chunk_rows == (long long)rc_rows) return NEMPC_OK;
     if (h.d_layered_hws) (void)hipFree(h.d_layered_hws);
     h.d_layered_hws = nullptr;

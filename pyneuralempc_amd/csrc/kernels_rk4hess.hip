@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void rk4_nu_kernel(size_t R, int H, int nx, in
     }
 }
 
-// one wave per (problem, step) row; LDS per wave: Ht[4][nin*nin] | C[3][nx*nin] with C_s = c_s dk_{s-1} | M[3][nin*nin] | out[nin*nin]
+// one wave per (problem, step) row, 4 / 2 / 1 rows per workgroup (congruence_waves); LDS per wave: Ht[4][nin*nin] | C[3][nx*nin] with C_s = c_s dk_{s-1} | M[3][nin*nin] | out[nin*nin]
 template <typename T>
 __global__ __launch_bounds__(256) void rk4_congruence_kernel(size_t R, int nx, int nin, T DT,
                                                              const T* __restrict__ stage, int stride,
@@ -105,6 +105,17 @@ __global__ __launch_bounds__(256) void rk4_congruence_kernel(size_t R, int nx, i
     }
 }
 
+// Waves (rows) per workgroup of the congruence kernel: 4, 2 or 1, as many as the device's LDS limit holds of a wave's
+// 8 nin^2 + 3 nx nin elements (16/8 in fp64: 46 KB a wave -- four of them passed 160 KB and the launch failed).  0: not even one
+// fits (fp64 beyond about 45 inputs at 160 KB): the pipeline returns NEMPC_EUNSUPPORTED before it launches anything and the
+// caller takes the generic Hessian kernel.  A row's arithmetic does not depend on how many rows share its workgroup.
+int congruence_waves(const Handle& h) {
+    const size_t per_wave = (size_t)(8 * h.nin * h.nin + 3 * h.cfg.nx * h.nin) * h.esz;
+    for (int nw = 4; nw >= 1; nw >>= 1)
+        if (nw * per_wave <= h.lds_limit) return nw;
+    return 0;
+}
+
 int dev_alloc_rk4(void** p, size_t bytes) {
     if (*p) return NEMPC_OK;
     hipError_t e = hipMalloc(p, bytes ? bytes : 16);
@@ -123,9 +134,11 @@ int run_small_kernels(Handle& h, size_t R, const void* lambda, void* blocks, int
         hipLaunchKernelGGL(rk4_nu_kernel<T>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, R, h.cfg.H, nx, nin, h.m,
                            (T)h.cfg.DT, (const T*)lambda, (const T*)h.d_rk4_stage, stride, (T*)h.d_rk4_nu);
     } else {
-        const size_t lds = 4 * (size_t)(8 * nin * nin + 3 * nx * nin) * sizeof(T);
+        const int nw = congruence_waves(h);
+        if (nw < 1) return NEMPC_EUNSUPPORTED;       // (the pipelines ask before their first launch: not reached)
+        const size_t lds = (size_t)nw * (size_t)(8 * nin * nin + 3 * nx * nin) * sizeof(T);
         NEMPC_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(rk4_congruence_kernel<T>), lds));
-        hipLaunchKernelGGL(rk4_congruence_kernel<T>, dim3((unsigned)((R + 3) / 4)), dim3(256), lds, s, R, nx, nin,
+        hipLaunchKernelGGL(rk4_congruence_kernel<T>, dim3((unsigned)((R + nw - 1) / nw)), dim3((unsigned)(64 * nw)), lds, s, R, nx, nin,
                            (T)h.cfg.DT, (const T*)h.d_rk4_stage, stride, (const T*)h.d_rk4_ht, (T*)blocks);
     }
     NEMPC_HIP(hipGetLastError());
@@ -147,6 +160,7 @@ int launch_rowhess_rk4_mfma(Handle& h, int B, const void* Z, const void* X0, con
     const int stride = nin + 2 * nx * nin;
     const size_t Rcap = (size_t)h.cfg.max_batch * h.cfg.H, R = (size_t)B * h.cfg.H;
     int rc;
+    if (congruence_waves(h) < 1) return NEMPC_EUNSUPPORTED;
     if ((rc = dev_alloc_rk4(&h.d_rk4_stage, Rcap * 4 * stride * h.esz))) return rc;
     if ((rc = dev_alloc_rk4(&h.d_rk4_nu, Rcap * 4 * nx * h.esz))) return rc;
     if ((rc = dev_alloc_rk4(&h.d_rk4_ht, Rcap * 4 * nin * nin * h.esz))) return rc;
@@ -176,6 +190,8 @@ int launch_rowhess_rk4_layered(Handle& h, int B, const void* Z, const void* X0, 
     const int stride = nin + 2 * nx * nin;
     const size_t Rcap = (size_t)h.cfg.max_batch * h.cfg.H, R = (size_t)B * h.cfg.H;
     int rc;
+    // (a wave's slice of the congruence kernel does not fit the device's LDS: the generic Hessian kernel, nothing launched here)
+    if (congruence_waves(h) < 1) return NEMPC_EUNSUPPORTED;
     if ((rc = dev_alloc_rk4(&h.d_rk4_stage, Rcap * 4 * stride * h.esz))) return rc;
     if ((rc = dev_alloc_rk4(&h.d_rk4_nu, Rcap * 4 * nx * h.esz))) return rc;
     if ((rc = dev_alloc_rk4(&h.d_rk4_ht, Rcap * 4 * nin * nin * h.esz))) return rc;

@@ -385,8 +385,11 @@ int nempc_create(const nempc_config* cfg, nempc_handle* out) {
         // compute units of the device: every "fill the chip" launch geometry is sized from this, never from a literal.
         // NEMPC_NUM_CUS overrides it (tests of the launch planning on the one device a box has).
         hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0)
-            h->num_cus = prop.multiProcessorCount;
+        if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess) {
+            if (prop.multiProcessorCount > 0) h->num_cus = prop.multiProcessorCount;
+            // (the LDS a workgroup may ask for: the RK4 congruence kernel sizes its workgroups by it, kernels_rk4hess.hip)
+            if (prop.sharedMemPerBlock > 0) h->lds_limit = prop.sharedMemPerBlock;
+        }
         if (const int v = env_int("NEMPC_NUM_CUS", 0); v > 0) h->num_cus = v;
     }
     h->variant = NEMPC_KERNEL_VALU;
@@ -411,7 +414,7 @@ int nempc_create(const nempc_config* cfg, nempc_handle* out) {
         } else if (cfg->kernel == NEMPC_KERNEL_LAYERED) {
             delete h;
             return fail(NEMPC_EUNSUPPORTED, "nempc_create: the layered matrix-core path needs >= 1 hidden layer, hidden widths <= 1024, "
-                                            "w*(nx+nu) <= 32 and nx <= 16");
+                                            "w*(nx+nu) <= 128 and nx <= 64");
         }
     }
 

@@ -130,6 +130,7 @@ inline GridPlan plan_grid(int ntiles, int num_cus, int per_cu) {
 struct Handle {
     nempc_config cfg{};
     int num_cus = 256;           // compute units of cfg.device (nempc_create)
+    size_t lds_limit = 65536;    // LDS a workgroup of cfg.device may ask for (hipDeviceProp_t::sharedMemPerBlock, nempc_create)
     int n = 0, m = 0, nl = 0;
     int nin = 0;                 // tile width = decision inputs one row's network reads: w*(nx+nu)
     int ne = 0;                  // extra network inputs (tvp + p); the network's input width is nin + ne
