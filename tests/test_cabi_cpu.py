@@ -134,3 +134,24 @@ def test_launch_planning_covers_every_tile_for_any_cu_count(num_cus):
             assert min(sizes) >= 1 and max(sizes) - min(sizes) <= 1 and sizes == sorted(sizes, reverse=True)
     assert lib.nempc_plan_grid(0, num_cus, 1, ctypes.byref(g), ctypes.byref(q), ctypes.byref(r)) == -1
     assert lib.nempc_plan_grid(8, 0, 1, ctypes.byref(g), ctypes.byref(q), ctypes.byref(r)) == -1
+
+
+def test_layered_plans_lend_only_what_fits_for_every_supported_shape(tmp_path):
+    """The layered path's host decisions (csrc/layered_plan.h: plain C++, no device) as a stand-alone program,
+    tests/layered_plan_check.cpp: one to four hidden layers of twelve widths, seven state and four control counts, with and
+    without extra inputs, the three integrators, linear and non-linear output layer, the default switches and each switch
+    away from its default.  For every shape the path takes: each workspace region a plan lends for partial sums holds them,
+    and the linear-output shortcut is planned exactly where the driver's former inline condition allowed it -- [11, 11] with 12
+    states not, [12, 12] yes."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "layered_plan_check")
+    subprocess.run([cxx, "-std=c++17", "-O2", "-pthread", "-I", os.path.join(REPO, "include"),
+                    "-I", os.path.join(REPO, "pyneuralempc_amd", "csrc"), "-o", exe,
+                    os.path.join(REPO, "tests", "layered_plan_check.cpp")], check=True, capture_output=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    m = re.search(r"(\d+) plans checked, 0 failures", r.stdout)
+    assert m and int(m.group(1)) > 100_000_000, r.stdout
