@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define NEMPC_ABI_VERSION 7
+#define NEMPC_ABI_VERSION 8
 #define NEMPC_MAX_LAYERS 8 /* dense layers incl. the linear output layer */
 
 /* status codes */
@@ -277,6 +277,28 @@ typedef struct nempc_solver_opts {
 
 int nempc_solve(nempc_handle h, int32_t B, const void* X0, void* Z, const double* lb, const double* ub,
                 const nempc_solver_opts* opts, int32_t* status, int32_t* iters, void* stream);
+
+/* Forward simulation of the handle's model (no reference counterpart: the reference never integrates its model over the
+ * horizon on its own -- its cold start tiles x0, optimizer/ipopt.py:149, and its examples step the plant outside the library).
+ *   Z (B,n) device, in/out: the controls are read from Z[:, H*nx:] and are not written; the states Z[:, :H*nx] are
+ *   overwritten with x_t = Phi(x_{t-1}, u_t), x_{-1} = X0, t = 0..H-1, and are NOT read (they may hold anything, NaN included);
+ *   X0 (B,nx) device;  f (B) optional: the handle's objective at the rolled-out point (NEMPC_ESTATE without an objective).
+ * Phi is the row kernels' map: Discret / Unity / RK4 (u and the extra inputs held over the four stages, cfg.DT), the extra
+ * inputs bound by nempc_bind_extra, rolling windows reaching into X0 and the history bound by nempc_bind_history (both
+ * orders), any of the NEMPC_ACT_* activations on any layer, both dtypes.  Serial in t, parallel in B: ONE launch, step t
+ * reading the states steps < t of the same call produced (they travel in registers / LDS, not through Z).
+ * Two kernels: generic (one wave per problem, any dims the handle takes) and matrix-core (one wave per 16 problems for all
+ * H steps; hidden widths <= 128, <= 4 hidden layers, any activation mix, nx <= 16, network inputs w*(nx+nu)+n_extra <= 32).
+ * By shape the library launches the one that measured faster: the matrix-core kernel when the shape fits it, the hidden
+ * widths are <= 64, its weight fragments fit the LDS and the batch gives at least 2.5 tiles per compute unit (its time
+ * does not grow with B up to 4 tiles per unit, the generic kernel's does), else the generic kernel.
+ * NEMPC_ROLLOUT_KERNEL=1|2 in the environment forces one (read per call); forcing 2 on a shape it does not take is
+ * NEMPC_EUNSUPPORTED.  Argument checks and codes as nempc_eval.  Asynchronous on `stream`; does not synchronise the device. */
+int nempc_rollout(nempc_handle h, int32_t B, const void* X0, void* Z, void* f, void* stream);
+
+/* kernel the handle's most recent nempc_rollout launched: 1 generic (rollout_wave_kernel), 2 matrix-core
+ * (rollout_mfma_kernel); 0 = none yet */
+int nempc_last_rollout_kernel(nempc_handle h);
 
 int nempc_sync(nempc_handle h, void* stream);
 

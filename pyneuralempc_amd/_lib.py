@@ -7,7 +7,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 # NEMPC_LIB: an alternative build of the same library (A/B kernel experiments, tools/build_variant.py)
 LIB_PATH = os.environ.get("NEMPC_LIB") or os.path.join(PKG, "libnempc.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 COMM_ID_BYTES = 128
 MAX_LAYERS = 8
 F64, F32 = 0, 1
@@ -43,7 +43,7 @@ def split_activation(spec):
 
 EXPORTS = ["nempc_create", "nempc_destroy", "nempc_reserve", "nempc_set_weights", "nempc_set_objective", "nempc_set_terminal_weight", "nempc_set_box_rows", "nempc_bind_extra", "nempc_bind_history",
            "nempc_dims", "nempc_constraint_bounds", "nempc_jac_structure", "nempc_hess_structure", "nempc_eval",
-           "nempc_hess", "nempc_hess_gn", "nempc_solve", "nempc_sync", "nempc_kernel_variant", "nempc_last_row_kernel", "nempc_last_hess_kernel", "nempc_last_error", "nempc_abi_version",
+           "nempc_hess", "nempc_hess_gn", "nempc_solve", "nempc_rollout", "nempc_last_rollout_kernel", "nempc_sync", "nempc_kernel_variant", "nempc_last_row_kernel", "nempc_last_hess_kernel", "nempc_last_error", "nempc_abi_version",
            "nempc_plan_grid", "nempc_num_cus",
            "nempc_comm_unique_id", "nempc_comm_init", "nempc_allgather_u0", "nempc_comm_size", "nempc_comm_destroy"]
 
@@ -103,6 +103,8 @@ def load():
     lib.nempc_hess.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nempc_hess_gn.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.nempc_solve.argtypes = [vp, i32, vp, vp, dp, dp, ctypes.POINTER(NempcSolverOpts), vp, ip, vp]
+    lib.nempc_rollout.argtypes = [vp, i32, vp, vp, vp, vp]
+    lib.nempc_last_rollout_kernel.argtypes = [vp]
     lib.nempc_sync.argtypes = [vp, vp]
     lib.nempc_kernel_variant.argtypes = [vp]
     lib.nempc_last_row_kernel.argtypes = [vp]

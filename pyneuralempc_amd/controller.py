@@ -73,15 +73,9 @@ class NMPC:
         return z[:nxh].reshape(self.integrator.H, -1), z[nxh:].reshape(self.integrator.H, -1)
 
 
-    def next_batch(self, X0, init_z=None, p=None, tvp=None, prev_x=None, prev_u=None, prev_tvp=None, **solver_opts):
-        """Solve B MPC problems at once on the device (no reference counterpart; SURVEY.md 8f-1).  X0 (B,nx) NumPy
-        array or device tensor.  Needs the fused device path (device integrator + QuadraticObjective; the only
-        extra rows accepted are BoxStateConstraint, which become bounds on the state variables).  Models with
-        parameters take p (p_dim,) or (B,p_dim) and tvp (H,tvp_dim) or (B,H,tvp_dim) -- one set for all problems or one
-        per problem (the batched form of NMPC.next's p / tvp, controller.py:65).  Rolling-window models take the histories
-        prev_x (w-1, nx) or (B, w-1, nx), prev_u, prev_tvp -- the batched form of set_prev_data (model/tensorflow.py:178-189);
-        left out, what set_prev_data stored serves every problem.  Returns (states (B,H,nx), u (B,H,nu),
-        status (B,) with Optimizer.SUCCESS / FAIL per problem) as NumPy arrays."""
+    def _batch_engine(self, X0, p, tvp, prev_x, prev_u, prev_tvp, who):
+        """What next_batch and closed_loop_batch share: the precondition check, the fused device engine with the extra inputs
+        and the histories of the B problems bound, X0 on the device, and the variable bounds (box rows folded in)."""
         import torch
         from .optimizer.base import fused_evaluator
         from .objective.quadratic import QuadraticObjective
@@ -90,7 +84,7 @@ class NMPC:
         boxes = [c for c in self.constraint_list if isinstance(c, BoxStateConstraint)]
         if not (isinstance(self.integrator, DeviceIntegrator) and self.integrator.on_device and isinstance(self.objective_func, QuadraticObjective)
                 and len(boxes) == len(self.constraint_list)):
-            raise NotImplementedError("next_batch needs a device integrator, a QuadraticObjective and no extra "
+            raise NotImplementedError(f"{who} needs a device integrator, a QuadraticObjective and no extra "
                                       "constraint rows other than BoxStateConstraint")
         eng = fused_evaluator(self.integrator, self.objective_func, None).engine
         H = self.integrator.H
@@ -135,7 +129,6 @@ class NMPC:
             eng.bind_extra(eng.to_device(np.concatenate(parts, axis=2)))
         elif p is not None or tvp is not None:
             raise ValueError("this model takes no p / tvp")
-        Zi = None if init_z is None else (init_z if isinstance(init_z, torch.Tensor) else eng.to_device(init_z))
         lb = np.asarray(self.domain_constraint.get_lower_bounds(H), dtype=np.float64).copy()
         ub = np.asarray(self.domain_constraint.get_upper_bounds(H), dtype=np.float64).copy()
         # box rows on the states are bounds on the state variables: intersect them with the domain
@@ -143,11 +136,79 @@ class NMPC:
             lo, hi = box._bounds(eng.nx)
             lb[:H * eng.nx] = np.maximum(lb[:H * eng.nx], np.tile(lo, H))
             ub[:H * eng.nx] = np.minimum(ub[:H * eng.nx], np.tile(hi, H))
-        Z, status, iters = eng.solve(X0t.contiguous(), Zi, lb, ub, **solver_opts)
+        return eng, X0t.contiguous(), lb, ub
+
+    def next_batch(self, X0, init_z=None, p=None, tvp=None, prev_x=None, prev_u=None, prev_tvp=None, **solver_opts):
+        """Solve B MPC problems at once on the device (no reference counterpart; SURVEY.md 8f-1).  X0 (B,nx) NumPy
+        array or device tensor.  Needs the fused device path (device integrator + QuadraticObjective; the only
+        extra rows accepted are BoxStateConstraint, which become bounds on the state variables).  Models with
+        parameters take p (p_dim,) or (B,p_dim) and tvp (H,tvp_dim) or (B,H,tvp_dim) -- one set for all problems or one
+        per problem (the batched form of NMPC.next's p / tvp, controller.py:65).  Rolling-window models take the histories
+        prev_x (w-1, nx) or (B, w-1, nx), prev_u, prev_tvp -- the batched form of set_prev_data (model/tensorflow.py:178-189);
+        left out, what set_prev_data stored serves every problem.  solver_opts go to CallbackEngine.solve; init="rollout"
+        among them starts from the roll-out of the start's controls (of zero controls without init_z) instead of the
+        reference's tiled x0.  Returns (states (B,H,nx), u (B,H,nu), status (B,) with Optimizer.SUCCESS / FAIL per problem)
+        as NumPy arrays."""
+        import torch
+        eng, X0t, lb, ub = self._batch_engine(X0, p, tvp, prev_x, prev_u, prev_tvp, "next_batch")
+        H = self.integrator.H
+        Zi = None if init_z is None else (init_z if isinstance(init_z, torch.Tensor) else eng.to_device(init_z))
+        Z, status, iters = eng.solve(X0t, Zi, lb, ub, **solver_opts)
         self.last_batch_iterations = iters
         z = Z.to("cpu", torch.float64).numpy()
         B, nx, nu = z.shape[0], eng.nx, eng.nu
         return z[:, :H * nx].reshape(B, H, nx), z[:, H * nx:].reshape(B, H, nu), status.cpu().numpy()
 
+    def closed_loop_batch(self, X0, steps, p=None, prev_x=None, prev_u=None, disturbance=None, **solver_opts):
+        """B closed loops of `steps` MPC steps on the device, the plant being the model itself (no reference counterpart:
+        the reference's examples step their plant on the host between NMPC.next calls).  Preconditions as next_batch.  Per
+        step, on device tensors only: (1) solve -- step 0 from solver_opts' init ("tile" by default), later steps from the
+        warm start below with mu_init = 1e-4; (2) apply u_0: x+ = Phi(x0, u0) exactly, the first state of the roll-out of the
+        solved controls (not the solver's state, which satisfies the dynamics to tol_constraint), plus disturbance[:, k]
+        (B, steps, nx) when given; (3) warm start: the controls shifted by one stage, the last repeated, and their roll-out
+        from the new x0, so the start satisfies the dynamics also after a disturbance; (4) rolling-window models: the histories
+        take in x0 / u0 and are bound again.  The host waits in the solver's own convergence polls and in the final copy only.
+        Returns (X (B,steps+1,nx), U (B,steps,nu), status (steps,B)) as NumPy arrays."""
+        import torch
+        model = self.integrator.model
+        if int(getattr(model, "tvp_dim", 0)) > 0:
+            raise NotImplementedError("closed_loop_batch: models with time-varying parameters (tvp_dim > 0) are not supported -- "
+                                      "a closed loop of `steps` steps needs a tvp schedule of H + steps - 1 rows, longer than the "
+                                      "horizon NMPC takes")
+        eng, X, lb, ub = self._batch_engine(X0, p, None, prev_x, prev_u, None, "closed_loop_batch")
+        B, H, nx, nu = int(X.shape[0]), eng.H, eng.nx, eng.nu
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("steps must be >= 1")
+        D = None
+        if disturbance is not None:
+            D = disturbance if isinstance(disturbance, torch.Tensor) else eng.to_device(np.asarray(disturbance, dtype=np.float64))
+            if tuple(D.shape) != (B, steps, nx):
+                raise ValueError(f"disturbance must have shape {(B, steps, nx)}, got {tuple(D.shape)}")
+        w = eng.rolling_window
+        hx, hu = eng._history if w > 1 else (None, None)
+        warm_opts = {k: v for k, v in solver_opts.items() if k != "init"}
+        warm_opts["mu_init"] = 1e-4
+        Xs, Us, Ss, iters, Zi = [X], [], [], [], None
+        for k in range(steps):
+            Z, status, it = eng.solve(X, Zi, lb, ub, **(solver_opts if k == 0 else warm_opts))[:3]
+            iters.append(it)
+            U = Z[:, H * nx:].reshape(B, H, nu).clone()
+            eng.rollout(X, Z=Z)                               # the plant is the model: x+ = Phi(x0, u0)
+            Xn = Z[:, :nx].clone()
+            if D is not None:
+                Xn = Xn + D[:, k]
+            if w > 1:                                         # the window moves on by one step
+                hx = torch.cat([hx[:, 1:], X[:, None, :]], dim=1).contiguous()
+                hu = torch.cat([hu[:, 1:], U[:, :1]], dim=1).contiguous()
+                eng.bind_history(hx, hu)
+            X = Xn.contiguous()
+            Zi = eng.rollout(X, U=torch.cat([U[:, 1:], U[:, -1:]], dim=1))
+            Xs.append(X)
+            Us.append(U[:, 0])
+            Ss.append(status)
+        self.last_closed_loop_iterations = iters      # outer iterations of every step's solve (a list; next_batch's int is last_batch_iterations)
+        return (torch.stack(Xs, dim=1).to("cpu", torch.float64).numpy(), torch.stack(Us, dim=1).to("cpu", torch.float64).numpy(),
+                torch.stack(Ss, dim=0).cpu().numpy())
 
 MPC = NMPC  # BASELINE.json's north_star calls the entry point controller.MPC

@@ -778,6 +778,33 @@ int nempc_solve(nempc_handle hh, int32_t B, const void* X0, void* Z, const doubl
     return solver_run(h, B, X0, Z, lb, ub, *opts, status, iters, reinterpret_cast<hipStream_t>(stream));
 }
 
+int nempc_rollout(nempc_handle hh, int32_t B, const void* X0, void* Z, void* f, void* stream) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_rollout: null handle");
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_rollout: B outside [0, max_batch]");
+    if (B == 0) return NEMPC_OK;
+    if (!Z || !X0) return fail(NEMPC_EINVAL, "nempc_rollout: null argument");
+    if (!h.have_weights) return fail(NEMPC_ESTATE, "nempc_rollout: call nempc_set_weights first");
+    if (f && !h.have_objective) return fail(NEMPC_ESTATE, "nempc_rollout: f asked for but the handle has no objective");
+    if (h.ne > 0 && !h.d_extra) return fail(NEMPC_ESTATE, "nempc_rollout: n_extra > 0 but nempc_bind_extra was not called");
+    if (h.w > 1 && !h.d_hist_x)
+        return fail(NEMPC_ESTATE, "nempc_rollout: rolling_window > 1 but nempc_bind_history was not called");
+    if ((h.ne > 0 && B > h.extra_B) || (h.w > 1 && B > h.hist_B))
+        return fail(NEMPC_EINVAL, "nempc_rollout: B exceeds the batch the bound extras / history cover");
+    const int which = env_int("NEMPC_ROLLOUT_KERNEL", 0);
+    if (which < 0 || which > 2) return fail(NEMPC_EINVAL, "nempc_rollout: NEMPC_ROLLOUT_KERNEL must be 1 (generic) or 2 (matrix-core)");
+    DeviceGuard dg(h.cfg.device);
+    if (!dg.ok) return fail(NEMPC_EHIP, "nempc_rollout: hipSetDevice failed");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (int rc = launch_rollout(h, B, X0, Z, which, s)) return rc;
+    return f ? launch_objective(h, B, Z, f, nullptr, s) : NEMPC_OK;
+}
+
+int nempc_last_rollout_kernel(nempc_handle hh) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_last_rollout_kernel: null handle");
+    return reinterpret_cast<Handle*>(hh)->last_rollout_kernel;
+}
+
 int nempc_sync(nempc_handle hh, void* stream) {
     if (!hh) return fail(NEMPC_EINVAL, "nempc_sync: null handle");
     Handle& h = *reinterpret_cast<Handle*>(hh);

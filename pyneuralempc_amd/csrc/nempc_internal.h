@@ -206,6 +206,7 @@ struct Handle {
     void* comm = nullptr;        // comm.hip: RCCL communicator of the u0 all-gather
     mutable int last_row_kernel = 0;  // 1 valu, 2 coop, 3 wave-tile
     mutable int last_hess_kernel = 0; // 1 valu, 2 coop, 3 wave-tile, 4 fixed shape; + 10: inside the RK4 pipeline (nempc_last_hess_kernel)
+    mutable int last_rollout_kernel = 0; // 1 generic, 2 matrix-core (nempc_last_rollout_kernel)
 };
 
 struct ObjOffsets {  // element offsets into Handle::d_obj
@@ -252,6 +253,11 @@ int launch_rows_layered_stages(Handle& h, int B, const void* Z, const void* X0, 
 int launch_rowhess_rk4_layered(Handle& h, int B, const void* Z, const void* X0, const void* lambda, void* blocks, hipStream_t s,
                                void* g_out, void* tiles_out);
 void layered_free(Handle& h);
+
+// ---- kernels_rollout.hip : forward simulation x_t = Phi(x_{t-1}, u_t), serial in t, parallel in B
+bool rollout_mfma_supported(const Handle& h);
+// which: 0 by shape, 1 generic, 2 matrix-core (NEMPC_EUNSUPPORTED when the shape is outside it)
+int launch_rollout(Handle& h, int B, const void* X0, void* Z, int which, hipStream_t s);
 
 // ---- kernels_mfma.hip : matrix-core row kernel
 bool mfma_supported(const Handle& h);

@@ -415,11 +415,46 @@ class CallbackEngine:
                 _lib.check(rc)
         return launch, res
 
+    @property
+    def last_rollout_kernel(self):
+        """Name of the kernel the most recent roll-out launched."""
+        return {0: None, 1: "rollout_wave_kernel", 2: "rollout_mfma_kernel"}[self.lib.nempc_last_rollout_kernel(self._handle)]
+
+    def rollout(self, X0, U=None, Z=None, want_f=False):
+        """Forward simulation of the model on the device (nempc_rollout): x_t = Phi(x_{t-1}, u_t), x_{-1} = X0, one launch
+        for the whole horizon.  X0 (B,nx); the controls come from U (B,H,nu) or (B,H*nu), or from the control part of Z (B,n),
+        which is then updated IN PLACE (its states are overwritten and never read); neither = zero controls.  Returns
+        Z (B,n) = [rolled-out states | controls], or (Z, f (B,)) with the objective at that point when want_f.
+        Asynchronous on the current torch stream."""
+        B = int(X0.shape[0])
+        self._check_in(X0, (B, self.nx), "X0")
+        if U is not None and Z is not None:
+            raise ValueError("rollout: pass U or Z, not both")
+        if Z is not None:
+            self._check_in(Z, (B, self.n), "Z")
+        else:
+            Z = torch.zeros(B, self.n, dtype=self.dtype, device=self.device)
+            if U is not None:
+                if not isinstance(U, torch.Tensor) or U.device != self.device or U.dtype != self.dtype:
+                    raise ValueError(f"U must be a {self.dtype} tensor on {self.device}")
+                if tuple(U.shape) not in ((B, self.H, self.nu), (B, self.H * self.nu)):
+                    raise ValueError(f"U must have shape {(B, self.H, self.nu)} or {(B, self.H * self.nu)}, got {tuple(U.shape)}")
+                Z[:, self.H * self.nx:] = U.reshape(B, self.H * self.nu)
+        self._check_extra(B)
+        self.reserve(B)
+        f = torch.empty(B, dtype=self.dtype, device=self.device) if want_f else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nempc_rollout(self._handle, B, ctypes.c_void_p(X0.data_ptr()), ctypes.c_void_p(Z.data_ptr()),
+                                              None if f is None else ctypes.c_void_p(f.data_ptr()), self._stream()))
+        return (Z, f) if want_f else Z
+
     def solve(self, X0, Z_init=None, lb=None, ub=None, max_iter=200, max_linesearch=6, check_every=4,
               tol_constraint=None, tol_step=None, mu_init=1e-1, mu_min=None, mu_factor=0.2, reg=None, lq_kernel="auto",
-              compact=True, return_iterations=False, barrier="primal-dual", linesearch="auto", lq_attempts=0):
+              compact=True, return_iterations=False, barrier="primal-dual", linesearch="auto", lq_attempts=0, init="tile"):
         """Batched on-device solve (Gauss-Newton SQP, see csrc/solver.hip).  X0 (B,nx) device tensor; Z_init (B,n)
-        or None for the reference's cold start [x0 tiled H ; zeros] (optimizer/ipopt.py:149); lb/ub (n) host
+        or None for the reference's cold start [x0 tiled H ; zeros] (optimizer/ipopt.py:149); init="rollout" makes the start
+        dynamically feasible instead: the states of the start (Z_init's, or of zero controls) are replaced by the roll-out of
+        its controls (`rollout`; the solver moves a start outside the bounds into their interior itself); lb/ub (n) host
         vectors as DomainConstraint produces them; tolerances default by dtype (fp64 1e-8, fp32 1e-4); lq_kernel picks the LQ solve ("auto" | "thread" per problem | "wave"
         per problem | "scan": parallel in time, 2/1 stages in fp64); compact=True gathers the unconverged problems to the front as the batch converges (same results,
         shorter launches); linesearch "loop" backtracks inside an iteration (every problem waits for the slowest search),
@@ -438,12 +473,18 @@ class CallbackEngine:
         tol_step = (1e-8 if f64 else 1e-4) if tol_step is None else tol_step
         mu_min = (1e-9 if f64 else 1e-5) if mu_min is None else mu_min
         reg = (1e-9 if f64 else 1e-6) if reg is None else reg
-        if Z_init is None:
+        if init not in ("tile", "rollout"):
+            raise ValueError("init must be 'tile' or 'rollout'")
+        if Z_init is None and init == "rollout":
+            Z = self.rollout(X0)
+        elif Z_init is None:
             Z = torch.cat([X0.repeat(1, self.H), torch.zeros(B, self.H * self.nu, dtype=self.dtype, device=self.device)],
                           dim=1).contiguous()
         else:
             self._check_in(Z_init, (B, self.n), "Z_init")
             Z = Z_init.clone()
+            if init == "rollout":
+                self.rollout(X0, Z=Z)
         keep, ptrs = [], []
         for v in (lb, ub):
             if v is None:
