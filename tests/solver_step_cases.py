@@ -1,0 +1,266 @@
+"""Shapes, networks, objectives and starts of the per-step solver checks  --  TEST INFRASTRUCTURE, not a test.
+
+Shared by tests/test_kkt_reference_cpu.py (the reference checks itself on these shapes) and tests/test_gpu_solver_steps.py
+(the solver against the reference).  Everything is seeded; references are computed once per case and cached.
+"""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+
+from oracle import nempc_oracle as orc
+import kkt_reference as kkt
+
+REG = 1e-9          # the Levenberg term every solve here passes (fp64: the solver's default, and its floor)
+BMAX = 16
+REF_SCALE = 0.1     # standard deviation of the per-stage xref, uref, cx, cu
+KINDS = {"discret": orc.DISCRET, "unity": orc.UNITY, "rk4": orc.RK4}
+
+# The smallest horizon at which plan_lq (csrc/solver.hip) no longer stages a 2/1 fp64 problem in LDS with lq_kernel =
+# "thread": per problem (48 H + 37) doubles at one damping level (39 H of iterate / tiles / blocks / steps, 9 H + 36 of one
+# attempt's gains and temporaries, made odd) against a budget of 150 KiB minus 2 n doubles:
+#     8 (48 H + 37) <= 153600 - 48 H   <=>   H <= 354
+H_GLOBAL = 355
+
+
+def lds_bytes_2x1_thread(H):
+    """(bytes one problem needs, budget) of the 2/1 fp64 thread-per-problem sweep at one damping level -- plan_lq's sizes."""
+    nx, nu, nin, n = 2, 1, 3, 3 * H
+    tmp = 3 * nx * nx + 3 * nx * nu + nu * nu + 5 * nx + 3 * nu + 1 + (nx + 1) * nu
+    att = H * nu * nx + H * nu + H * nx * nx + H * nx + tmp
+    per = (2 * n + 2 * H * nx + H * nx * nin + H * nin * nin + n + n + H * nx + 2 * n + att) | 1
+    return 8 * per, 150 * 1024 - 2 * n * 8
+
+
+# ---- (a) one Newton step on an equality-constrained convex QP: linear networks.
+# name: (nx, nu, hidden, integrator, DT, horizons, lq kernels, dtype, window, forward_rolling, n_extra)
+QP_ROWS = {
+    "2x1_discret":   (2, 1, [32], "discret", 1.0, (1, 2, 3, 20, 63), ("thread", "wave", "scan", "auto"), "float64", 1, True, 0),
+    "2x1_global":    (2, 1, [32], "discret", 1.0, (H_GLOBAL,), ("thread",), "float64", 1, True, 0),
+    "6x3_rk4":       (6, 3, [16, 16], "rk4", 0.1, (8,), ("thread", "wave", "auto"), "float64", 1, True, 0),
+    "3x2_unity":     (3, 2, [8], "unity", 1.0, (7,), ("thread", "wave"), "float64", 1, True, 0),
+    "5x2_one_layer": (5, 2, [], "rk4", 0.1, (9,), ("auto",), "float64", 1, True, 0),
+    "roll3_fwd":     (2, 1, [8], "discret", 1.0, (10,), ("auto",), "float64", 3, True, 0),
+    "roll3_rev":     (2, 1, [8], "discret", 1.0, (10,), ("auto",), "float64", 3, False, 0),
+    "2x1_extras":    (2, 1, [8], "discret", 1.0, (10,), ("auto",), "float64", 1, True, 2),
+    "2x1_fp32":      (2, 1, [32], "discret", 1.0, (20,), ("thread", "wave"), "float32", 1, True, 0),
+}
+# (one seed for every row.  It matters at H = 355 only: of the seeds 0..11 this one gives the 2/1 Discret dynamics I + 0.1 W the
+#  smallest spectral radius, 1.0007 -- a mode of 1.015 grows 200-fold over 355 stages and takes the conditioning with it)
+QP_SEED = 1
+QP_CASES = [(name, H) for name, row in QP_ROWS.items() for H in row[5]]
+QP_RANDOM_START = {("2x1_discret", 20), ("6x3_rk4", 8)}      # also run from a random Z_init
+
+# ---- (b) three steps of a nonlinear solve: tanh networks, output layer scaled by 0.1, X0 in +-0.5, 8 problems
+# name: (nx, nu, hidden, integrator, DT, H, lq kernels, dtype, steps)
+NL_ROWS = {
+    "2x1_h20":   (2, 1, [64, 64], "discret", 1.0, 20, ("thread", "wave", "scan", "auto"), "float64", 3),
+    "2x1_h63":   (2, 1, [64, 64], "discret", 1.0, 63, ("thread", "wave", "scan", "auto"), "float64", 3),
+    "6x3_rk4":   (6, 3, [32, 32], "rk4", 0.1, 8, ("thread", "wave", "auto"), "float64", 3),
+    "3x2_unity": (3, 2, [24], "unity", 1.0, 7, ("thread", "wave", "auto"), "float64", 3),
+    "5x2_h9":    (5, 2, [16, 16], "discret", 1.0, 9, ("thread", "wave", "auto"), "float64", 3),
+    "6x3_fp32":  (6, 3, [32, 32], "rk4", 0.1, 8, ("thread", "wave", "auto"), "float32", 2),
+}
+NL_B = 8
+GATE_EIG = 0.05          # reduced-Hessian eigenvalue below which the sweep could restart with damping
+STOP_STEP = 1e-6         # a reference step below this is at the convergence test: the solver rightly stands still
+
+
+def _round(a, dtype):
+    """Values as the handle holds them: an fp32 handle solves the problem with fp32-rounded data."""
+    return np.asarray(a, dtype=np.float64) if dtype == "float64" else np.asarray(a, dtype=np.float32).astype(np.float64)
+
+
+def objective(nx, nu, H, seed, dtype="float64"):
+    """Non-symmetric Q = I + 0.1 N, R = 0.3 I + 0.03 N, QT = 2 I + 0.1 N (N seeded standard normal), random per-stage xref,
+    uref, cx, cu."""
+    rng = np.random.default_rng(seed)
+    ob = dict(Q=np.eye(nx) + 0.1 * rng.normal(size=(nx, nx)), R=0.3 * np.eye(nu) + 0.03 * rng.normal(size=(nu, nu)),
+              QT=2.0 * np.eye(nx) + 0.1 * rng.normal(size=(nx, nx)), xref=REF_SCALE * rng.normal(size=(H, nx)),
+              uref=REF_SCALE * rng.normal(size=(H, nu)), cx=REF_SCALE * rng.normal(size=(H, nx)), cu=REF_SCALE * rng.normal(size=(H, nu)))
+    return {k: _round(v, dtype) for k, v in ob.items()}
+
+
+class Case:
+    """One shape: the network, the objective, BMAX starts and per-problem oracle Problems."""
+
+    def __init__(self, name, nx, nu, hidden, integ, DT, H, kernels, dtype, window=1, forward=True, n_extra=0,
+                 act="linear", seed=0, B=BMAX, scale_b=False, x0_range=0.5):
+        self.name, self.nx, self.nu, self.H, self.integ, self.DT = name, nx, nu, H, integ, DT
+        self.kernels, self.dtype, self.window, self.forward, self.n_extra, self.B = kernels, dtype, window, forward, n_extra, B
+        n_in = window * (nx + nu) + n_extra
+        net = orc.MLP.random(n_in, hidden, nx, seed=seed, activations=act)
+        if integ == "discret" or act != "linear":
+            net.W[-1] *= 0.1
+            if scale_b:
+                net.b[-1] *= 0.1
+        net.W = [_round(w, dtype) for w in net.W]
+        net.b = [_round(b, dtype) for b in net.b]
+        self.net = net
+        self.obj = objective(nx, nu, H, seed + 100, dtype)
+        rng = np.random.default_rng(seed + 200)
+        self.X0 = _round(rng.uniform(-x0_range, x0_range, size=(B, nx)), dtype)
+        self.extra = _round(0.5 * rng.normal(size=(B, H, n_extra)), dtype) if n_extra else None
+        self.hist_x = _round(rng.uniform(-0.5, 0.5, size=(B, window - 1, nx)), dtype) if window > 1 else None
+        self.hist_u = _round(rng.uniform(-0.5, 0.5, size=(B, window - 1, nu)), dtype) if window > 1 else None
+        self.n = H * (nx + nu)
+        self.Zrand = _round(np.concatenate([rng.uniform(-0.5, 0.5, size=(B, H * nx)), rng.uniform(-0.5, 0.5, size=(B, H * nu))],
+                                           axis=1), dtype)
+
+    def problem(self, b):
+        roll = {} if self.window == 1 else dict(window=self.window, forward_rolling=self.forward, hist_x=self.hist_x[b],
+                                                hist_u=self.hist_u[b])
+        return orc.Problem(self.net, self.H, self.nx, self.nu, KINDS[self.integ], self.DT,
+                           extra=None if self.extra is None else self.extra[b], **self.obj, **roll)
+
+    def start(self, b, random_start=False):
+        return self.Zrand[b].copy() if random_start else orc.cold_start(self.X0[b], self.H, self.nu)
+
+    def engine(self, **kw):
+        """The device handle of this case (GPU tests only)."""
+        import torch
+        from pyneuralempc_amd import CallbackEngine
+        dt = {"float64": torch.float64, "float32": torch.float32}[self.dtype]
+        eng = CallbackEngine(self.net.W, self.net.b, self.H, self.nx, self.nu, integrator=self.integ, DT=self.DT, dtype=dt,
+                             device="cuda:0", max_batch=self.B, n_extra=self.n_extra, rolling_window=self.window,
+                             forward_rolling=self.forward, activations=self.net.act, **kw)
+        eng.set_objective(**self.obj)
+        return eng
+
+    def bind(self, eng, B):
+        """Per-problem data of the first B problems: extras / history bound on the handle; returns X0 on the device."""
+        if self.n_extra:
+            eng.bind_extra(eng.to_device(self.extra[:B]))
+        if self.window > 1:
+            eng.bind_history(eng.to_device(self.hist_x[:B]), eng.to_device(self.hist_u[:B]))
+        return eng.to_device(self.X0[:B])
+
+
+@functools.lru_cache(maxsize=None)
+def qp_case(name, H):
+    nx, nu, hidden, integ, DT, _, kernels, dtype, window, forward, n_extra = QP_ROWS[name]
+    return Case(name, nx, nu, hidden, integ, DT, H, kernels, dtype, window, forward, n_extra, act="linear",
+                seed=QP_SEED)
+
+
+@functools.lru_cache(maxsize=None)
+def nl_case(name):
+    nx, nu, hidden, integ, DT, H, kernels, dtype, _ = NL_ROWS[name]
+    return Case(name, nx, nu, hidden, integ, DT, H, kernels, dtype, act="tanh", seed=NL_SEEDS.get(name, 0), B=NL_B, scale_b=True)
+
+
+# (seeds at which the REFERENCE clears both gates of (b) for all 8 problems and all three steps; of the seeds 0..7 the 2/1
+#  Discret network clears them at 1, 2 and 6 -- at the others a reference step meets an indefinite reduced Hessian or raises
+#  the merit, which is the damped / shortened territory these tests leave out)
+NL_SEEDS = {"2x1_h20": 1, "2x1_h63": 1}
+
+
+def np_dtype(case):
+    return np.float64 if case.dtype == "float64" else np.float32
+
+
+def step_tolerance(e, z):
+    """Ten times what a correct sweep in the handle's precision loses on this system, floored at
+    1e-12 (1 + |z|inf)."""
+    return max(10.0 * e, 1e-12 * (1.0 + float(np.abs(z).max())))
+
+
+@functools.lru_cache(maxsize=None)
+def qp_reference(name, H, random_start=False):
+    """Per problem of the case: (z0, dz_ref, lam_ref, tolerance, e) -- float64 dense Newton step from the start, and the
+    tolerance from the Riccati sweep in the handle's precision."""
+    case = qp_case(name, H)
+    out = []
+    for b in range(case.B):
+        prob, x0 = case.problem(b), case.X0[b]
+        z0 = case.start(b, random_start)
+        dz, lam, _, _ = kkt.newton_step(prob, z0, x0, np.zeros(H * case.nx), REG, diagnostics=False)
+        dzr, _ = kkt.riccati_step(prob, z0, x0, np.zeros(H * case.nx), REG, np_dtype(case))
+        e = float(np.abs(dzr - dz).max())
+        out.append((z0, dz, lam, step_tolerance(e, z0 + dz), e))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def nl_reference(name):
+    """Per problem: the replayed steps (kkt.replay) and the cumulative sweep error in the handle's precision."""
+    case = nl_case(name)
+    steps = NL_ROWS[name][8]
+    out = []
+    for b in range(case.B):
+        prob, x0 = case.problem(b), case.X0[b]
+        z0 = case.start(b)
+        out.append((kkt.replay(prob, x0, z0, steps, REG), kkt.sweep_error(prob, x0, z0, steps, REG, np_dtype(case))))
+    return out
+
+
+# ---- (c) bounded convex QP: linear networks, tight control bounds, wide state bounds, one state limit from the box rows
+# name: (nx, nu, hidden, integrator, DT, H, seed)
+BOUNDED_ROWS = {
+    "2x1_h12": (2, 1, [32], "discret", 1.0, 12, 1),
+    "3x2_h7":  (3, 2, [8], "unity", 1.0, 7, 1),
+}
+BOUNDED_B = 4
+STATE_WIDE = 5.0
+NU_MIN = 1e-3            # smallest active bound multiplier the reference must show (strict complementarity with a margin)
+
+
+def slsqp(prob, x0, lb, ub):
+    """SciPy SLSQP on the oracle's callbacks (defect rows as equalities, lb / ub as bounds)."""
+    import warnings
+    from scipy.optimize import Bounds, minimize
+    m = prob.H * prob.nx
+    zi = np.clip(orc.cold_start(x0, prob.H, prob.nu), lb, ub)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return minimize(prob.objective, zi, method="SLSQP", jac=prob.gradient, bounds=Bounds(lb, ub),
+                        constraints=[{"type": "eq", "fun": lambda z: prob.constraints(z, x0)[:m],
+                                      "jac": lambda z: prob.jacobian(z, x0)[:m]}],
+                        options={"maxiter": 500, "ftol": 1e-14})
+
+
+@functools.lru_cache(maxsize=None)
+def bounded_case(name):
+    """(case of BOUNDED_B problems, lb, ub as the solver ends up with them, what the handle is given: dict(lb, ub, box_lo,
+    box_hi)).  The control limit is 40 % of the largest unconstrained control of problem 0; the box rows cap state 0 a tenth of its range
+    under the highest value it reaches in problem 0's control-bounded solution; of a seeded pool of starts the first
+    BOUNDED_B are kept whose REFERENCE solution has at least two controls on a bound and no active multiplier under NU_MIN
+    (problem 0, which the limits were cut for, among them)."""
+    nx, nu, hidden, integ, DT, H, seed = BOUNDED_ROWS[name]
+    pool = Case(name, nx, nu, hidden, integ, DT, H, ("auto",), "float64", act="linear", seed=seed, B=32)
+    n = pool.n
+    p0, x00 = pool.problem(0), pool.X0[0]
+    dz, _, _, _ = kkt.newton_step(p0, pool.start(0), x00, np.zeros(H * nx), REG, diagnostics=False)
+    umax = float(np.abs((pool.start(0) + dz)[H * nx:]).max())
+    c = round(0.4 * umax, 3)
+    lb = np.concatenate([np.full(H * nx, -STATE_WIDE), np.full(H * nu, -c)])
+    ub = -lb
+    z1, _, _, _ = kkt.qp_solution(p0, x00, lb, ub)
+    xs = z1[:H * nx].reshape(H, nx)
+    cap = round(float(xs[:, 0].max()) - 0.1 * float(np.ptp(xs[:, 0])), 3)
+    box_lo, box_hi = np.full(nx, -STATE_WIDE), np.full(nx, STATE_WIDE)
+    box_hi[0] = cap
+    lbe, ube = lb.copy(), ub.copy()
+    ube[:H * nx] = np.minimum(ube[:H * nx], np.tile(box_hi, H))
+    keep = []
+    for b in range(pool.B):
+        try:
+            z, lam, nlo, nhi = kkt.qp_solution(pool.problem(b), pool.X0[b], lbe, ube)
+        except (RuntimeError, AssertionError, np.linalg.LinAlgError):
+            continue                              # (infeasible under the cap from this start)
+        act = np.concatenate([nlo[nlo > 0], nhi[nhi > 0]])
+        if ((nlo + nhi)[H * nx:] > 0).sum() >= 2 and act.min() >= NU_MIN:
+            keep.append(b)
+        if len(keep) == BOUNDED_B:
+            break
+    assert len(keep) == BOUNDED_B and keep[0] == 0, keep
+    case = Case(name, nx, nu, hidden, integ, DT, H, ("auto",), "float64", act="linear", seed=seed, B=32)
+    case.X0, case.B = pool.X0[keep].copy(), BOUNDED_B
+    return case, lbe, ube, dict(lb=lb, ub=ub, box_lo=box_lo, box_hi=box_hi)
+
+
+@functools.lru_cache(maxsize=None)
+def bounded_reference(name):
+    case, lbe, ube, _ = bounded_case(name)
+    return [kkt.qp_solution(case.problem(b), case.X0[b], lbe, ube) for b in range(case.B)]

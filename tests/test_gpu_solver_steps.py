@@ -1,0 +1,166 @@
+"""GPU: single steps of the batched solver (csrc/solver.hip) against a dense float64 KKT reference.
+
+`nempc_solve` with max_iter = k returns the iterate after k accepted steps (the last iteration of a budget runs its
+acceptance test), and each step is the solution of a KKT system the oracle builds densely (tests/kkt_reference.py).  The
+existing solver tests check where a solve ends; a globalised SQP method gets there with a wrong direction too -- these
+check the direction: the Riccati recursion, the cross term Qux, the Lagrangian blocks, the costates, the terminal weight,
+the off-diagonals of Q / R / QT and the linear cost terms.
+
+Tolerances are not taken from the device: per case, e = |riccati_step(handle's dtype) - newton_step(float64)|inf on the
+CPU is what a correct sweep in that precision loses on that system; 10 e is allowed, floored at 1e-12 (1 + |z|inf)
+(solver_step_cases.step_tolerance).  Largest tolerance over the problems of each shape:
+
+  (a) one Newton step, linear networks                       (b) cumulative over the steps, tanh networks
+  2x1_discret  H=1 1.8e-12  H=2 2.1e-12  H=3 2.3e-12          2x1_h20    3.1e-13 3.3e-13 3.7e-13 -> floor ~3e-12
+               H=20 5.9e-12  H=63 2.1e-11                     2x1_h63    1.0e-12 1.4e-12 1.6e-12
+  2x1_global   H=355 1.3e-10                                  6x3_rk4    floor ~1.5e-12
+  6x3_rk4 2.0e-12   3x2_unity 1.8e-12   5x2_one_layer 1.9e-12 3x2_unity  floor ~1.6e-12
+  roll3_fwd 2.2e-12  roll3_rev 2.1e-12  2x1_extras 2.0e-12    5x2_h9     3.4e-13 3.7e-13 4.1e-13 -> floor ~3e-12
+  2x1_fp32 H=20 2.4e-05                                       6x3_fp32   5.5e-07 8.5e-07
+against steps of order 1 (up to 18 at H = 355) and multipliers up to 1100.
+"""
+import numpy as np
+import pytest
+
+import solver_step_cases as sc
+
+pytestmark = pytest.mark.gpu
+
+BATCHES = (1, 2, 3, 16)     # solver_lq_kernel's staging splits its waves differently for 1, 2 and >= 3 problems per workgroup
+
+
+def _solve(eng, X0, Zi, **kw):
+    Z, st, it, per = eng.solve(X0, Zi, reg=sc.REG, return_iterations=True, **kw)
+    return Z.cpu().double().numpy(), st.cpu().numpy(), it, per.cpu().numpy()
+
+
+def _kernels(eng):
+    return f"variant {eng.kernel_variant}, rows {eng.last_row_kernel}, blocks {eng.last_hess_kernel}"
+
+
+@pytest.mark.parametrize("name,H", sc.QP_CASES)
+def test_one_newton_step_solves_an_equality_constrained_qp(name, H):
+    """Linear networks: the NLP is an equality-constrained convex QP, the Lagrangian blocks are zero and the first step is
+    exact.  After max_iter = 1 the iterate is z0 + dz_ref; a full solve ends there too (status 0 everywhere) and every
+    problem's convergence iteration is at most 3: the Newton step lands on the solution, the next iteration sees a zero step
+    and passes the convergence test, one more is allowed for a deferred acceptance.  Every lq_kernel the row names, B in
+    {1, 2, 3, 16}, cold start (and a random Z_init on two rows).
+
+    Observed on an MI355X: every problem of every row, kernel and batch size converges at iteration 2.  Handle variant,
+    last row kernel, last block kernel, and the largest error as a fraction of the tolerance (one step = full solve):
+      2x1_discret H=1,2,3   mfma  rows_mfma_kernel  rowhess_coop_kernel       0.000
+      2x1_discret H=20      mfma  rows_mfma_kernel  rowhess_coop_kernel       0.025 (random Z_init: 0.025)
+      2x1_discret H=63      mfma  rows_mfma_kernel  rowhess_coop_kernel       0.100
+      2x1_global  H=355     mfma  rows_mfma_kernel  rowhess_coop_kernel       0.100
+      6x3_rk4     H=8       mfma  rows_coop_kernel  rk4:rowhess_coop_kernel   0.003 (random Z_init: 0.004)
+      3x2_unity   H=7       mfma  rows_coop_kernel  rowhess_coop_kernel       0.000
+      5x2_one_layer H=9     valu  rows_valu_kernel  rowhess_valu_kernel       0.006
+      roll3_fwd / roll3_rev mfma  rows_coop_kernel  rowhess_coop_kernel       0.002 / 0.006
+      2x1_extras  H=10      mfma  rows_mfma_kernel  rowhess_coop_kernel       0.003
+      2x1_fp32    H=20      mfma  rows_coop_kernel  rowhess_coop_kernel       0.151
+    (a linear network is not among the fused launch's compiled shapes -- the row kernel is rows_mfma_kernel, not
+    rows_coopfx_kernel, also at 2 x 64 linear -- so the 2/1 rows run the deferred schedule with evaluation, block and
+    acceptance launches of their own; the trial point's blocks from the evaluation launch and the acceptance test inside the
+    next LQ kernel are reached by the tanh 2 x 64 shapes of the next test)"""
+    case = sc.qp_case(name, H)
+    eng = case.engine()
+    bad = []
+    for rnd in ((False, True) if (name, H) in sc.QP_RANDOM_START else (False,)):
+        ref = sc.qp_reference(name, H, rnd)
+        worst1 = worstf = 0.0
+        its = set()
+        for B in BATCHES:
+            X0 = case.bind(eng, B)
+            Zi = eng.to_device(case.Zrand[:B]) if rnd else None
+            for k in case.kernels:
+                Z1, _, _, _ = _solve(eng, X0, Zi, max_iter=1, lq_kernel=k)
+                Zf, st, _, per = _solve(eng, X0, Zi, max_iter=30, lq_kernel=k)
+                its.update(per.tolist())
+                if not (st == 0).all() or per.max() > 3 or per.min() < 1:
+                    bad.append(f"{k} B={B} random={rnd}: status {st.tolist()} convergence iterations {per.tolist()}")
+                for b in range(B):
+                    z0, dz, _, tol, _ = ref[b]
+                    e1, ef = np.abs(Z1[b] - (z0 + dz)).max(), np.abs(Zf[b] - (z0 + dz)).max()
+                    worst1, worstf = max(worst1, e1 / tol), max(worstf, ef / tol)
+                    if not e1 <= tol:
+                        bad.append(f"{k} B={B} b={b} random={rnd}: after one step |Z - (z0 + dz)| = {e1:.3e} > {tol:.3e}")
+                    if not ef <= tol:
+                        bad.append(f"{k} B={B} b={b} random={rnd}: full solve |Z - (z0 + dz)| = {ef:.3e} > {tol:.3e}")
+        print(f"[qp {name} H={H} random={rnd}] {_kernels(eng)}; convergence iterations {sorted(its)}; "
+              f"error / tolerance: one step {worst1:.3f}, full solve {worstf:.3f}")
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("name", list(sc.NL_ROWS))
+def test_three_steps_of_a_nonlinear_solve_follow_the_newton_replay(name):
+    """tanh networks: max_iter = 1, 2, 3 against the full-step SQP replay with lam <- lam+.  Step 2 is the first whose
+    Hessian carries sum lam d2Phi with the costates of step 1 (wrong if the blocks' use in the sweep or the costates are);
+    step 3 checks the costates of a step that had blocks.  Every problem must clear the reference's gates at every compared
+    step (reduced Hessian eigenvalue >= 0.05: no damping restart; l1 merit strictly decreasing under the full step): a gate
+    failure fails the test.  A problem is no longer compared once the reference step is below 1e-6.
+
+    Observed on an MI355X (handle variant mfma everywhere; last row kernel, last block kernel, largest error as a fraction of
+    the tolerance after 1 / 2 / 3 steps):
+      2x1_h20    rows_coopfx_kernel  rowhess_coopfx_kernel    0.017 0.003 0.003   (auto: scan, fused accept path)
+      2x1_h63    rows_coopfx_kernel  rowhess_coopfx_kernel    0.054 0.058 0.012
+      6x3_rk4    rows_mfma_kernel    rk4:rowhess_coop_kernel  0.008 0.006 0.003   (auto: wave, inner-loop line search)
+      3x2_unity  rows_mfma_kernel    rowhess_coop_kernel      0.000 0.000 0.000
+      5x2_h9     rows_mfma_kernel    rowhess_coop_kernel      0.020 0.005 0.003
+      6x3_fp32   rows_mfma_kernel    rk4:rowhess_coop_kernel  0.523 0.131
+    Sharpness, checked once with a local edit: with the Lagrangian block's term of Qux negated in solver_lq_kernel every
+    `thread` case here fails from step 2 on (errors 1e-9 ... 2e-1 against 2e-12) while the one-step QP test above passes."""
+    case = sc.nl_case(name)
+    steps = sc.NL_ROWS[name][8]
+    ref = sc.nl_reference(name)
+    for rp, _ in ref:
+        for s in rp:
+            assert s["eig"] >= sc.GATE_EIG and s["dmerit"] < 0.0, (s["eig"], s["dmerit"])
+    eng = case.engine()
+    X0 = case.bind(eng, case.B)
+    bad = []
+    worst = np.zeros(steps)
+    for k in case.kernels:
+        for it in range(1, steps + 1):
+            Z, _, _, _ = _solve(eng, X0, None, max_iter=it, lq_kernel=k)
+            for b, (rp, cum_e) in enumerate(ref):
+                if any(np.abs(s["dz"]).max() < sc.STOP_STEP for s in rp[:it]):
+                    continue
+                tol = sc.step_tolerance(cum_e[it - 1], rp[it - 1]["z"])
+                e = np.abs(Z[b] - rp[it - 1]["z"]).max()
+                worst[it - 1] = max(worst[it - 1], e / tol)
+                if not e <= tol:
+                    bad.append(f"{k} b={b} after {it} steps: |Z - z_ref| = {e:.3e} > {tol:.3e} (ratio {e / tol:.1f})")
+    print(f"[nl {name}] {_kernels(eng)}; error / tolerance per step {np.round(worst, 3).tolist()}")
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("linesearch", ["loop", "deferred"])
+@pytest.mark.parametrize("barrier", ["primal-dual", "primal"])
+@pytest.mark.parametrize("name", list(sc.BOUNDED_ROWS))
+def test_interior_point_ends_at_the_solution_of_the_bounded_qp(name, barrier, linesearch):
+    """Linear networks with tight control bounds, wide state bounds and one state limit set through the box rows: the
+    converged iterate against the exact active-set solution (kkt.qp_solution).  The reference's smallest active bound
+    multiplier nu_min is at least 1e-3 (asserted), and the tolerance is 10 (mu_min / nu_min + tol_step (1 + |z*|inf)): the
+    distance the barrier's last sub-problem keeps from an active bound plus the stopping test, with a tenfold margin."""
+    mu_min, tol_step = 1e-9, 1e-8
+    case, lbe, ube, given = sc.bounded_case(name)
+    ref = sc.bounded_reference(name)
+    eng = case.engine()
+    eng.set_box_rows(given["box_lo"], given["box_hi"])
+    Z, st, it, per = _solve(eng, case.bind(eng, case.B), None, lb=given["lb"], ub=given["ub"], max_iter=400, barrier=barrier,
+                            linesearch=linesearch, mu_min=mu_min, tol_step=tol_step)
+    assert (st == 0).all(), (st.tolist(), it)
+    H, nx = case.H, case.nx
+    worst, box_active = 0.0, 0
+    for b, (zs, _, nlo, nhi) in enumerate(ref):
+        act = np.concatenate([nlo[nlo > 0], nhi[nhi > 0]])
+        assert act.min() >= sc.NU_MIN and ((nlo + nhi)[H * nx:] > 0).sum() >= 2
+        box_active += int(((nlo + nhi)[:H * nx] > 0).sum())
+        tol = 10.0 * (mu_min / act.min() + tol_step * (1.0 + np.abs(zs).max()))
+        e = np.abs(Z[b] - zs).max()
+        worst = max(worst, e / tol)
+        print(f"[bounded {name} {barrier} {linesearch}] b={b}: {len(act)} active bounds, nu_min {act.min():.3e}, "
+              f"|Z - z*| = {e:.3e}, tolerance {tol:.3e}, iterations {per[b]}")
+        assert e <= tol, (b, e, tol)
+        assert (Z[b] >= lbe - 1e-12).all() and (Z[b] <= ube + 1e-12).all()
+    assert box_active >= 1          # the state limit of the box rows binds
