@@ -182,6 +182,23 @@ int nempc_bind_extra(nempc_handle h, const void* E, int32_t B);
  * tensors cover (evaluations of more problems are refused). */
 int nempc_bind_history(nempc_handle h, const void* hist_x, const void* hist_u, int32_t B);
 
+/* per-problem tracking references and linear costs for subsequent nempc_eval / nempc_rollout / nempc_solve calls.  The
+ * weights Q, R, QT stay the handle's; each of xref, uref, cx, cu that is given replaces the matching array of
+ * nempc_set_objective for problem b by that problem's own block, an array left NULL keeps the shared values:
+ *    f_b = sum_t (x_t - xref_{b,t})' Q|QT (x_t - xref_{b,t}) + (u_t - uref_{b,t})' R (u_t - uref_{b,t})
+ *                + cx_{b,t} . x_t + cu_{b,t} . u_t
+ * (evaluated in this form, subtraction first: the arithmetic of the shared objective, to the bit when the data are equal).
+ *   xref, cx  B blocks of (H,nx), ld_x elements from one problem's block to the next (ld_x >= H*nx);
+ *   uref, cu  B blocks of (H,nu), ld_u elements apart (ld_u >= H*nu).
+ * A leading dimension larger than one block lets a window slide over a longer per-problem reference without a copy: bind
+ * base + k*nx (base + k*nu) for the window that starts at row k.  Device pointers of the handle's dtype, stored not copied,
+ * read in stream order by the launches that follow.  B = problems the arrays cover: an evaluation of more problems is
+ * NEMPC_EINVAL.  All four NULL removes the binding.  nempc_hess / nempc_hess_gn do not read these arrays (the Hessian of
+ * the objective is the weights').  nempc_solve with a binding on a rolling_window > 1 handle is NEMPC_EUNSUPPORTED (the
+ * objective table over the window state is built on the host). */
+int nempc_bind_tracking(nempc_handle h, const void* xref, const void* uref, const void* cx, const void* cu,
+                        int32_t B, int64_t ld_x, int64_t ld_u);
+
 /* extra constraint rows g_box = states.ravel() (a Constraint in the sense of constraints.py:36-63
  * with constant selector Jacobian); lo/hi (nx) host doubles are only reported back through
  * nempc_constraint_bounds. enabled=0 removes the rows. */

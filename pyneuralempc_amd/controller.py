@@ -138,7 +138,36 @@ class NMPC:
             ub[:H * eng.nx] = np.minimum(ub[:H * eng.nx], np.tile(hi, H))
         return eng, X0t.contiguous(), lb, ub
 
-    def next_batch(self, X0, init_z=None, p=None, tvp=None, prev_x=None, prev_u=None, prev_tvp=None, **solver_opts):
+    def _tracking_check(self, X0, L, who, **arrays):
+        """Shapes of the per-problem references / linear costs, checked before anything touches a device: (B,L,d), or (L,d)
+        for one set shared by all problems.  Returns the arrays that were given."""
+        model = self.integrator.model
+        B = 1 if len(np.shape(X0)) < 2 else int(np.shape(X0)[0])
+        given = {}
+        for name, v in arrays.items():
+            if v is None:
+                continue
+            d = int(model.x_dim if name in ("xref", "cx") else model.u_dim)
+            shape = tuple(int(k) for k in np.shape(v))
+            if shape not in ((B, L, d), (L, d)):
+                raise ValueError(f"{who}: {name} must have shape {(B, L, d)} (one per problem) or {(L, d)} (shared), got {shape}")
+            given[name] = v
+        return given
+
+    @staticmethod
+    def _tracking_bind(eng, B, given, offset=0):
+        """Device tensors (B,L,d) of the engine's dtype for the given arrays, bound at `offset`; returns them."""
+        import torch
+        dev = {}
+        for name, v in given.items():
+            t = v.to(device=eng.device, dtype=eng.dtype) if isinstance(v, torch.Tensor) else \
+                torch.as_tensor(np.asarray(v, dtype=np.float64), dtype=eng.dtype, device=eng.device)
+            dev[name] = (t if t.dim() == 3 else t[None].expand(B, -1, -1)).contiguous()
+        eng.bind_tracking(**dev, offset=offset)
+        return dev
+
+    def next_batch(self, X0, init_z=None, p=None, tvp=None, prev_x=None, prev_u=None, prev_tvp=None, xref=None, uref=None,
+                   cx=None, cu=None, **solver_opts):
         """Solve B MPC problems at once on the device (no reference counterpart).  X0 (B,nx) NumPy
         array or device tensor.  Needs the fused device path (device integrator + QuadraticObjective; the only
         extra rows accepted are BoxStateConstraint, which become bounds on the state variables).  Models with
@@ -147,19 +176,30 @@ class NMPC:
         prev_x (w-1, nx) or (B, w-1, nx), prev_u, prev_tvp -- the batched form of set_prev_data (model/tensorflow.py:178-189);
         left out, what set_prev_data stored serves every problem.  solver_opts go to CallbackEngine.solve; init="rollout"
         among them starts from the roll-out of the start's controls (of zero controls without init_z) instead of the
-        reference's tiled x0.  Returns (states (B,H,nx), u (B,H,nu), status (B,) with Optimizer.SUCCESS / FAIL per problem)
-        as NumPy arrays."""
+        reference's tiled x0.  xref / cx (B,H,nx) and uref / cu (B,H,nu), NumPy arrays or device tensors, give every problem
+        its own tracking reference / linear cost in place of the QuadraticObjective's (whose weights stay shared); an (H,d)
+        value serves all problems; an array left out keeps the objective's.  They are bound for this call only (not with
+        rolling-window models: the device solver refuses that combination).  Returns (states (B,H,nx), u (B,H,nu),
+        status (B,) with Optimizer.SUCCESS / FAIL per problem) as NumPy arrays."""
         import torch
-        eng, X0t, lb, ub = self._batch_engine(X0, p, tvp, prev_x, prev_u, prev_tvp, "next_batch")
         H = self.integrator.H
+        given = self._tracking_check(X0, H, "next_batch", xref=xref, uref=uref, cx=cx, cu=cu)
+        eng, X0t, lb, ub = self._batch_engine(X0, p, tvp, prev_x, prev_u, prev_tvp, "next_batch")
         Zi = None if init_z is None else (init_z if isinstance(init_z, torch.Tensor) else eng.to_device(init_z))
-        Z, status, iters = eng.solve(X0t, Zi, lb, ub, **solver_opts)
+        try:
+            if given:
+                self._tracking_bind(eng, int(X0t.shape[0]), given)
+            Z, status, iters = eng.solve(X0t, Zi, lb, ub, **solver_opts)
+        finally:
+            if given:       # the engine is NMPC.next's too: back to the shared objective
+                eng.bind_tracking()
         self.last_batch_iterations = iters
         z = Z.to("cpu", torch.float64).numpy()
         B, nx, nu = z.shape[0], eng.nx, eng.nu
         return z[:, :H * nx].reshape(B, H, nx), z[:, H * nx:].reshape(B, H, nu), status.cpu().numpy()
 
-    def closed_loop_batch(self, X0, steps, p=None, prev_x=None, prev_u=None, disturbance=None, **solver_opts):
+    def closed_loop_batch(self, X0, steps, p=None, prev_x=None, prev_u=None, disturbance=None, xref=None, uref=None, cx=None,
+                          cu=None, **solver_opts):
         """B closed loops of `steps` MPC steps on the device, the plant being the model itself (no reference counterpart:
         the reference's examples step their plant on the host between NMPC.next calls).  Preconditions as next_batch.  Per
         step, on device tensors only: (1) solve -- step 0 from solver_opts' init ("tile" by default), later steps from the
@@ -168,18 +208,22 @@ class NMPC:
         (B, steps, nx) when given; (3) warm start: the controls shifted by one stage, the last repeated, and their roll-out
         from the new x0, so the start satisfies the dynamics also after a disturbance; (4) rolling-window models: the histories
         take in x0 / u0 and are bound again.  The host waits in the solver's own convergence polls and in the final copy only.
-        Returns (X (B,steps+1,nx), U (B,steps,nu), status (steps,B)) as NumPy arrays."""
+        xref / cx (B, steps+H-1, nx) and uref / cu (B, steps+H-1, nu) (or one (steps+H-1, d) schedule for all problems) are
+        per-problem references / linear costs over the whole run: step k scores its horizon against rows k .. k+H-1, bound
+        by offset into the same device tensor (no copy, no synchronisation per step); left out, the QuadraticObjective's
+        (H,d) values serve every step.  Returns (X (B,steps+1,nx), U (B,steps,nu), status (steps,B)) as NumPy arrays."""
         import torch
         model = self.integrator.model
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("steps must be >= 1")
+        given = self._tracking_check(X0, steps + int(self.integrator.H) - 1, "closed_loop_batch", xref=xref, uref=uref, cx=cx, cu=cu)
         if int(getattr(model, "tvp_dim", 0)) > 0:
             raise NotImplementedError("closed_loop_batch: models with time-varying parameters (tvp_dim > 0) are not supported -- "
                                       "a closed loop of `steps` steps needs a tvp schedule of H + steps - 1 rows, longer than the "
                                       "horizon NMPC takes")
         eng, X, lb, ub = self._batch_engine(X0, p, None, prev_x, prev_u, None, "closed_loop_batch")
         B, H, nx, nu = int(X.shape[0]), eng.H, eng.nx, eng.nu
-        steps = int(steps)
-        if steps < 1:
-            raise ValueError("steps must be >= 1")
         D = None
         if disturbance is not None:
             D = disturbance if isinstance(disturbance, torch.Tensor) else eng.to_device(np.asarray(disturbance, dtype=np.float64))
@@ -190,23 +234,30 @@ class NMPC:
         warm_opts = {k: v for k, v in solver_opts.items() if k != "init"}
         warm_opts["mu_init"] = 1e-4
         Xs, Us, Ss, iters, Zi = [X], [], [], [], None
-        for k in range(steps):
-            Z, status, it = eng.solve(X, Zi, lb, ub, **(solver_opts if k == 0 else warm_opts))[:3]
-            iters.append(it)
-            U = Z[:, H * nx:].reshape(B, H, nu).clone()
-            eng.rollout(X, Z=Z)                               # the plant is the model: x+ = Phi(x0, u0)
-            Xn = Z[:, :nx].clone()
-            if D is not None:
-                Xn = Xn + D[:, k]
-            if w > 1:                                         # the window moves on by one step
-                hx = torch.cat([hx[:, 1:], X[:, None, :]], dim=1).contiguous()
-                hu = torch.cat([hu[:, 1:], U[:, :1]], dim=1).contiguous()
-                eng.bind_history(hx, hu)
-            X = Xn.contiguous()
-            Zi = eng.rollout(X, U=torch.cat([U[:, 1:], U[:, -1:]], dim=1))
-            Xs.append(X)
-            Us.append(U[:, 0])
-            Ss.append(status)
+        try:
+            track = self._tracking_bind(eng, B, given) if given else None
+            for k in range(steps):
+                if track and k > 0:                               # the horizon's window of the schedules: rows k .. k+H-1
+                    eng.bind_tracking(**track, offset=k)
+                Z, status, it = eng.solve(X, Zi, lb, ub, **(solver_opts if k == 0 else warm_opts))[:3]
+                iters.append(it)
+                U = Z[:, H * nx:].reshape(B, H, nu).clone()
+                eng.rollout(X, Z=Z)                               # the plant is the model: x+ = Phi(x0, u0)
+                Xn = Z[:, :nx].clone()
+                if D is not None:
+                    Xn = Xn + D[:, k]
+                if w > 1:                                         # the window moves on by one step
+                    hx = torch.cat([hx[:, 1:], X[:, None, :]], dim=1).contiguous()
+                    hu = torch.cat([hu[:, 1:], U[:, :1]], dim=1).contiguous()
+                    eng.bind_history(hx, hu)
+                X = Xn.contiguous()
+                Zi = eng.rollout(X, U=torch.cat([U[:, 1:], U[:, -1:]], dim=1))
+                Xs.append(X)
+                Us.append(U[:, 0])
+                Ss.append(status)
+        finally:
+            if given:       # the engine is NMPC.next's too: back to the shared objective
+                eng.bind_tracking()
         self.last_closed_loop_iterations = iters      # outer iterations of every step's solve (a list; next_batch's int is last_batch_iterations)
         return (torch.stack(Xs, dim=1).to("cpu", torch.float64).numpy(), torch.stack(Us, dim=1).to("cpu", torch.float64).numpy(),
                 torch.stack(Ss, dim=0).cpu().numpy())

@@ -128,4 +128,49 @@ __device__ __forceinline__ void objective_body(int b, int lane, int H, int nx, i
     objective_row<T>(b, lane, H, nx, nu, o, P, Z + (size_t)b * (H * (nx + nu)), f, grad);
 }
 
+// The same objective with per-problem tracking data (nempc_bind_tracking): row b of grad, the references and linear costs of
+// problem p -- each from its bound array (base + p * stride) or, where none is bound, from the shared table.  Lane-to-step
+// mapping, operation order and reduction tree are objective_row_value's, so equal data give equal bits.
+template <typename T>
+__device__ __forceinline__ double objective_row_value_tracking(int b, int p, int lane, int H, int nx, int nu, const ObjOffsets& o,
+                                                               const T* __restrict__ P, const TrackBind& tk,
+                                                               const T* __restrict__ z, T* __restrict__ grad) {
+    const int n = H * (nx + nu);
+    const T *Rm = P + o.R, *Rs = P + o.Rs;
+    const T* xref = tk.xref ? static_cast<const T*>(tk.xref) + (size_t)p * tk.ld_x : P + o.xref;
+    const T* uref = tk.uref ? static_cast<const T*>(tk.uref) + (size_t)p * tk.ld_u : P + o.uref;
+    const T* cx = tk.cx ? static_cast<const T*>(tk.cx) + (size_t)p * tk.ld_x : P + o.cx;
+    const T* cu = tk.cu ? static_cast<const T*>(tk.cu) + (size_t)p * tk.ld_u : P + o.cu;
+    double acc = 0.0;
+    for (int t = lane; t < H; t += 64) {
+        const T* Q = t == H - 1 ? P + o.QT : P + o.Q;
+        const T* Qs = t == H - 1 ? P + o.QTs : P + o.Qs;
+        const T* x = z + t * nx;
+        const T* u = z + H * nx + t * nu;
+        for (int i = 0; i < nx; ++i) {
+            const T dxi = x[i] - xref[t * nx + i];
+            T qd = T(0), qsd = T(0);
+            for (int j = 0; j < nx; ++j) {
+                const T dxj = x[j] - xref[t * nx + j];
+                qd = fma(Q[i * nx + j], dxj, qd);
+                qsd = fma(Qs[i * nx + j], dxj, qsd);
+            }
+            acc += (double)(dxi * qd + cx[t * nx + i] * x[i]);
+            if (grad) grad[(size_t)b * n + t * nx + i] = qsd + cx[t * nx + i];
+        }
+        for (int i = 0; i < nu; ++i) {
+            const T dui = u[i] - uref[t * nu + i];
+            T rd = T(0), rsd = T(0);
+            for (int j = 0; j < nu; ++j) {
+                const T duj = u[j] - uref[t * nu + j];
+                rd = fma(Rm[i * nu + j], duj, rd);
+                rsd = fma(Rs[i * nu + j], duj, rsd);
+            }
+            acc += (double)(dui * rd + cu[t * nu + i] * u[i]);
+            if (grad) grad[(size_t)b * n + H * nx + t * nu + i] = rsd + cu[t * nu + i];
+        }
+    }
+    return wave_sum_lane0(acc);
+}
+
 }  // namespace nempc

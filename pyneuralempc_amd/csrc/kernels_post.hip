@@ -27,6 +27,20 @@ __global__ __launch_bounds__(64) void objective_kernel(int B, int H, int nx, int
     if ((int)blockIdx.x < B) objective_body<T>(blockIdx.x, threadIdx.x, H, nx, nu, o, P, Z, f, grad);
 }
 
+// objective with per-problem tracking data (nempc_bind_tracking): one wave per row of Z, as objective_kernel; prob (optional)
+// maps the row to the caller's problem whose data it is scored against (the solver's compacted batch)
+template <typename T>
+__global__ __launch_bounds__(64) void objective_tracking_kernel(int B, int H, int nx, int nu, ObjOffsets o,
+                                                                const T* __restrict__ P, TrackBind tk,
+                                                                const int* __restrict__ prob, const T* __restrict__ Z,
+                                                                T* __restrict__ f, T* __restrict__ grad) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const double acc = objective_row_value_tracking<T>(b, prob ? prob[b] : b, lane, H, nx, nu, o, P, tk,
+                                                       Z + (size_t)b * (H * (nx + nu)), grad);
+    if (f && lane == 0) f[b] = (T)acc;
+}
+
 // grid (ceil(m*n / (256 * kAsmVPT * 16/sizeof(T))), B)
 // each lane produces VPT x 16 bytes (2 doubles / 4 floats per store), the VPT stores of a lane 256 lanes apart so
 // that every store instruction of a wave is contiguous; the map / tile loads of all VPT vectors are issued
@@ -226,7 +240,20 @@ __global__ __launch_bounds__(256) void assemble_hess_gn_kernel(int cnt, int w, i
 
 }  // namespace
 
+int launch_objective_tracking(Handle& h, int B, const void* Z, void* f, void* grad, const int* prob, hipStream_t s) {
+    ObjOffsets o = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
+    if (h.cfg.dtype == NEMPC_F64)
+        hipLaunchKernelGGL(objective_tracking_kernel<double>, dim3(B), dim3(64), 0, s, B, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
+                           (const double*)h.d_obj, h.track, prob, (const double*)Z, (double*)f, (double*)grad);
+    else
+        hipLaunchKernelGGL(objective_tracking_kernel<float>, dim3(B), dim3(64), 0, s, B, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
+                           (const float*)h.d_obj, h.track, prob, (const float*)Z, (float*)f, (float*)grad);
+    NEMPC_HIP(hipGetLastError());
+    return NEMPC_OK;
+}
+
 int launch_objective(Handle& h, int B, const void* Z, void* f, void* grad, hipStream_t s) {
+    if (h.track.on()) return launch_objective_tracking(h, B, Z, f, grad, nullptr, s);
     ObjOffsets o = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     if (h.cfg.dtype == NEMPC_F64)
         hipLaunchKernelGGL(objective_kernel<double>, dim3(B), dim3(64), 0, s, B, h.cfg.H, h.cfg.nx, h.cfg.nu, o,

@@ -576,6 +576,24 @@ int nempc_bind_history(nempc_handle hh, const void* hist_x, const void* hist_u, 
     return NEMPC_OK;
 }
 
+int nempc_bind_tracking(nempc_handle hh, const void* xref, const void* uref, const void* cx, const void* cu, int32_t B,
+                        int64_t ld_x, int64_t ld_u) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_bind_tracking: null handle");
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    const bool any = xref || uref || cx || cu;
+    if (any && B < 1) return fail(NEMPC_EINVAL, "nempc_bind_tracking: B (problems the arrays cover) must be >= 1");
+    if ((xref || cx) && ld_x < (int64_t)h.cfg.H * h.cfg.nx)
+        return fail(NEMPC_EINVAL, "nempc_bind_tracking: ld_x must be at least H * nx");
+    if ((uref || cu) && ld_u < (int64_t)h.cfg.H * h.cfg.nu)
+        return fail(NEMPC_EINVAL, "nempc_bind_tracking: ld_u must be at least H * nu");
+    h.track = TrackBind{};
+    if (any) {
+        h.track.xref = xref; h.track.uref = uref; h.track.cx = cx; h.track.cu = cu;
+        h.track.ld_x = ld_x; h.track.ld_u = ld_u; h.track.B = B;
+    }
+    return NEMPC_OK;
+}
+
 int nempc_set_box_rows(nempc_handle hh, int enabled, const double* lo, const double* hi) {
     if (!hh) return fail(NEMPC_EINVAL, "nempc_set_box_rows: null handle");
     Handle& h = *reinterpret_cast<Handle*>(hh);
@@ -647,9 +665,16 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
         return fail(NEMPC_ESTATE, "nempc_eval: rolling_window > 1 but nempc_bind_history was not called");
     if (need_rows && ((h.ne > 0 && B > h.extra_B) || (h.w > 1 && B > h.hist_B)))
         return fail(NEMPC_EINVAL, "nempc_eval: B exceeds the batch the bound extras / history cover");
+    // per-problem tracking data (nempc_bind_tracking): the launches that fuse the shared objective get no f / grad (ff, gf)
+    // and the binding's own kernel follows them
+    const bool trk = (f || grad) && h.track.on();
+    if (trk && B > h.track.B) return fail(NEMPC_EINVAL, "nempc_eval: B exceeds the batch the bound tracking data cover");
+    void* const ff = trk ? nullptr : f;
+    void* const gf = trk ? nullptr : grad;
     DeviceGuard dg(h.cfg.device);
     if (!dg.ok) return fail(NEMPC_EHIP, "nempc_eval: hipSetDevice failed");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    auto then_tracking = [&](int r) { return r == NEMPC_OK && trk ? launch_objective_tracking(h, B, Z, f, grad, nullptr, s) : r; };
     int rc;
     if (need_rows) {
         // defects only (IpoptProblem.constraints on its own): the matrix-core kernel skips its reverse sweeps
@@ -658,33 +683,33 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
         void* gout = g ? g : h.d_g_ws;
         // compiled shape: rows, objective and (dense contract) the dense assembly in ONE launch; without a derivative
         // output (g with f / grad: what a line-search trial needs) the same launch runs its forward passes only
-        if (!jac_sparse && (jac_dense || f || grad) && h.variant == NEMPC_KERNEL_MFMA) {
-            rc = launch_eval_fused(h, B, Z, X0, gout, jac_tiles, jac_dense, f, grad, s);
-            if (rc != NEMPC_EUNSUPPORTED) return rc;
+        if (!jac_sparse && (jac_dense || ff || gf) && h.variant == NEMPC_KERNEL_MFMA) {
+            rc = launch_eval_fused(h, B, Z, X0, gout, jac_tiles, jac_dense, ff, gf, s);
+            if (rc != NEMPC_EUNSUPPORTED) return then_tracking(rc);
         }
         // sparse contract (what a real Ipopt run wants: SURVEY 8f-2; the reference hands cyipopt the dense (m, n),
         // optimizer/ipopt.py:88-96): rows, band values in nempc_jac_structure order and the objective from ONE launch -- of
         // the fixed-shape kernel on a compiled shape, of the cooperative kernel on every other plain-model shape it takes.
         // No tile round trip through memory, no assembly launch.
         if (jac_sparse && !jac_dense && h.variant == NEMPC_KERNEL_MFMA) {
-            rc = launch_eval_fused(h, B, Z, X0, gout, jac_tiles, nullptr, f, grad, s, jac_sparse);
-            if (rc != NEMPC_EUNSUPPORTED) return rc;
-            rc = launch_rows_mfma_sparse(h, B, Z, X0, gout, jac_tiles, jac_sparse, f, grad, s);
-            if (rc != NEMPC_EUNSUPPORTED) return rc;
+            rc = launch_eval_fused(h, B, Z, X0, gout, jac_tiles, nullptr, ff, gf, s, jac_sparse);
+            if (rc != NEMPC_EUNSUPPORTED) return then_tracking(rc);
+            rc = launch_rows_mfma_sparse(h, B, Z, X0, gout, jac_tiles, jac_sparse, ff, gf, s);
+            if (rc != NEMPC_EUNSUPPORTED) return then_tracking(rc);
         }
         // dense contract on any shape the cooperative kernel takes (plain models): the dense rows AND the objective leave
         // from the row launch itself -- no assembly launch, no tile round trip through memory, no objective launch
         if (jac_dense && !jac_sparse && h.variant == NEMPC_KERNEL_MFMA) {
-            rc = launch_rows_mfma_dense(h, B, Z, X0, gout, jac_tiles, jac_dense, f, grad, s);
-            if (rc != NEMPC_EUNSUPPORTED) return rc;
+            rc = launch_rows_mfma_dense(h, B, Z, X0, gout, jac_tiles, jac_dense, ff, gf, s);
+            if (rc != NEMPC_EUNSUPPORTED) return then_tracking(rc);
         }
         rc = h.variant != NEMPC_KERNEL_VALU ? launch_rows_mfma(h, B, Z, X0, gout, tiles, s)
                                             : launch_rows_valu(h, B, Z, X0, gout, tiles, s);
         if (rc) return rc;
         // sparse contract with the objective and without the dense matrix: one fused launch
-        if (jac_sparse && !jac_dense && (f || grad)) return launch_post_sparse(h, B, tiles, jac_sparse, Z, f, grad, s);
+        if (jac_sparse && !jac_dense && (ff || gf)) return launch_post_sparse(h, B, tiles, jac_sparse, Z, ff, gf, s);
         if (jac_sparse && (rc = launch_assemble_sparse(h, B, tiles, jac_sparse, s))) return rc;
-        if (jac_dense && (f || grad)) return launch_post(h, B, tiles, jac_dense, Z, f, grad, s);
+        if (jac_dense && (ff || gf)) return launch_post(h, B, tiles, jac_dense, Z, ff, gf, s);
         if (jac_dense && (rc = launch_assemble_dense(h, B, tiles, jac_dense, s))) return rc;
     }
     if ((f || grad) && (rc = launch_objective(h, B, Z, f, grad, s))) return rc;
@@ -770,6 +795,10 @@ int nempc_solve(nempc_handle hh, int32_t B, const void* X0, void* Z, const doubl
     if (h.w > 1 && !h.d_hist_x)
         return fail(NEMPC_ESTATE, "nempc_solve: rolling_window > 1 but nempc_bind_history was not called");
     if (h.w > 1 && B > h.hist_B) return fail(NEMPC_EINVAL, "nempc_solve: B exceeds the batch the bound history covers");
+    if (h.track.on() && B > h.track.B) return fail(NEMPC_EINVAL, "nempc_solve: B exceeds the batch the bound tracking data cover");
+    if (h.track.on() && h.w > 1)
+        return fail(NEMPC_EUNSUPPORTED, "nempc_solve: per-problem tracking data (nempc_bind_tracking) on a rolling_window > 1 handle: "
+                                        "the objective table over the window state is built on the host");
     if (opts->max_iter < 1 || opts->max_linesearch < 1 || !(opts->mu_factor > 0.0 && opts->mu_factor < 1.0) ||
         !(opts->mu_init > 0.0) || !(opts->mu_min > 0.0) || opts->lq_kernel < 0 || opts->lq_kernel > 3)
         return fail(NEMPC_EINVAL, "nempc_solve: bad options");
@@ -791,6 +820,8 @@ int nempc_rollout(nempc_handle hh, int32_t B, const void* X0, void* Z, void* f, 
         return fail(NEMPC_ESTATE, "nempc_rollout: rolling_window > 1 but nempc_bind_history was not called");
     if ((h.ne > 0 && B > h.extra_B) || (h.w > 1 && B > h.hist_B))
         return fail(NEMPC_EINVAL, "nempc_rollout: B exceeds the batch the bound extras / history cover");
+    if (f && h.track.on() && B > h.track.B)
+        return fail(NEMPC_EINVAL, "nempc_rollout: B exceeds the batch the bound tracking data cover");
     const int which = env_int("NEMPC_ROLLOUT_KERNEL", 0);
     if (which < 0 || which > 2) return fail(NEMPC_EINVAL, "nempc_rollout: NEMPC_ROLLOUT_KERNEL must be 1 (generic) or 2 (matrix-core)");
     DeviceGuard dg(h.cfg.device);

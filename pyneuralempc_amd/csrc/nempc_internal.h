@@ -113,6 +113,15 @@ struct ObjHost {   // host copy of the objective parameters (doubles), re-upload
     std::vector<double> Q, R, xref, uref, cx, cu;
 };
 
+// Per-problem tracking data bound by nempc_bind_tracking: base pointers (dtype of the handle; null = the shared table's
+// array) and the element strides from one problem's block to the next.  B = problems covered, 0 = nothing bound.
+struct TrackBind {
+    const void *xref = nullptr, *uref = nullptr, *cx = nullptr, *cu = nullptr;
+    long long ld_x = 0, ld_u = 0;
+    int B = 0;
+    bool on() const { return xref || uref || cx || cu; }
+};
+
 // Launch geometry of the cooperative kernels: `per_cu` co-resident workgroups on each of the device's `num_cus`
 // compute units (fewer when there are fewer tiles), each owning a contiguous run of tiles_per_wg (+1 for the first
 // tiles_rem workgroups) 16-row tiles.  num_cus comes from hipDeviceProp_t::multiProcessorCount of the handle's device
@@ -140,6 +149,7 @@ struct Handle {
     int w = 1, rev = 0;          // rolling window (1 = plain model), newest-first flag
     const void* d_hist_x = nullptr;  // bound by nempc_bind_history
     const void* d_hist_u = nullptr;
+    TrackBind track;             // bound by nempc_bind_tracking
     RowGather gather() const {
         RowGather gk;
         gk.H = cfg.H; gk.nx = cfg.nx; gk.nu = cfg.nu; gk.n = n; gk.w = w; gk.rev = rev;
@@ -294,7 +304,9 @@ int launch_rowhess_rk4_mfma(Handle& h, int B, const void* Z, const void* X0, con
 void rk4hess_free(Handle& h);
 
 // ---- kernels_post.hip : objective, dense / sparse assembly, hessian assembly
-int launch_objective(Handle& h, int B, const void* Z, void* f, void* grad, hipStream_t s);
+int launch_objective(Handle& h, int B, const void* Z, void* f, void* grad, hipStream_t s);   // (the binding's kernel when one is present)
+// per-problem objective: row b of Z / f / grad is scored against the bound data of problem prob[b] (null: b itself)
+int launch_objective_tracking(Handle& h, int B, const void* Z, void* f, void* grad, const int* prob, hipStream_t s);
 int launch_assemble_hess_gn(Handle& h, int B, const void* tiles, const void* w, const void* sigma, void* hvals, void* hdense,
                             hipStream_t s);
 int launch_assemble_dense(Handle& h, int B, const void* tiles, void* jac, hipStream_t s);

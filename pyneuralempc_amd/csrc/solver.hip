@@ -68,6 +68,10 @@ struct SolverArgs {
     const void* hblk;                                                    // (B,H,nin,nin) Lagrangian blocks
     void* lam; void* lamn;                                               // (B,m) multipliers: current, LQ costates
     const void* obj;  ObjOffsets oo;                                     // Qs, Rs live in the objective block
+    // per-problem tracking data (nempc_bind_tracking; trk.B == 0: none) and, per slot of the working batch, the caller's
+    // index of the problem that sits there (the buffer set's orig[]): the data are the CALLER's problem's, wherever
+    // compaction or a trial list has moved it
+    TrackBind trk; const int* trk_prob;
     const void* lb; const void* ub;                                      // (n) device, dtype T, +-inf allowed
     void* mu; void* pen; void* reg; void* alpha; void* phi0; void* dir;  // (B) per problem (pen = l1 penalty)
     int lq_attempts;      // Riccati sweeps a problem may try per iteration before it sits the iteration out
@@ -1710,7 +1714,11 @@ __device__ __forceinline__ void solver_merit_body(const SolverArgs& a, const T* 
         #pragma unroll
         for (int k = 0; k < PRE_H; ++k) hpre[k] = a.hblk_t && lane + 64 * k < nhb_c ? ((const T*)a.hblk_t)[(size_t)b * nhb_c + lane + 64 * k] : T(0);
     }
-    if (!ft) ftb = (T)wave_bcast_lane0(objective_row_value<T>(b, lane, H, nx, a.nu, a.oo, (const T*)a.obj, zt,
+    if (!ft && a.trk.B > 0)
+        ftb = (T)wave_bcast_lane0(objective_row_value_tracking<T>(b, a.trk_prob[b], lane, H, nx, a.nu, a.oo, (const T*)a.obj, a.trk,
+                                                                  zt, a.carry ? (T*)a.grad_t : (T*)nullptr));
+    else if (!ft)
+        ftb = (T)wave_bcast_lane0(objective_row_value<T>(b, lane, H, nx, a.nu, a.oo, (const T*)a.obj, zt,
                                                                  a.carry ? (T*)a.grad_t : (T*)nullptr));
     if (done) return;
     // log-barrier value and l1 norm of the defects at the trial point, one loop (the loads of both in flight together;
@@ -2311,6 +2319,8 @@ struct Solve {
     bool have_blocks = false;     // ... and so does the block buffer
     bool accept_pending = false;  // the last trial point has been evaluated, its acceptance test has not been launched
     bool published_polls = false, trace = false, compact = false;
+    bool tracking = false;        // per-problem tracking data are bound: no launch that fuses the shared objective; f and grad from
+                                  // the binding's kernel at the iterate and from the acceptance test at a trial point
     static SolverKnobs read_knobs() { static const ProcessKnobs once; return SolverKnobs{once}; }
     static SolverWs& workspace(Handle& h) { return *static_cast<SolverWs*>(h.solver_ws ? h.solver_ws : (h.solver_ws = new SolverWs())); }
     Solve(Handle& hh, int BB, const void* X0_, const nempc_solver_opts& oo, hipStream_t ss)
@@ -2572,6 +2582,7 @@ struct Solve {
         a.Z = ws.Zc[k]; a.lam = ws.lamc[k]; a.mu = ws.muc[k]; a.pen = ws.nuc[k]; a.reg = ws.regc[k];
         a.status = ws.stc[k]; a.iters_done = ws.itc[k]; a.info = ws.infoc[k]; a.zl = ws.zlc[k]; a.zu = ws.zuc[k];
         if (ex_per) h.d_extra = ws.exc[k];
+        a.trk_prob = ws.orig[k];
     }
     // ---- working copies in buffer set 0 (the caller's Z / status are written once, at the end, in the caller's order), the
     //      kernels' arguments, the LQ plan and the routes this solve takes
@@ -2600,6 +2611,8 @@ struct Solve {
         a.grad = ws.grad; a.g = ws.g; a.tiles = ws.tiles;
         a.hblk = ws.hblk; a.lamn = ws.lamn;
         a.obj = obj_dev; a.oo = obj_offsets(H, nx, nu);
+        tracking = h.track.on();
+        a.trk = tracking ? h.track : TrackBind{};
         a.lb = ws.lb; a.ub = ws.ub; a.alpha = ws.alpha; a.phi0 = ws.phi0;
         a.dir = ws.dir; a.lsdone = ws.lsdone; a.n_active = ws.n_active; a.n_pending = ws.n_active + 1; a.n_done = ws.n_active + 2;
         a.dz = ws.dz; a.Kst = ws.Kst;
@@ -2700,14 +2713,17 @@ struct Solve {
             // arithmetic whichever way an iterate's evaluation was obtained: blocks, defects, tiles; f and grad below
         } else {
             // compiled shapes: defects, tiles, f and grad from one launch
-            fused_eval = h.variant == NEMPC_KERNEL_MFMA &&
+            fused_eval = h.variant == NEMPC_KERNEL_MFMA && !tracking &&
                          (rc = launch_eval_fused(h, Bact, Zc, X0c, ws.g, ws.tiles, nullptr, ws.f, ws.grad, s)) != NEMPC_EUNSUPPORTED;
             if (!fused_eval) rc = launch_rows(Bact, Zc, X0c, ws.g, ws.tiles, nullptr);
             if (rc) return rc;
             rc = launch_blocks(Bact, Zc, X0c, lam, ws.hblk);
         }
         if (rc) return rc;
-        return fused_eval ? NEMPC_OK : launch_objective(h, Bact, Zc, ws.f, ws.grad, s);
+        if (fused_eval) return NEMPC_OK;
+        // (slot i of the working batch holds the caller's problem orig[i]: its own references and linear costs)
+        return tracking ? launch_objective_tracking(h, Bact, Zc, ws.f, ws.grad, ws.orig[cur], s)
+                        : launch_objective(h, Bact, Zc, ws.f, ws.grad, s);
     }
     void launch_lq() {
         // bounds: barrier diagonal for the LQ model, barrier gradient folded into grad
@@ -2815,6 +2831,7 @@ struct Solve {
                 if (rc == NEMPC_EUNSUPPORTED) hess_trial = false;
                 else { trial_done = true; a.carry = 1; a.hblk_t = ws.hblk_t; }
             }
+            if (carry && !trial_done && tracking) carry = false;      // (that launch fuses the shared objective)
             if (carry && !trial_done) {
                 // full evaluation of the trial point (tiles and gradient too): it is the next iterate's if accepted
                 fused_trial = (rc = launch_eval_fused(h, nb, ws.Zt, X0t, ws.gt, ws.tiles_t, nullptr, ws.ft, ws.grad_t, s)) !=
@@ -2827,7 +2844,7 @@ struct Solve {
                 rc = roll_eval(ws.Zt, nullptr);
             } else {
                 if (!fused_trial)
-                    fused_trial = h.variant == NEMPC_KERNEL_MFMA &&
+                    fused_trial = h.variant == NEMPC_KERNEL_MFMA && !tracking &&
                         (rc = launch_eval_fused(h, nb, ws.Zt, X0t, ws.gt, nullptr, nullptr, ws.ft, nullptr, s)) != NEMPC_EUNSUPPORTED;
                 if (!fused_trial) rc = launch_rows(nb, ws.Zt, X0t, ws.gt, nullptr, h.d_tiles_ws);
             }

@@ -65,6 +65,7 @@ class CallbackEngine:
         self.nin = self.rolling_window * (self.nx + self.nu)
         self.n_extra = int(n_extra)   # tvp_dim + p_dim of the reference's Model: network inputs that are not variables
         self._extra = None
+        self._tracking = None
         self.integrator = integrator if isinstance(integrator, int) else _lib.INTEGRATOR_IDS[integrator]
         self.DT = float(DT)
         self.kernel = kernel
@@ -128,6 +129,8 @@ class CallbackEngine:
                                                  int(self._extra.shape[0])))
         if self._history is not None:
             self.bind_history(*self._history)
+        if self._tracking is not None:
+            self.bind_tracking(**self._tracking[0], offset=self._tracking[1])
         self._refresh_dims()
         self._buffers = {}
 
@@ -230,6 +233,50 @@ class CallbackEngine:
         _lib.check(self.lib.nempc_bind_history(self._handle, ctypes.c_void_p(self._history[0].data_ptr()),
                                                ctypes.c_void_p(self._history[1].data_ptr()),
                                                int(self._history[0].shape[0])))
+
+    def bind_tracking(self, xref=None, uref=None, cx=None, cu=None, offset=0):
+        """Bind per-problem tracking references / linear costs for the following eval / rollout / solve calls
+        (nempc_bind_tracking): problem b is scored against xref[b], uref[b], cx[b], cu[b]; an array left None keeps the
+        shared values of set_objective, and the weights Q, R, QT stay shared.  xref, cx: device tensors (B,L,nx); uref, cu:
+        (B,L,nu); L >= offset + H, and rows offset .. offset+H-1 of every problem are the horizon's (a window sliding over a
+        longer reference needs no copy: bind the same tensors at the next offset).  The tensors are kept alive here, not
+        copied.  bind_tracking() with nothing removes the binding."""
+        H, given = self.H, {}
+        offset = int(offset)
+        for name, t, d in (("xref", xref, self.nx), ("uref", uref, self.nu), ("cx", cx, self.nx), ("cu", cu, self.nu)):
+            if t is None:
+                continue
+            if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != self.dtype or t.dim() != 3
+                    or t.shape[2] != d or offset < 0 or t.shape[1] < offset + H or t.shape[0] < 1):
+                raise ValueError(f"{name} must be a {self.dtype} tensor (B,L,{d}) on {self.device} with L >= offset + H = "
+                                 f"{offset + H}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+            if t.stride(2) != 1 or t.stride(1) != d or (t.shape[0] > 1 and t.stride(0) < t.shape[1] * d):
+                t = t.contiguous()
+            given[name] = t
+        if not given:
+            self._tracking = None
+            _lib.check(self.lib.nempc_bind_tracking(self._handle, None, None, None, None, 0, 0, 0))
+            return
+        if len({int(t.shape[0]) for t in given.values()}) != 1:
+            raise ValueError("the bound tracking tensors must cover the same batch")
+        ld = {}
+        for key, names, d in (("x", ("xref", "cx"), self.nx), ("u", ("uref", "cu"), self.nu)):
+            ts = [given[k] for k in names if k in given]
+            lds = {int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]) * d for t in ts}
+            if len(lds) > 1:     # one leading dimension per pair in the C interface
+                for k in names:
+                    if k in given:
+                        given[k] = given[k].contiguous()
+                lds = {int(given[k].shape[1]) * d for k in names if k in given}
+                if len(lds) > 1:
+                    raise ValueError(f"{names[0]} and {names[1]} must have the same length L")
+            ld[key] = lds.pop() if lds else 0
+        self._tracking = (given, offset)
+        esz = 8 if self.dtype == torch.float64 else 4
+        ptr = lambda k, d: (ctypes.c_void_p(given[k].data_ptr() + offset * d * esz) if k in given else None)
+        B = int(next(iter(given.values())).shape[0])
+        _lib.check(self.lib.nempc_bind_tracking(self._handle, ptr("xref", self.nx), ptr("uref", self.nu), ptr("cx", self.nx),
+                                                ptr("cu", self.nu), B, ld["x"], ld["u"]))
 
     def _check_extra(self, B):
         if self.n_extra and (self._extra is None or self._extra.shape[0] < B):
