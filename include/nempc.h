@@ -295,6 +295,46 @@ typedef struct nempc_solver_opts {
 int nempc_solve(nempc_handle h, int32_t B, const void* X0, void* Z, const double* lb, const double* ub,
                 const nempc_solver_opts* opts, int32_t* status, int32_t* iters, void* stream);
 
+/* nempc_solve, plus the multipliers the returned iterate carries (Ipopt's mult_g, mult_x_L, mult_x_U; the reference reads
+ * none of them back).  lam (B,m), zl (B,n), zu (B,n): device pointers of the handle's dtype, each may be NULL;
+ * nempc_solve is this call with three NULLs -- same launches, same results.
+ *   Sign convention: g = Phi - x,  L = f + lam.g - zl.(z - lb) + zu.(z - ub),  zl, zu >= 0; stationarity reads
+ *       grad f + J' lam - zl + zu = 0.
+ *   Which multipliers: those of the RETURNED iterate, lam + alpha (lamn - lam) of the last accepted step (lamn the Riccati
+ *   costates of that step's LQ solve) and zl / zu advanced by their own step length -- after max_iter = k full steps they
+ *   are the multipliers of Newton step k exactly as Z is the iterate after k steps.  A trial point whose acceptance test
+ *   was still outstanding when the loop ended is tested first and counts.  lam is zero when no step was accepted (zl / zu
+ *   of a bounded problem then still hold the values the interior point starts from, mu_init / slack at the start).
+ *   lam: the first H*nx entries are the defect multipliers in g order; with box rows enabled the H*nx box-row entries
+ *   are written as zeros (those limits are bounds for this solver: their multipliers are zl / zu of the state variables),
+ *   so lam is what nempc_hess takes.  An infinite bound has multiplier exactly 0.  opts->barrier == 1 (primal barrier, no
+ *   bound multipliers carried): zl = mu/(z - lb), zu = mu/(ub - z) with the problem's final mu.  Problems that did not
+ *   converge (status 1) return what they hold.  Identical to the bit with compact 0 or 1.
+ *   rolling_window > 1 with a non-NULL multiplier pointer: NEMPC_EUNSUPPORTED (the costates of the window state are not
+ *   mapped back). */
+int nempc_solve_duals(nempc_handle h, int32_t B, const void* X0, void* Z, const double* lb, const double* ub,
+                      const nempc_solver_opts* opts, int32_t* status, int32_t* iters, void* lam, void* zl, void* zu,
+                      void* stream);
+
+/* KKT residuals of B primal-dual points (any points: a solver's result or not), in the convention above.
+ *   Z (B,n), X0 (B,nx), lam (B,m) device, required; zl, zu (B,n) device, NULL = zeros; lb, ub (n) HOST doubles as in
+ *   nempc_solve (NULL = unbounded, +-INFINITY allowed), intersected with the box rows on the state variables.
+ *   r (B,4) device out, per problem, with T_t = [A_t | B_t] the Jacobian tile of step t:
+ *     s_x[t] = grad f_x[t] - lam_t + A_{t+1}' lam_{t+1} (no last term at t = H-1) [+ lam_box[t]] - zl + zu
+ *     s_u[t] = grad f_u[t] + B_t' lam_t - zl + zu
+ *     r[0] = |s|_inf                                                     stationarity
+ *     r[1] = max(|defects|_inf, max_i (lb_i - z_i)+, (z_i - ub_i)+)      primal feasibility
+ *     r[2] = max_i over FINITE bounds |zl_i (z_i - lb_i)|, |zu_i (ub_i - z_i)|   complementarity
+ *     r[3] = max(0, max_i -zl_i, max_i -zu_i)                            dual feasibility
+ *   stat (B,n) device out, optional: s.  Entries of zl / zu on an infinite bound count as zero everywhere.
+ * One evaluation by the handle's own kernels (what nempc_eval launches for grad, g, jac_tiles: every kernel family, the
+ * extras and tracking bindings, both dtypes) into buffers the handle owns, then one kernel that forms J' lam from the
+ * compact tiles and reduces the four norms in double.  Asynchronous on `stream`, except that bounds that differ from the
+ * previous call's are uploaded with a stream synchronisation.  Argument checks and codes as nempc_eval (a batch larger
+ * than a binding covers: NEMPC_EINVAL); rolling_window > 1: NEMPC_EUNSUPPORTED. */
+int nempc_kkt_residual(nempc_handle h, int32_t B, const void* Z, const void* X0, const void* lam, const void* zl,
+                       const void* zu, const double* lb, const double* ub, void* r, void* stat, void* stream);
+
 /* Forward simulation of the handle's model (no reference counterpart: the reference never integrates its model over the
  * horizon on its own -- its cold start tiles x0, optimizer/ipopt.py:149, and its examples step the plant outside the library).
  *   Z (B,n) device, in/out: the controls are read from Z[:, H*nx:] and are not written; the states Z[:, :H*nx] are

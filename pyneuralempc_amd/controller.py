@@ -167,7 +167,7 @@ class NMPC:
         return dev
 
     def next_batch(self, X0, init_z=None, p=None, tvp=None, prev_x=None, prev_u=None, prev_tvp=None, xref=None, uref=None,
-                   cx=None, cu=None, **solver_opts):
+                   cx=None, cu=None, return_duals=False, **solver_opts):
         """Solve B MPC problems at once on the device (no reference counterpart).  X0 (B,nx) NumPy
         array or device tensor.  Needs the fused device path (device integrator + QuadraticObjective; the only
         extra rows accepted are BoxStateConstraint, which become bounds on the state variables).  Models with
@@ -180,7 +180,9 @@ class NMPC:
         its own tracking reference / linear cost in place of the QuadraticObjective's (whose weights stay shared); an (H,d)
         value serves all problems; an array left out keeps the objective's.  They are bound for this call only (not with
         rolling-window models: the device solver refuses that combination).  Returns (states (B,H,nx), u (B,H,nu),
-        status (B,) with Optimizer.SUCCESS / FAIL per problem) as NumPy arrays."""
+        status (B,) with Optimizer.SUCCESS / FAIL per problem) as NumPy arrays.  return_duals=True appends the multipliers the
+        returned iterates carry, as CallbackEngine.solve hands them back: a dict of device tensors {"lam": (B,m), "zl": (B,n),
+        "zu": (B,n)} for the bounds the controller builds from its DomainConstraint (box rows folded in)."""
         import torch
         H = self.integrator.H
         given = self._tracking_check(X0, H, "next_batch", xref=xref, uref=uref, cx=cx, cu=cu)
@@ -189,14 +191,19 @@ class NMPC:
         try:
             if given:
                 self._tracking_bind(eng, int(X0t.shape[0]), given)
-            Z, status, iters = eng.solve(X0t, Zi, lb, ub, **solver_opts)
+            duals = None
+            if return_duals:
+                Z, status, iters, duals = eng.solve(X0t, Zi, lb, ub, return_duals=True, **solver_opts)
+            else:
+                Z, status, iters = eng.solve(X0t, Zi, lb, ub, **solver_opts)
         finally:
             if given:       # the engine is NMPC.next's too: back to the shared objective
                 eng.bind_tracking()
         self.last_batch_iterations = iters
         z = Z.to("cpu", torch.float64).numpy()
         B, nx, nu = z.shape[0], eng.nx, eng.nu
-        return z[:, :H * nx].reshape(B, H, nx), z[:, H * nx:].reshape(B, H, nu), status.cpu().numpy()
+        res = (z[:, :H * nx].reshape(B, H, nx), z[:, H * nx:].reshape(B, H, nu), status.cpu().numpy())
+        return res + (duals,) if return_duals else res
 
     def closed_loop_batch(self, X0, steps, p=None, prev_x=None, prev_u=None, disturbance=None, xref=None, uref=None, cx=None,
                           cu=None, **solver_opts):

@@ -9,6 +9,7 @@
 //  assemble_hess_*       per-row Lagrangian blocks -> tril values / dense (n,n)  (ipopt.py:66-86)
 #include "nempc_internal.h"
 #include "kernels_obj_impl.h"
+#include "kernels_kkt_impl.h"
 
 namespace nempc {
 
@@ -442,6 +443,55 @@ int launch_assemble_hess_gn(Handle& h, int B, const void* tiles, const void* w, 
     };
     if (hvals) go(nnz, h.d_hess_map, objc, hvals);
     if (hdense) go(nn, h.d_hess_map + (size_t)nnz * h.w, objc + (size_t)nnz * esz, hdense);
+    NEMPC_HIP(hipGetLastError());
+    return NEMPC_OK;
+}
+
+// KKT residuals (nempc_kkt_residual): one wave per problem, four problems per workgroup; the lanes stride over the n
+// variables, each entry by kkt_variable_terms (kernels_kkt_impl.h: the band product J' lam straight from the compact tiles,
+// sums in double), then over the H nx defects; four wave maxima, and lanes 0..3 store one of them each.
+template <typename T>
+__global__ __launch_bounds__(256) void kkt_residual_kernel(int B, int H, int nx, int nu, int m, int box, const T* __restrict__ Z,
+                                                           const T* __restrict__ grad, const T* __restrict__ g,
+                                                           const T* __restrict__ tiles, const T* __restrict__ lam,
+                                                           const T* __restrict__ zl, const T* __restrict__ zu,
+                                                           const double* __restrict__ lb, const double* __restrict__ ub,
+                                                           T* __restrict__ r, T* __restrict__ stat) {
+    const int b = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+    if (b >= B) return;            // (the whole wave leaves: the reductions below need every lane of theirs)
+    const int n = H * (nx + nu), hx = H * nx;
+    const size_t on = (size_t)b * n;
+    const T* zb = Z + on;
+    const T* gradb = grad + on;
+    const T* tb = tiles + (size_t)b * hx * (nx + nu);
+    const T* lamb = lam + (size_t)b * m;
+    const T* zlb = zl ? zl + on : nullptr;
+    const T* zub = zu ? zu + on : nullptr;
+    double rs = 0.0, rp = 0.0, rc = 0.0, rd = 0.0;
+    for (int i = lane; i < n; i += 64) {
+        const KktTerms k = kkt_variable_terms<T>(i, H, nx, nu, box != 0, zb, gradb, tb, lamb, zlb, zub, lb, ub);
+        if (stat) stat[on + i] = (T)k.s;
+        rs = fmax(rs, fabs(k.s)); rp = fmax(rp, k.pfeas); rc = fmax(rc, k.comp); rd = fmax(rd, k.dfeas);
+    }
+    for (int i = lane; i < hx; i += 64) rp = fmax(rp, fabs((double)g[(size_t)b * m + i]));
+    rs = wave_bcast_lane0(wave_max_lane0(rs));
+    rp = wave_bcast_lane0(wave_max_lane0(rp));
+    rc = wave_bcast_lane0(wave_max_lane0(rc));
+    rd = wave_bcast_lane0(wave_max_lane0(rd));
+    if (lane < 4) r[(size_t)b * 4 + lane] = (T)(lane == 0 ? rs : (lane == 1 ? rp : (lane == 2 ? rc : rd)));
+}
+
+int launch_kkt_residual(Handle& h, int B, const void* Z, const void* grad, const void* g, const void* tiles, const void* lam,
+                        const void* zl, const void* zu, const double* lb, const double* ub, void* r, void* stat, hipStream_t s) {
+    const dim3 grid((unsigned)((B + 3) / 4)), block(256);
+    if (h.cfg.dtype == NEMPC_F64)
+        hipLaunchKernelGGL(kkt_residual_kernel<double>, grid, block, 0, s, B, h.cfg.H, h.cfg.nx, h.cfg.nu, h.m, h.box ? 1 : 0,
+                           (const double*)Z, (const double*)grad, (const double*)g, (const double*)tiles, (const double*)lam,
+                           (const double*)zl, (const double*)zu, lb, ub, (double*)r, (double*)stat);
+    else
+        hipLaunchKernelGGL(kkt_residual_kernel<float>, grid, block, 0, s, B, h.cfg.H, h.cfg.nx, h.cfg.nu, h.m, h.box ? 1 : 0,
+                           (const float*)Z, (const float*)grad, (const float*)g, (const float*)tiles, (const float*)lam,
+                           (const float*)zl, (const float*)zu, lb, ub, (float*)r, (float*)stat);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
 }

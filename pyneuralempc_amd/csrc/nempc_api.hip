@@ -294,6 +294,8 @@ void destroy_impl(Handle* h) {
     dev_free(h->d_g_ws);
     dev_free(h->d_valu_ws);
     dev_free(h->d_hess_ws);
+    dev_free(h->d_kkt_grad);
+    { void* q = h->d_kkt_bounds; dev_free(q); h->d_kkt_bounds = nullptr; }
     delete h;
 }
 
@@ -431,6 +433,8 @@ int nempc_create(const nempc_config* cfg, nempc_handle* out) {
             if (h->layered_hess && (rc = layered_reserve(*h))) break;
         }
         if ((rc = dev_alloc(&h->d_hess_ws, Bm * cfg->H * h->nin * h->nin * h->esz))) break;
+        if ((rc = dev_alloc(&h->d_kkt_grad, Bm * h->n * h->esz))) break;               // nempc_kkt_residual's evaluation
+        if ((rc = dev_alloc((void**)&h->d_kkt_bounds, (size_t)2 * h->n * sizeof(double)))) break;
         if ((rc = rebuild_structure(*h))) break;
         ObjHost o;
         const int nx = cfg->nx, nu = cfg->nu, H = cfg->H;
@@ -473,7 +477,7 @@ int nempc_reserve(nempc_handle hh, int32_t max_batch) {
     const size_t Bm = (size_t)max_batch;
     rk4hess_free(h);      // sized lazily from max_batch on their next use
     solver_free(h);
-    dev_free(h.d_tiles_ws); dev_free(h.d_valu_ws); dev_free(h.d_hess_ws); dev_free(h.d_g_ws);
+    dev_free(h.d_tiles_ws); dev_free(h.d_valu_ws); dev_free(h.d_hess_ws); dev_free(h.d_g_ws); dev_free(h.d_kkt_grad);
     int rc = NEMPC_OK;
     do {
         if ((rc = dev_alloc(&h.d_tiles_ws, Bm * h.cfg.H * h.cfg.nx * h.nin * h.esz))) break;
@@ -485,6 +489,7 @@ int nempc_reserve(nempc_handle hh, int32_t max_batch) {
         }
         if ((rc = dev_alloc(&h.d_hess_ws, Bm * h.cfg.H * h.nin * h.nin * h.esz))) break;
         if ((rc = dev_alloc(&h.d_g_ws, Bm * h.m * h.esz))) break;
+        if ((rc = dev_alloc(&h.d_kkt_grad, Bm * h.n * h.esz))) break;
     } while (0);
     if (rc) h.cfg.max_batch = 0;   // workspaces are gone: every evaluation is refused until a reserve succeeds
     return rc;
@@ -784,6 +789,12 @@ int nempc_hess_gn(nempc_handle hh, int32_t B, const void* Z, const void* X0, con
 
 int nempc_solve(nempc_handle hh, int32_t B, const void* X0, void* Z, const double* lb, const double* ub,
                 const nempc_solver_opts* opts, int32_t* status, int32_t* iters, void* stream) {
+    return nempc_solve_duals(hh, B, X0, Z, lb, ub, opts, status, iters, nullptr, nullptr, nullptr, stream);
+}
+
+int nempc_solve_duals(nempc_handle hh, int32_t B, const void* X0, void* Z, const double* lb, const double* ub,
+                      const nempc_solver_opts* opts, int32_t* status, int32_t* iters, void* lam, void* zl, void* zu,
+                      void* stream) {
     if (!hh) return fail(NEMPC_EINVAL, "nempc_solve: null handle");
     Handle& h = *reinterpret_cast<Handle*>(hh);
     if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_solve: B outside [0, max_batch]");
@@ -804,7 +815,46 @@ int nempc_solve(nempc_handle hh, int32_t B, const void* X0, void* Z, const doubl
         return fail(NEMPC_EINVAL, "nempc_solve: bad options");
     DeviceGuard dg(h.cfg.device);
     if (!dg.ok) return fail(NEMPC_EHIP, "nempc_solve: hipSetDevice failed");
-    return solver_run(h, B, X0, Z, lb, ub, *opts, status, iters, reinterpret_cast<hipStream_t>(stream));
+    SolverDuals duals;
+    duals.lam = lam; duals.zl = zl; duals.zu = zu;
+    return solver_run(h, B, X0, Z, lb, ub, *opts, status, iters, duals, reinterpret_cast<hipStream_t>(stream));
+}
+
+int nempc_kkt_residual(nempc_handle hh, int32_t B, const void* Z, const void* X0, const void* lam, const void* zl,
+                       const void* zu, const double* lb, const double* ub, void* r, void* stat, void* stream) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_kkt_residual: null handle");
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    if (h.w > 1)
+        return fail(NEMPC_EUNSUPPORTED, "nempc_kkt_residual: rolling_window > 1 handles are not supported (the band product is "
+                                        "built for the tiles of a plain model)");
+    if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_kkt_residual: B outside [0, max_batch]");
+    if (B == 0) return NEMPC_OK;
+    if (!Z || !X0 || !lam || !r) return fail(NEMPC_EINVAL, "nempc_kkt_residual: null argument (Z, X0, lam and r are required)");
+    if (!h.d_kkt_grad || !h.d_kkt_bounds || !h.d_g_ws || !h.d_tiles_ws)
+        return fail(NEMPC_ESTATE, "nempc_kkt_residual: the handle's workspaces are gone (a failed nempc_reserve)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // the bounds the solver would see (box rows intersected), as doubles on the device; uploaded when they change
+    const double *dlb = nullptr, *dub = nullptr;
+    if (lb || ub || h.box) {
+        std::vector<double> both, hi;
+        if (int rc = intersect_bounds(h, lb, ub, false, "nempc_kkt_residual", both, hi)) return rc;
+        both.insert(both.end(), hi.begin(), hi.end());
+        DeviceGuard dgb(h.cfg.device);
+        if (!dgb.ok) return fail(NEMPC_EHIP, "nempc_kkt_residual: hipSetDevice failed");
+        // (bit-wise comparison: -inf / inf compare equal to themselves either way, and a NaN is uploaded every time)
+        if (h.kkt_bounds_host.size() != both.size() ||
+            std::memcmp(h.kkt_bounds_host.data(), both.data(), both.size() * sizeof(double)) != 0) {
+            NEMPC_HIP(hipMemcpyAsync(h.d_kkt_bounds, both.data(), both.size() * sizeof(double), hipMemcpyHostToDevice, s));
+            NEMPC_HIP(hipStreamSynchronize(s));   // `both` is stack-owned
+            h.kkt_bounds_host = both;
+        }
+        dlb = h.d_kkt_bounds; dub = h.d_kkt_bounds + h.n;
+    }
+    // one ordinary evaluation: whatever nempc_eval launches for grad, g and the compact tiles at this shape (its checks too)
+    if (int rc = nempc_eval(hh, B, Z, X0, nullptr, h.d_kkt_grad, h.d_g_ws, nullptr, h.d_tiles_ws, nullptr, stream)) return rc;
+    DeviceGuard dg(h.cfg.device);
+    if (!dg.ok) return fail(NEMPC_EHIP, "nempc_kkt_residual: hipSetDevice failed");
+    return launch_kkt_residual(h, B, Z, h.d_kkt_grad, h.d_g_ws, h.d_tiles_ws, lam, zl, zu, dlb, dub, r, stat, s);
 }
 
 int nempc_rollout(nempc_handle hh, int32_t B, const void* X0, void* Z, void* f, void* stream) {

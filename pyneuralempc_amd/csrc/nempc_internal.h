@@ -200,6 +200,9 @@ struct Handle {
     void* d_valu_ws = nullptr;   // scratch of the generic row kernel
     size_t valu_ws_elems = 0;
     void* d_hess_ws = nullptr;   // (Bmax,H,nin,nin) per-row Lagrangian blocks
+    void* d_kkt_grad = nullptr;  // (Bmax,n) objective gradient of nempc_kkt_residual's evaluation (tiles / g: the two above)
+    double* d_kkt_bounds = nullptr;          // (2,n) doubles: lb | ub of the last nempc_kkt_residual, +-inf kept
+    std::vector<double> kkt_bounds_host;     // ... as last uploaded (empty: nothing uploaded yet)
     void* d_rk4_stage = nullptr; // RK4 Hessian pipeline (allocated on first use): (Bmax*H, 4, nin + 2*nx*nin) stage records,
     void* d_rk4_nu = nullptr;    //   (Bmax*H, 4, nx) stage multipliers,
     void* d_rk4_ht = nullptr;    //   (Bmax*H, 4, nin, nin) contracted stage Hessians
@@ -317,10 +320,24 @@ int launch_post_sparse(Handle& h, int B, const void* tiles, void* vals, const vo
 int launch_assemble_hess(Handle& h, int B, const void* blocks, const void* sigma, void* hvals, void* hdense,
                          hipStream_t s);
 int launch_gn_blocks(Handle& h, int B, const void* tiles, const void* w, void* blocks, hipStream_t s);
+// KKT residuals of B primal-dual points from an evaluation's grad / g / tiles (kernels_kkt_impl.h): r (B,4), stat (B,n) or
+// null; zl / zu null = zeros; lb / ub (n) DEVICE doubles (+-inf for a missing bound) or null = unbounded
+int launch_kkt_residual(Handle& h, int B, const void* Z, const void* grad, const void* g, const void* tiles, const void* lam,
+                        const void* zl, const void* zu, const double* lb, const double* ub, void* r, void* stat, hipStream_t s);
 
 // ---- solver.hip : batched Gauss-Newton SQP
+// the caller's variable bounds (n host doubles each, null = unbounded) intersected with the handle's box rows on the state
+// variables -> lo, hi (n, +-INFINITY for a missing bound).  lo > hi is NEMPC_EINVAL, lo == hi too when `need_interior`;
+// `who` names the entry point in the message.
+int intersect_bounds(const Handle& h, const double* lb, const double* ub, bool need_interior, const char* who,
+                     std::vector<double>& lo, std::vector<double>& hi);
+// multipliers the solver hands back (each may be null): lam (B,m), zl / zu (B,n), device, dtype of the handle
+struct SolverDuals {
+    void *lam = nullptr, *zl = nullptr, *zu = nullptr;
+    bool any() const { return lam || zl || zu; }
+};
 int solver_run(Handle& h, int B, const void* X0, void* Z, const double* lb, const double* ub,
-               const nempc_solver_opts& o, int32_t* status_dev, int32_t* iters_host, hipStream_t s);
+               const nempc_solver_opts& o, int32_t* status_dev, int32_t* iters_host, const SolverDuals& duals, hipStream_t s);
 void solver_free(Handle& h);
 
 // ---- comm.hip : RCCL all-gather of the first controls

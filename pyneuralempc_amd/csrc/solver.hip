@@ -2071,6 +2071,42 @@ __global__ __launch_bounds__(256) void solver_scatter_kernel(int B, int n, const
     }
 }
 
+// ... and the multipliers the returned iterates carry (nempc_solve_duals), a sibling launch of the scatter above: the defect
+// multipliers (zeros on box rows: those limits are bounds here), the bound multipliers -- the carried ones, or mu / slack
+// with the problem's final mu under the primal barrier -- and exact zeros on infinite bounds.  Each output may be null.
+template <typename T>
+__global__ __launch_bounds__(256) void solver_scatter_duals_kernel(int B, int n, int m, int hx, const T* __restrict__ Zc,
+                                                                   const T* __restrict__ lamc, const T* __restrict__ zlc,
+                                                                   const T* __restrict__ zuc, const T* __restrict__ muc,
+                                                                   const T* __restrict__ lb, const T* __restrict__ ub,
+                                                                   const int* __restrict__ orig, int primal_barrier,
+                                                                   T* __restrict__ lam_out, T* __restrict__ zl_out,
+                                                                   T* __restrict__ zu_out) {
+    const int slot = blockIdx.x;
+    if (slot >= B) return;
+    const int o = orig[slot];
+    if (lam_out)
+        for (int i = threadIdx.x; i < m; i += 256) lam_out[(size_t)o * m + i] = i < hx ? lamc[(size_t)slot * m + i] : T(0);
+    if (!zl_out && !zu_out) return;
+    const T mu = muc[slot];
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const size_t k = (size_t)slot * n + i;
+        const T lo = lb[i], hi = ub[i];
+        const bool flo = lo > -std::numeric_limits<T>::max(), fhi = hi < std::numeric_limits<T>::max();
+        T vl = T(0), vu = T(0);
+        if (primal_barrier) {
+            const T z = Zc[k];
+            if (flo && mu > T(0)) vl = mu / (z - lo);
+            if (fhi && mu > T(0)) vu = mu / (hi - z);
+        } else {
+            if (flo) vl = zlc[k];
+            if (fhi) vu = zuc[k];
+        }
+        if (zl_out) zl_out[(size_t)o * n + i] = vl;
+        if (zu_out) zu_out[(size_t)o * n + i] = vu;
+    }
+}
+
 // ---- rolling-window models (model/tensorflow.py:132-340: the network of step t reads the last w states and controls).
 // The Riccati sweeps need a STAGE-wise problem: the window is made the state,
 //     s_tau = [x_tau, x_{tau-1}, .., x_{tau-w+1} | u_{tau-1}, .., u_{tau-w+1}]            (ns = w nx + (w-1) nu entries)
@@ -2297,6 +2333,7 @@ struct RollTablesHost { std::vector<int> src, src0, prim, isprim, dcol, shift; }
 template <typename T>
 struct Solve {
     Handle& h; SolverWs& ws; const nempc_solver_opts& o; const int B; const void* const X0; const hipStream_t s;
+    const SolverDuals duals;      // where the multipliers of the returned iterates go (nempc_solve_duals; all null: nowhere)
     // rolling-window models run as a plain problem in the augmented (window) state, see RollTables: nx, nin, n, m are
     // the SOLVER's stage dimensions; *_r the handle's (the caller's variables, the callbacks' shapes)
     const bool rolling; const int H, nx_r, nu, nin_r, n_r, m_r, back, nx, nin, n, m;
@@ -2323,8 +2360,8 @@ struct Solve {
                                   // the binding's kernel at the iterate and from the acceptance test at a trial point
     static SolverKnobs read_knobs() { static const ProcessKnobs once; return SolverKnobs{once}; }
     static SolverWs& workspace(Handle& h) { return *static_cast<SolverWs*>(h.solver_ws ? h.solver_ws : (h.solver_ws = new SolverWs())); }
-    Solve(Handle& hh, int BB, const void* X0_, const nempc_solver_opts& oo, hipStream_t ss)
-        : h(hh), ws(workspace(hh)), o(oo), B(BB), X0(X0_), s(ss), rolling(h.w > 1), H(h.cfg.H), nx_r(h.cfg.nx), nu(h.cfg.nu),
+    Solve(Handle& hh, int BB, const void* X0_, const nempc_solver_opts& oo, const SolverDuals& dd, hipStream_t ss)
+        : h(hh), ws(workspace(hh)), o(oo), B(BB), X0(X0_), s(ss), duals(dd), rolling(h.w > 1), H(h.cfg.H), nx_r(h.cfg.nx), nu(h.cfg.nu),
           nin_r(h.nin), n_r(h.n), m_r(h.m), back(h.w - 1), nx(rolling ? h.w * nx_r + back * nu : nx_r),
           nin(rolling ? nx + nu : nin_r), n(rolling ? H * (nx + nu) : n_r), m(rolling ? H * nx : m_r), ex_per((size_t)H * h.ne),
           gBn((unsigned)(((size_t)BB * std::max(n, std::max(m, nx)) + 255) / 256)),
@@ -2452,17 +2489,10 @@ struct Solve {
     int upload_bounds(const double* lb, const double* ub) {
         const T big = std::numeric_limits<T>::max();
         std::vector<T> hl(n, -big), hu(n, big);      // (rolling: the copies inside the window state carry no bounds of their own)
+        std::vector<double> blo, bhi;
+        if (int rc = intersect_bounds(h, lb, ub, true, "nempc_solve", blo, bhi)) return rc;
         for (int i = 0; i < n_r; ++i) {
-            double lo = lb ? lb[i] : -INFINITY, hi = ub ? ub[i] : INFINITY;
-            if (h.box && i < H * nx_r) {
-                lo = std::max(lo, h.box_lo[i % nx_r]);
-                hi = std::min(hi, h.box_hi[i % nx_r]);
-            }
-            if (lo > hi) { set_error("nempc_solve: lb > ub"); return NEMPC_EINVAL; }
-            if (lo == hi) {
-                set_error("nempc_solve: lb == ub (a fixed variable has no interior for the barrier); eliminate it from the problem");
-                return NEMPC_EINVAL;
-            }
+            const double lo = blo[i], hi = bhi[i];
             const int k = rolling ? ws.prim_host[i] : i;
             hl[k] = std::isfinite(lo) ? (T)lo : -big;
             hu[k] = std::isfinite(hi) ? (T)hi : big;
@@ -2978,6 +3008,15 @@ struct Solve {
             NEMPC_HIP(hipMemcpyAsync(ws.stc[nxt] + Bact, ws.stc[cur] + Bact, rest * sizeof(int), hipMemcpyDeviceToDevice, s));
             NEMPC_HIP(hipMemcpyAsync(ws.orig[nxt] + Bact, ws.orig[cur] + Bact, rest * sizeof(int), hipMemcpyDeviceToDevice, s));
             NEMPC_HIP(hipMemcpyAsync(ws.itc[nxt] + Bact, ws.itc[cur] + Bact, rest * sizeof(int), hipMemcpyDeviceToDevice, s));
+            // ... with the multipliers they finished with (and the barrier parameter the primal barrier reports them from),
+            // when the caller takes them: nothing else reads those rows of a finished problem
+            if (duals.any()) {
+                const size_t e = sizeof(T);
+                NEMPC_HIP(hipMemcpyAsync((T*)ws.lamc[nxt] + (size_t)Bact * m, (const T*)ws.lamc[cur] + (size_t)Bact * m, rest * m * e, hipMemcpyDeviceToDevice, s));
+                NEMPC_HIP(hipMemcpyAsync((T*)ws.zlc[nxt] + (size_t)Bact * n, (const T*)ws.zlc[cur] + (size_t)Bact * n, rest * n * e, hipMemcpyDeviceToDevice, s));
+                NEMPC_HIP(hipMemcpyAsync((T*)ws.zuc[nxt] + (size_t)Bact * n, (const T*)ws.zuc[cur] + (size_t)Bact * n, rest * n * e, hipMemcpyDeviceToDevice, s));
+                NEMPC_HIP(hipMemcpyAsync((T*)ws.muc[nxt] + Bact, (const T*)ws.muc[cur] + Bact, rest * e, hipMemcpyDeviceToDevice, s));
+            }
         }
         // the unconverged problems now sit in front.  Their exact number is on the device; the host shrinks the
         // launches to the counter it has just read -- taken a period earlier, so an upper bound (problems only ever
@@ -3005,6 +3044,11 @@ struct Solve {
         if (rolling)      // the caller's variables are the primary copies
             hipLaunchKernelGGL(roll_in_kernel<T>, dim3(gRn), dim3(256), 0, s, B, n, n_r, H, nx_r, nx, m_r, ws.rt, (const T*)ws.rZout,
                                (T*)Z, (const T*)nullptr, (T*)nullptr);
+        if (duals.any())  // (plain models only, solver_run: n, m are the caller's)
+            hipLaunchKernelGGL(solver_scatter_duals_kernel<T>, dim3(B), dim3(256), 0, s, B, n, m, H * nx, (const T*)ws.Zc[cur],
+                               (const T*)ws.lamc[cur], (const T*)ws.zlc[cur], (const T*)ws.zuc[cur], (const T*)ws.muc[cur],
+                               (const T*)ws.lb, (const T*)ws.ub, (const int*)ws.orig[cur], has_bounds && o.barrier == 1 ? 1 : 0,
+                               (T*)duals.lam, (T*)duals.zl, (T*)duals.zu);
         NEMPC_HIP(hipGetLastError());
         NEMPC_HIP(hipStreamSynchronize(s));
         if (iters_host) *iters_host = it;
@@ -3018,8 +3062,8 @@ struct Solve {
 // next solve zeroes those words on the assumption that nothing is in flight.  Drain the stream, reset the counters.
 template <typename T>
 static int solve_typed(Handle& h, int B, const void* X0, void* Z, const double* lb, const double* ub,
-                       const nempc_solver_opts& o, int32_t* status_dev, int32_t* iters_host, hipStream_t s) {
-    const int rc = Solve<T>(h, B, X0, o, s).run(Z, lb, ub, status_dev, iters_host);
+                       const nempc_solver_opts& o, int32_t* status_dev, int32_t* iters_host, const SolverDuals& duals, hipStream_t s) {
+    const int rc = Solve<T>(h, B, X0, o, duals, s).run(Z, lb, ub, status_dev, iters_host);
     if (rc != NEMPC_OK) {
         (void)hipStreamSynchronize(s);
         if (SolverWs* w = static_cast<SolverWs*>(h.solver_ws)) {
@@ -3031,10 +3075,36 @@ static int solve_typed(Handle& h, int B, const void* X0, void* Z, const double* 
     return rc;
 }
 
+int intersect_bounds(const Handle& h, const double* lb, const double* ub, bool need_interior, const char* who,
+                     std::vector<double>& lo_out, std::vector<double>& hi_out) {
+    const int hx = h.cfg.H * h.cfg.nx, nx = h.cfg.nx;
+    lo_out.assign(h.n, -INFINITY);
+    hi_out.assign(h.n, INFINITY);
+    for (int i = 0; i < h.n; ++i) {
+        double lo = lb ? lb[i] : -INFINITY, hi = ub ? ub[i] : INFINITY;
+        if (h.box && i < hx) {
+            lo = std::max(lo, h.box_lo[i % nx]);
+            hi = std::min(hi, h.box_hi[i % nx]);
+        }
+        if (lo > hi) { set_error(std::string(who) + ": lb > ub"); return NEMPC_EINVAL; }
+        if (need_interior && lo == hi) {
+            set_error(std::string(who) + ": lb == ub (a fixed variable has no interior for the barrier); eliminate it from the problem");
+            return NEMPC_EINVAL;
+        }
+        lo_out[i] = lo; hi_out[i] = hi;
+    }
+    return NEMPC_OK;
+}
+
 int solver_run(Handle& h, int B, const void* X0, void* Z, const double* lb, const double* ub,
-               const nempc_solver_opts& o, int32_t* status_dev, int32_t* iters_host, hipStream_t s) {
-    return h.cfg.dtype == NEMPC_F64 ? solve_typed<double>(h, B, X0, Z, lb, ub, o, status_dev, iters_host, s)
-                                    : solve_typed<float>(h, B, X0, Z, lb, ub, o, status_dev, iters_host, s);
+               const nempc_solver_opts& o, int32_t* status_dev, int32_t* iters_host, const SolverDuals& duals, hipStream_t s) {
+    if (duals.any() && h.w > 1) {
+        set_error("nempc_solve_duals: multipliers of a rolling_window > 1 handle are not supported (the costates of the window "
+                  "state are not mapped back to the caller's rows); pass NULL for lam, zl and zu");
+        return NEMPC_EUNSUPPORTED;
+    }
+    return h.cfg.dtype == NEMPC_F64 ? solve_typed<double>(h, B, X0, Z, lb, ub, o, status_dev, iters_host, duals, s)
+                                    : solve_typed<float>(h, B, X0, Z, lb, ub, o, status_dev, iters_host, duals, s);
 }
 
 }  // namespace nempc

@@ -497,7 +497,8 @@ class CallbackEngine:
 
     def solve(self, X0, Z_init=None, lb=None, ub=None, max_iter=200, max_linesearch=6, check_every=4,
               tol_constraint=None, tol_step=None, mu_init=1e-1, mu_min=None, mu_factor=0.2, reg=None, lq_kernel="auto",
-              compact=True, return_iterations=False, barrier="primal-dual", linesearch="auto", lq_attempts=0, init="tile"):
+              compact=True, return_iterations=False, barrier="primal-dual", linesearch="auto", lq_attempts=0, init="tile",
+              return_duals=False):
         """Batched on-device solve (Gauss-Newton SQP, see csrc/solver.hip).  X0 (B,nx) device tensor; Z_init (B,n)
         or None for the reference's cold start [x0 tiled H ; zeros] (optimizer/ipopt.py:149); init="rollout" makes the start
         dynamically feasible instead: the states of the start (Z_init's, or of zero controls) are replaced by the roll-out of
@@ -509,7 +510,9 @@ class CallbackEngine:
         (about half the time per iteration at the 2/1 shape, more iterations for hard problems), "auto" defers for small
         stages and loops for matrix-core-bound ones; lq_attempts bounds the Riccati sweeps a problem may try per iteration
         (0: the library's default of 3).  Returns (Z (B,n), status (B,) int32 [0 ok / 1 fail], iters) [+ per-problem convergence
-        iteration (B,) int32 with return_iterations=True]."""
+        iteration (B,) int32 with return_iterations=True] [+ with return_duals=True, last, the multipliers the returned
+        iterates carry (nempc_solve_duals): {"lam": (B,m), "zl": (B,n), "zu": (B,n)} device tensors in the convention
+        grad f + J' lam - zl + zu = 0, zl, zu >= 0; lam goes straight into `hess` and `kkt_residual`]."""
         B = int(X0.shape[0])
         self._check_in(X0, (B, self.nx), "X0")
         self._check_extra(B)
@@ -550,13 +553,59 @@ class CallbackEngine:
                                     linesearch={"auto": 0, "loop": 1, "deferred": 2}[linesearch], lq_attempts=int(lq_attempts))
         status = torch.empty(B, dtype=torch.int32, device=self.device)
         iters = ctypes.c_int32(0)
+        duals = None
+        if return_duals:
+            duals = {"lam": torch.empty(B, self.m, dtype=self.dtype, device=self.device),
+                     "zl": torch.empty(B, self.n, dtype=self.dtype, device=self.device),
+                     "zu": torch.empty(B, self.n, dtype=self.dtype, device=self.device)}
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.nempc_solve(self._handle, B, ctypes.c_void_p(X0.data_ptr()), ctypes.c_void_p(Z.data_ptr()),
-                                            ptrs[0], ptrs[1], ctypes.byref(opts), ctypes.c_void_p(status.data_ptr()),
-                                            ctypes.byref(iters), self._stream()))
-        if return_iterations:
-            return Z, status, iters.value, its_dev
-        return Z, status, iters.value
+            if duals is None:
+                _lib.check(self.lib.nempc_solve(self._handle, B, ctypes.c_void_p(X0.data_ptr()), ctypes.c_void_p(Z.data_ptr()),
+                                                ptrs[0], ptrs[1], ctypes.byref(opts), ctypes.c_void_p(status.data_ptr()),
+                                                ctypes.byref(iters), self._stream()))
+            else:
+                _lib.check(self.lib.nempc_solve_duals(self._handle, B, ctypes.c_void_p(X0.data_ptr()),
+                                                      ctypes.c_void_p(Z.data_ptr()), ptrs[0], ptrs[1], ctypes.byref(opts),
+                                                      ctypes.c_void_p(status.data_ptr()), ctypes.byref(iters),
+                                                      ctypes.c_void_p(duals["lam"].data_ptr()),
+                                                      ctypes.c_void_p(duals["zl"].data_ptr()),
+                                                      ctypes.c_void_p(duals["zu"].data_ptr()), self._stream()))
+        res = (Z, status, iters.value) + ((its_dev,) if return_iterations else ()) + ((duals,) if return_duals else ())
+        return res
+
+    def kkt_residual(self, Z, X0, lam, zl=None, zu=None, lb=None, ub=None, want_stat=False):
+        """KKT residuals of B primal-dual points (nempc_kkt_residual; any points, a solver's or not).  Z (B,n), X0 (B,nx),
+        lam (B,m) device tensors; zl, zu (B,n) multipliers of z >= lb, z <= ub or None (zeros); lb / ub (n) host vectors as in
+        `solve` (None = unbounded; box rows are intersected).  Returns r (B,4) = [stationarity |grad f + J' lam - zl + zu|_inf,
+        primal feasibility, complementarity, dual feasibility] per problem, or (r, stat (B,n)) with the stationarity vector
+        when want_stat (the engine's own output tensors, reused between calls like `eval`'s).  One callback evaluation and
+        one reduction kernel; asynchronous on the current torch stream."""
+        B = int(Z.shape[0])
+        self._check_in(Z, (B, self.n), "Z")
+        self._check_in(X0, (B, self.nx), "X0")
+        self._check_in(lam, (B, self.m), "lam")
+        for name, t in (("zl", zl), ("zu", zu)):
+            if t is not None:
+                self._check_in(t, (B, self.n), name)
+        if self.rolling_window == 1:      # (a rolling-window handle is refused by the library, history bound or not)
+            self._check_extra(B)
+        self.reserve(B)
+        keep, ptrs = [], []
+        for v in (lb, ub):
+            if v is None:
+                ptrs.append(None)
+            else:
+                a, p = _as_c_double(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n,)))
+                keep.append(a)
+                ptrs.append(p)
+        r = self._out("kkt_r", (B, 4))
+        stat = self._out("kkt_stat", (B, self.n)) if want_stat else None
+        opt = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nempc_kkt_residual(self._handle, B, ctypes.c_void_p(Z.data_ptr()), ctypes.c_void_p(X0.data_ptr()),
+                                                   ctypes.c_void_p(lam.data_ptr()), opt(zl), opt(zu), ptrs[0], ptrs[1],
+                                                   ctypes.c_void_p(r.data_ptr()), opt(stat), self._stream()))
+        return (r, stat) if want_stat else r
 
     def sync(self):
         _lib.check(self.lib.nempc_sync(self._handle, self._stream()))

@@ -16,17 +16,23 @@ from .slsqp import Slsqp, SlsqpProblemFactory
 
 class DeviceSqp(Slsqp):
     def __init__(self, max_iteration=200, tolerance=None, verbose=0, init_with_last_result=False, warm_mu=1e-4,
-                 **solver_opts):
+                 certificate=False, **solver_opts):
         """tolerance: max |defect| and relative step at convergence (tol_constraint = tol_step); None = what an iterate
         of the model's precision can reach (CallbackEngine.solve: 1e-8 for fp64, 1e-4 for fp32 -- an fp32 iterate stalls
         near 1e-5 and would never report success against 1e-8); warm_mu: initial barrier
         parameter of a warm-started solve (a cold start uses the solver's default of 0.1); solver_opts: further keyword
-        arguments of CallbackEngine.solve (linesearch, lq_kernel, mu_min, ...)."""
+        arguments of CallbackEngine.solve (linesearch, lq_kernel, mu_min, ...).  certificate=True: every solve also takes
+        the multipliers of its result (``last_duals``: {"lam", "zl", "zu"} as NumPy vectors of the one problem) and scores
+        the point on the device (``last_kkt``: stationarity, primal feasibility, complementarity, dual feasibility --
+        CallbackEngine.kkt_residual); without it nothing more than the solve is launched and both stay None."""
         super().__init__(max_iteration=max_iteration, tolerance=tolerance, verbose=verbose,
                          init_with_last_result=init_with_last_result)
         self.warm_mu = warm_mu
         self.solver_opts = dict(solver_opts)
         self.last_iterations = None
+        self.certificate = bool(certificate)
+        self.last_duals = None
+        self.last_kkt = None
 
     def get_factory(self):
         return SlsqpProblemFactory()      # the same problem object: x0, parameters, fused evaluator, initial values
@@ -49,7 +55,13 @@ class DeviceSqp(Slsqp):
             opts["mu_init"] = self.warm_mu
         opts.update(self.solver_opts)
         X0 = eng.to_device(np.asarray(problem.get_init_value(), dtype=np.float64).reshape(1, -1))
-        Z, status, iters = eng.solve(X0, eng.to_device(z0), lb, ub, **opts)
+        if self.certificate:
+            Z, status, iters, duals = eng.solve(X0, eng.to_device(z0), lb, ub, return_duals=True, **opts)
+            r = eng.kkt_residual(Z, X0, duals["lam"], duals["zl"], duals["zu"], lb, ub)
+            self.last_duals = {k: v[0].to("cpu").double().numpy() for k, v in duals.items()}
+            self.last_kkt = r[0].to("cpu").double().numpy()
+        else:
+            Z, status, iters = eng.solve(X0, eng.to_device(z0), lb, ub, **opts)
         self.last_iterations = iters
         if int(status[0].item()) != 0:
             return Optimizer.FAIL
