@@ -335,6 +335,35 @@ int nempc_solve_duals(nempc_handle h, int32_t B, const void* X0, void* Z, const 
 int nempc_kkt_residual(nempc_handle h, int32_t B, const void* Z, const void* X0, const void* lam, const void* zl,
                        const void* zu, const double* lb, const double* ub, void* r, void* stat, void* stream);
 
+/* Solution sensitivities with respect to the initial state (reference counterpart: none -- the reference never
+ * differentiates its solution).  At a primal-dual point (z, lam, zl, zu) the perturbed KKT system
+ *     [[W + Sigma, J'], [J, 0]] [dz ; dlam] = -d/dx0 [grad L ; g],   Sigma_i = zl_i/(z_i - lb_i) + zu_i/(ub_i - z_i)
+ * (finite bounds only; this also serves the primal barrier's zl = mu/d) is an LQ problem with zero linear terms and initial
+ * state dx_{-1} = I: one gain-only backward Riccati sweep (K_t = -Quu_t^-1 Qux_t) and a closed-loop propagation of nx
+ * columns (D_{-1} = I, dU_t = K_t D_{t-1}, D_t = A_t D_{t-1} + B_t dU_t, dlam_t = P_t D_t).  Objective second-order
+ * terms: Q+Q', QT+QT' at t = H-1, R+R'; a tracking binding changes none of them; extras feed the tiles and blocks only.
+ *   Inputs, conventions and bound handling exactly as nempc_kkt_residual: Z (B,n), X0 (B,nx), lam (B,m) device, required
+ *   (box-row entries of lam are not read: those limits are bounds here, as in nempc_solve); zl, zu (B,n) device, NULL =
+ *   zeros; lb, ub (n) HOST doubles, intersected with the box rows, +-INFINITY allowed.
+ *   Outputs: device, dtype of the handle, row-major; each may be NULL, at least one must be given:
+ *     dU0   (B,nu,nx)     du_0* / dx0 = K_0
+ *     dZ    (B,n,nx)      row i = dz_i / dx0, in z order (states, then controls)
+ *     dlam  (B,H*nx,nx)   dlam_t / dx0 = P_t D_t
+ *     gains (B,H,nu,nx)   K_t, with du_t = K_t dx_{t-1}
+ *   status (B) device int32, required: 0 ok; 1 a pivot of some Quu_t was not positive (the point is not a strict local
+ *   minimiser of the barrier problem; NO Levenberg term is ever added: the sensitivity of a regularised problem is a
+ *   different number); 2 a finite bound with a non-zero multiplier has gap <= 0 (Sigma is undefined there; a zero
+ *   multiplier contributes 0 whatever the gap); 2 takes precedence over 1.  On status != 0 every requested output of that
+ *   problem is NaN.
+ * One evaluation by the handle's own kernels for the tiles, the Lagrangian blocks from the dispatch nempc_hess uses, then
+ * one kernel (one wave per problem) whose arithmetic is double whatever the handle's dtype: with an active bound on a
+ * state Sigma reaches 1e11 inside P and single precision loses every digit.  Asynchronous on `stream` apart from the
+ * bound upload; checks and codes as nempc_kkt_residual (rolling_window > 1: NEMPC_EUNSUPPORTED; a batch larger than a
+ * binding covers: NEMPC_EINVAL). */
+int nempc_sensitivity(nempc_handle h, int32_t B, const void* Z, const void* X0, const void* lam, const void* zl,
+                      const void* zu, const double* lb, const double* ub, void* dU0, void* dZ, void* dlam, void* gains,
+                      int32_t* status, void* stream);
+
 /* Forward simulation of the handle's model (no reference counterpart: the reference never integrates its model over the
  * horizon on its own -- its cold start tiles x0, optimizer/ipopt.py:149, and its examples step the plant outside the library).
  *   Z (B,n) device, in/out: the controls are read from Z[:, H*nx:] and are not written; the states Z[:, :H*nx] are

@@ -167,7 +167,7 @@ class NMPC:
         return dev
 
     def next_batch(self, X0, init_z=None, p=None, tvp=None, prev_x=None, prev_u=None, prev_tvp=None, xref=None, uref=None,
-                   cx=None, cu=None, return_duals=False, **solver_opts):
+                   cx=None, cu=None, return_duals=False, return_gain=False, **solver_opts):
         """Solve B MPC problems at once on the device (no reference counterpart).  X0 (B,nx) NumPy
         array or device tensor.  Needs the fused device path (device integrator + QuadraticObjective; the only
         extra rows accepted are BoxStateConstraint, which become bounds on the state variables).  Models with
@@ -182,7 +182,11 @@ class NMPC:
         rolling-window models: the device solver refuses that combination).  Returns (states (B,H,nx), u (B,H,nu),
         status (B,) with Optimizer.SUCCESS / FAIL per problem) as NumPy arrays.  return_duals=True appends the multipliers the
         returned iterates carry, as CallbackEngine.solve hands them back: a dict of device tensors {"lam": (B,m), "zl": (B,n),
-        "zu": (B,n)} for the bounds the controller builds from its DomainConstraint (box rows folded in)."""
+        "zu": (B,n)} for the bounds the controller builds from its DomainConstraint (box rows folded in).  return_gain=True
+        appends (after the duals when both are asked for) the feedback gain K0 = du_0*/dx0 (B,nu,nx) as a NumPy array, for
+        u = u0* + K0 (x_measured - x0) between solves (CallbackEngine.sensitivity at the returned point, from the duals of
+        the same solve and the controller's own bounds); entries are NaN where the sensitivity status, kept in
+        ``self.last_gain_status`` (B,), is non-zero."""
         import torch
         H = self.integrator.H
         given = self._tracking_check(X0, H, "next_batch", xref=xref, uref=uref, cx=cx, cu=cu)
@@ -191,11 +195,15 @@ class NMPC:
         try:
             if given:
                 self._tracking_bind(eng, int(X0t.shape[0]), given)
-            duals = None
-            if return_duals:
+            duals = gain = None
+            if return_duals or return_gain:
                 Z, status, iters, duals = eng.solve(X0t, Zi, lb, ub, return_duals=True, **solver_opts)
             else:
                 Z, status, iters = eng.solve(X0t, Zi, lb, ub, **solver_opts)
+            if return_gain:
+                sens = eng.sensitivity(Z, X0t, duals["lam"], duals["zl"], duals["zu"], lb, ub, want=("du0",))
+                gain = sens["du0"].to("cpu", torch.float64).numpy()
+                self.last_gain_status = sens["status"].cpu().numpy()
         finally:
             if given:       # the engine is NMPC.next's too: back to the shared objective
                 eng.bind_tracking()
@@ -203,7 +211,7 @@ class NMPC:
         z = Z.to("cpu", torch.float64).numpy()
         B, nx, nu = z.shape[0], eng.nx, eng.nu
         res = (z[:, :H * nx].reshape(B, H, nx), z[:, H * nx:].reshape(B, H, nu), status.cpu().numpy())
-        return res + (duals,) if return_duals else res
+        return res + ((duals,) if return_duals else ()) + ((gain,) if return_gain else ())
 
     def closed_loop_batch(self, X0, steps, p=None, prev_x=None, prev_u=None, disturbance=None, xref=None, uref=None, cx=None,
                           cu=None, **solver_opts):

@@ -296,7 +296,31 @@ void destroy_impl(Handle* h) {
     dev_free(h->d_hess_ws);
     dev_free(h->d_kkt_grad);
     { void* q = h->d_kkt_bounds; dev_free(q); h->d_kkt_bounds = nullptr; }
+    { void* q = h->d_sens_ws; dev_free(q); h->d_sens_ws = nullptr; }
     delete h;
+}
+
+// The variable bounds nempc_kkt_residual and nempc_sensitivity see -- the caller's lb / ub (n host doubles each, null =
+// unbounded) intersected with the box rows, as doubles on the device (+-inf kept) -- uploaded when they differ from the
+// previous call's (a stream synchronisation then).  dlb / dub stay null when there is no bound at all.
+int cached_bounds(Handle& h, const double* lb, const double* ub, const char* who, hipStream_t s, const double*& dlb,
+                  const double*& dub) {
+    dlb = dub = nullptr;
+    if (!lb && !ub && !h.box) return NEMPC_OK;
+    std::vector<double> both, hi;
+    if (int rc = intersect_bounds(h, lb, ub, false, who, both, hi)) return rc;
+    both.insert(both.end(), hi.begin(), hi.end());
+    DeviceGuard dgb(h.cfg.device);
+    if (!dgb.ok) return fail(NEMPC_EHIP, std::string(who) + ": hipSetDevice failed");
+    // (bit-wise comparison: -inf / inf compare equal to themselves either way, and a NaN is uploaded every time)
+    if (h.kkt_bounds_host.size() != both.size() ||
+        std::memcmp(h.kkt_bounds_host.data(), both.data(), both.size() * sizeof(double)) != 0) {
+        NEMPC_HIP(hipMemcpyAsync(h.d_kkt_bounds, both.data(), both.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        NEMPC_HIP(hipStreamSynchronize(s));   // `both` is stack-owned
+        h.kkt_bounds_host = both;
+    }
+    dlb = h.d_kkt_bounds; dub = h.d_kkt_bounds + h.n;
+    return NEMPC_OK;
 }
 
 }  // namespace
@@ -435,6 +459,8 @@ int nempc_create(const nempc_config* cfg, nempc_handle* out) {
         if ((rc = dev_alloc(&h->d_hess_ws, Bm * cfg->H * h->nin * h->nin * h->esz))) break;
         if ((rc = dev_alloc(&h->d_kkt_grad, Bm * h->n * h->esz))) break;               // nempc_kkt_residual's evaluation
         if ((rc = dev_alloc((void**)&h->d_kkt_bounds, (size_t)2 * h->n * sizeof(double)))) break;
+        // nempc_sensitivity's double workspaces (plain models only: the call refuses rolling windows)
+        if (h->w == 1 && (rc = dev_alloc((void**)&h->d_sens_ws, sens_ws_doubles(*h, Bm) * sizeof(double)))) break;
         if ((rc = rebuild_structure(*h))) break;
         ObjHost o;
         const int nx = cfg->nx, nu = cfg->nu, H = cfg->H;
@@ -478,6 +504,7 @@ int nempc_reserve(nempc_handle hh, int32_t max_batch) {
     rk4hess_free(h);      // sized lazily from max_batch on their next use
     solver_free(h);
     dev_free(h.d_tiles_ws); dev_free(h.d_valu_ws); dev_free(h.d_hess_ws); dev_free(h.d_g_ws); dev_free(h.d_kkt_grad);
+    { void* q = h.d_sens_ws; dev_free(q); h.d_sens_ws = nullptr; }
     int rc = NEMPC_OK;
     do {
         if ((rc = dev_alloc(&h.d_tiles_ws, Bm * h.cfg.H * h.cfg.nx * h.nin * h.esz))) break;
@@ -490,6 +517,7 @@ int nempc_reserve(nempc_handle hh, int32_t max_batch) {
         if ((rc = dev_alloc(&h.d_hess_ws, Bm * h.cfg.H * h.nin * h.nin * h.esz))) break;
         if ((rc = dev_alloc(&h.d_g_ws, Bm * h.m * h.esz))) break;
         if ((rc = dev_alloc(&h.d_kkt_grad, Bm * h.n * h.esz))) break;
+        if (h.w == 1 && (rc = dev_alloc((void**)&h.d_sens_ws, sens_ws_doubles(h, Bm) * sizeof(double)))) break;
     } while (0);
     if (rc) h.cfg.max_batch = 0;   // workspaces are gone: every evaluation is refused until a reserve succeeds
     return rc;
@@ -833,28 +861,43 @@ int nempc_kkt_residual(nempc_handle hh, int32_t B, const void* Z, const void* X0
     if (!h.d_kkt_grad || !h.d_kkt_bounds || !h.d_g_ws || !h.d_tiles_ws)
         return fail(NEMPC_ESTATE, "nempc_kkt_residual: the handle's workspaces are gone (a failed nempc_reserve)");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    // the bounds the solver would see (box rows intersected), as doubles on the device; uploaded when they change
     const double *dlb = nullptr, *dub = nullptr;
-    if (lb || ub || h.box) {
-        std::vector<double> both, hi;
-        if (int rc = intersect_bounds(h, lb, ub, false, "nempc_kkt_residual", both, hi)) return rc;
-        both.insert(both.end(), hi.begin(), hi.end());
-        DeviceGuard dgb(h.cfg.device);
-        if (!dgb.ok) return fail(NEMPC_EHIP, "nempc_kkt_residual: hipSetDevice failed");
-        // (bit-wise comparison: -inf / inf compare equal to themselves either way, and a NaN is uploaded every time)
-        if (h.kkt_bounds_host.size() != both.size() ||
-            std::memcmp(h.kkt_bounds_host.data(), both.data(), both.size() * sizeof(double)) != 0) {
-            NEMPC_HIP(hipMemcpyAsync(h.d_kkt_bounds, both.data(), both.size() * sizeof(double), hipMemcpyHostToDevice, s));
-            NEMPC_HIP(hipStreamSynchronize(s));   // `both` is stack-owned
-            h.kkt_bounds_host = both;
-        }
-        dlb = h.d_kkt_bounds; dub = h.d_kkt_bounds + h.n;
-    }
+    if (int rc = cached_bounds(h, lb, ub, "nempc_kkt_residual", s, dlb, dub)) return rc;
     // one ordinary evaluation: whatever nempc_eval launches for grad, g and the compact tiles at this shape (its checks too)
     if (int rc = nempc_eval(hh, B, Z, X0, nullptr, h.d_kkt_grad, h.d_g_ws, nullptr, h.d_tiles_ws, nullptr, stream)) return rc;
     DeviceGuard dg(h.cfg.device);
     if (!dg.ok) return fail(NEMPC_EHIP, "nempc_kkt_residual: hipSetDevice failed");
     return launch_kkt_residual(h, B, Z, h.d_kkt_grad, h.d_g_ws, h.d_tiles_ws, lam, zl, zu, dlb, dub, r, stat, s);
+}
+
+int nempc_sensitivity(nempc_handle hh, int32_t B, const void* Z, const void* X0, const void* lam, const void* zl,
+                      const void* zu, const double* lb, const double* ub, void* dU0, void* dZ, void* dlam, void* gains,
+                      int32_t* status, void* stream) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_sensitivity: null handle");
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    if (h.w > 1)
+        return fail(NEMPC_EUNSUPPORTED, "nempc_sensitivity: rolling_window > 1 handles are not supported (the sweep is built "
+                                        "for the stages of a plain model)");
+    if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_sensitivity: B outside [0, max_batch]");
+    if (!dU0 && !dZ && !dlam && !gains) return fail(NEMPC_EINVAL, "nempc_sensitivity: no output asked for (dU0, dZ, dlam, gains all null)");
+    if (B == 0) return NEMPC_OK;
+    if (!Z || !X0 || !lam || !status)
+        return fail(NEMPC_EINVAL, "nempc_sensitivity: null argument (Z, X0, lam and status are required)");
+    // (a tracking binding changes no second-order term, but the batch it covers is checked as nempc_kkt_residual's evaluation does)
+    if (h.track.on() && B > h.track.B) return fail(NEMPC_EINVAL, "nempc_sensitivity: B exceeds the batch the bound tracking data cover");
+    if (!h.d_sens_ws || !h.d_kkt_bounds || !h.d_g_ws || !h.d_tiles_ws || !h.d_hess_ws)
+        return fail(NEMPC_ESTATE, "nempc_sensitivity: the handle's workspaces are gone (a failed nempc_reserve)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const double *dlb = nullptr, *dub = nullptr;
+    if (int rc = cached_bounds(h, lb, ub, "nempc_sensitivity", s, dlb, dub)) return rc;
+    // the tiles from one ordinary evaluation, the Lagrangian blocks from nempc_hess's dispatch (their checks too), both into
+    // buffers the handle owns (not the solver's)
+    if (int rc = nempc_eval(hh, B, Z, X0, nullptr, nullptr, h.d_g_ws, nullptr, h.d_tiles_ws, nullptr, stream)) return rc;
+    // (blocks only: the objective factor, which nempc_hess asks for and only its assembly reads, is not used -- any pointer)
+    if (int rc = nempc_hess(hh, B, Z, X0, lam, lam, nullptr, nullptr, h.d_hess_ws, stream)) return rc;
+    DeviceGuard dg(h.cfg.device);
+    if (!dg.ok) return fail(NEMPC_EHIP, "nempc_sensitivity: hipSetDevice failed");
+    return launch_sensitivity(h, B, Z, h.d_tiles_ws, h.d_hess_ws, zl, zu, dlb, dub, dU0, dZ, dlam, gains, status, s);
 }
 
 int nempc_rollout(nempc_handle hh, int32_t B, const void* X0, void* Z, void* f, void* stream) {

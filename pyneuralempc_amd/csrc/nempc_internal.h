@@ -203,6 +203,7 @@ struct Handle {
     void* d_kkt_grad = nullptr;  // (Bmax,n) objective gradient of nempc_kkt_residual's evaluation (tiles / g: the two above)
     double* d_kkt_bounds = nullptr;          // (2,n) doubles: lb | ub of the last nempc_kkt_residual, +-inf kept
     std::vector<double> kkt_bounds_host;     // ... as last uploaded (empty: nothing uploaded yet)
+    double* d_sens_ws = nullptr;             // nempc_sensitivity (plain models): gains | value matrices | Sigma | scratch (sens_ws_doubles)
     void* d_rk4_stage = nullptr; // RK4 Hessian pipeline (allocated on first use): (Bmax*H, 4, nin + 2*nx*nin) stage records,
     void* d_rk4_nu = nullptr;    //   (Bmax*H, 4, nx) stage multipliers,
     void* d_rk4_ht = nullptr;    //   (Bmax*H, 4, nin, nin) contracted stage Hessians
@@ -324,6 +325,14 @@ int launch_gn_blocks(Handle& h, int B, const void* tiles, const void* w, void* b
 // null; zl / zu null = zeros; lb / ub (n) DEVICE doubles (+-inf for a missing bound) or null = unbounded
 int launch_kkt_residual(Handle& h, int B, const void* Z, const void* grad, const void* g, const void* tiles, const void* lam,
                         const void* zl, const void* zu, const double* lb, const double* ub, void* r, void* stat, hipStream_t s);
+
+// ---- kernels_sens.hip : solution sensitivities dz*/dx0 (nempc_sensitivity)
+size_t sens_ws_doubles(const Handle& h, size_t Bmax);   // elements of Handle::d_sens_ws for a batch of Bmax
+// tiles (B,H,nx,nin), blocks (B,H,nin,nin) of the point; lam is not needed (it is inside the blocks).  zl / zu null = zeros;
+// lb / ub (n) DEVICE doubles or null; outputs as nempc_sensitivity (each may be null), status (B) device
+int launch_sensitivity(Handle& h, int B, const void* Z, const void* tiles, const void* blocks, const void* zl, const void* zu,
+                       const double* lb, const double* ub, void* dU0, void* dZ, void* dlam, void* gains, int32_t* status,
+                       hipStream_t s);
 
 // ---- solver.hip : batched Gauss-Newton SQP
 // the caller's variable bounds (n host doubles each, null = unbounded) intersected with the handle's box rows on the state

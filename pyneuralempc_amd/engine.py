@@ -607,6 +607,50 @@ class CallbackEngine:
                                                    ctypes.c_void_p(r.data_ptr()), opt(stat), self._stream()))
         return (r, stat) if want_stat else r
 
+    def sensitivity(self, Z, X0, lam, zl=None, zu=None, lb=None, ub=None, want=("du0",)):
+        """Solution sensitivities with respect to the initial state at B primal-dual points (nempc_sensitivity; any points,
+        a solver's or not).  Inputs as `kkt_residual`.  want: any of "du0" (B,nu,nx) du_0*/dx0 = K_0 -- the feedback gain of
+        u = u0* + K0 (x_measured - x0) --, "dz" (B,n,nx) rows dz_i/dx0 in z order, "dlam" (B,H*nx,nx), "gains" (B,H,nu,nx)
+        the time-varying K_t with du_t = K_t dx_{t-1}.  Returns a dict of new device tensors with those keys plus "status" (B,)
+        int32: 0 ok; 1 some Quu_t is not positive definite (not a strict local minimiser; nothing is regularised); 2 a
+        non-zero bound multiplier on a gap <= 0.  Outputs of a problem with status != 0 are NaN.  The sweep runs in double
+        whatever the engine's dtype.  One evaluation, one Hessian-block launch and one sweep kernel; asynchronous on the
+        current torch stream."""
+        names = ("du0", "dz", "dlam", "gains")
+        want = tuple(want)
+        if not want or any(k not in names for k in want):
+            raise ValueError(f"want must name at least one of {names}")
+        B = int(Z.shape[0])
+        self._check_in(Z, (B, self.n), "Z")
+        self._check_in(X0, (B, self.nx), "X0")
+        self._check_in(lam, (B, self.m), "lam")
+        for name, t in (("zl", zl), ("zu", zu)):
+            if t is not None:
+                self._check_in(t, (B, self.n), name)
+        if self.rolling_window == 1:      # (a rolling-window handle is refused by the library, history bound or not)
+            self._check_extra(B)
+        self.reserve(B)
+        keep, ptrs = [], []
+        for v in (lb, ub):
+            if v is None:
+                ptrs.append(None)
+            else:
+                a, p = _as_c_double(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n,)))
+                keep.append(a)
+                ptrs.append(p)
+        shapes = {"du0": (B, self.nu, self.nx), "dz": (B, self.n, self.nx), "dlam": (B, self.H * self.nx, self.nx),
+                  "gains": (B, self.H, self.nu, self.nx)}
+        res = {k: torch.empty(shapes[k], dtype=self.dtype, device=self.device) for k in want}
+        res["status"] = torch.empty(B, dtype=torch.int32, device=self.device)
+        opt = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nempc_sensitivity(self._handle, B, ctypes.c_void_p(Z.data_ptr()), ctypes.c_void_p(X0.data_ptr()),
+                                                  ctypes.c_void_p(lam.data_ptr()), opt(zl), opt(zu), ptrs[0], ptrs[1],
+                                                  opt(res.get("du0")), opt(res.get("dz")), opt(res.get("dlam")),
+                                                  opt(res.get("gains")), ctypes.c_void_p(res["status"].data_ptr()),
+                                                  self._stream()))
+        return res
+
     def sync(self):
         _lib.check(self.lib.nempc_sync(self._handle, self._stream()))
 

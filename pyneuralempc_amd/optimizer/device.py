@@ -16,7 +16,7 @@ from .slsqp import Slsqp, SlsqpProblemFactory
 
 class DeviceSqp(Slsqp):
     def __init__(self, max_iteration=200, tolerance=None, verbose=0, init_with_last_result=False, warm_mu=1e-4,
-                 certificate=False, **solver_opts):
+                 certificate=False, gain=False, **solver_opts):
         """tolerance: max |defect| and relative step at convergence (tol_constraint = tol_step); None = what an iterate
         of the model's precision can reach (CallbackEngine.solve: 1e-8 for fp64, 1e-4 for fp32 -- an fp32 iterate stalls
         near 1e-5 and would never report success against 1e-8); warm_mu: initial barrier
@@ -24,7 +24,9 @@ class DeviceSqp(Slsqp):
         arguments of CallbackEngine.solve (linesearch, lq_kernel, mu_min, ...).  certificate=True: every solve also takes
         the multipliers of its result (``last_duals``: {"lam", "zl", "zu"} as NumPy vectors of the one problem) and scores
         the point on the device (``last_kkt``: stationarity, primal feasibility, complementarity, dual feasibility --
-        CallbackEngine.kkt_residual); without it nothing more than the solve is launched and both stay None."""
+        CallbackEngine.kkt_residual); without it nothing more than the solve is launched and both stay None.  gain=True:
+        every solve also keeps the feedback gain of its result, ``last_gain`` (nu,nx) = du_0*/dx0 for
+        u = u0* + K0 (x_measured - x0), and ``last_gain_status`` (CallbackEngine.sensitivity: 0 ok, else the gain is NaN)."""
         super().__init__(max_iteration=max_iteration, tolerance=tolerance, verbose=verbose,
                          init_with_last_result=init_with_last_result)
         self.warm_mu = warm_mu
@@ -33,6 +35,9 @@ class DeviceSqp(Slsqp):
         self.certificate = bool(certificate)
         self.last_duals = None
         self.last_kkt = None
+        self.gain = bool(gain)
+        self.last_gain = None
+        self.last_gain_status = None
 
     def get_factory(self):
         return SlsqpProblemFactory()      # the same problem object: x0, parameters, fused evaluator, initial values
@@ -55,11 +60,16 @@ class DeviceSqp(Slsqp):
             opts["mu_init"] = self.warm_mu
         opts.update(self.solver_opts)
         X0 = eng.to_device(np.asarray(problem.get_init_value(), dtype=np.float64).reshape(1, -1))
-        if self.certificate:
+        if self.certificate or self.gain:
             Z, status, iters, duals = eng.solve(X0, eng.to_device(z0), lb, ub, return_duals=True, **opts)
-            r = eng.kkt_residual(Z, X0, duals["lam"], duals["zl"], duals["zu"], lb, ub)
-            self.last_duals = {k: v[0].to("cpu").double().numpy() for k, v in duals.items()}
-            self.last_kkt = r[0].to("cpu").double().numpy()
+            if self.certificate:
+                r = eng.kkt_residual(Z, X0, duals["lam"], duals["zl"], duals["zu"], lb, ub)
+                self.last_duals = {k: v[0].to("cpu").double().numpy() for k, v in duals.items()}
+                self.last_kkt = r[0].to("cpu").double().numpy()
+            if self.gain:
+                sens = eng.sensitivity(Z, X0, duals["lam"], duals["zl"], duals["zu"], lb, ub, want=("du0",))
+                self.last_gain = sens["du0"][0].to("cpu").double().numpy()
+                self.last_gain_status = int(sens["status"][0].item())
         else:
             Z, status, iters = eng.solve(X0, eng.to_device(z0), lb, ub, **opts)
         self.last_iterations = iters
