@@ -17,8 +17,6 @@ namespace nempc {
 
 namespace {
 
-constexpr size_t kSensLdsBudget = (size_t)150 * 1024;     // (plan_lq's, solver.hip)
-
 struct SensPlan {
     int ppw;            // problems (= waves) per workgroup
     bool use_lds;       // working set in LDS
@@ -36,7 +34,7 @@ SensPlan sens_plan(const Handle& h) {
     const size_t ws_bytes = p.stride * sizeof(double);
     const size_t staged_bytes = ws_bytes + (even(H * nin) + even(H * nu * nx)) * sizeof(double) +
                                 ((H * nx * nin + H * nin * nin + 2 * nx * nx + nu * nu) * h.esz + 15) / 16 * 16;
-    const size_t fit = std::min<size_t>(4, kSensLdsBudget / ws_bytes), fit_staged = std::min<size_t>(4, kSensLdsBudget / staged_bytes);
+    const size_t fit = std::min<size_t>(4, kLqLdsBudget / ws_bytes), fit_staged = std::min<size_t>(4, kLqLdsBudget / staged_bytes);
     p.use_lds = fit >= 1;
     p.staged = p.use_lds && fit_staged == fit;     // (never at the price of fewer problems per workgroup)
     p.ppw = p.use_lds ? (int)fit : 4;

@@ -334,7 +334,10 @@ int launch_sensitivity(Handle& h, int B, const void* Z, const void* tiles, const
                        const double* lb, const double* ub, void* dU0, void* dZ, void* dlam, void* gains, int32_t* status,
                        hipStream_t s);
 
-// ---- solver.hip : batched Gauss-Newton SQP
+// ---- solver.hip : batched Gauss-Newton SQP (host driver; its kernels are in solver_args.h and the solver_*_impl.h headers,
+// which only solver.hip includes)
+// LDS bytes of a workgroup that plan_lq (solver.hip) and sens_plan (kernels_sens.hip) fill with per-problem working sets
+constexpr size_t kLqLdsBudget = (size_t)150 * 1024;
 // the caller's variable bounds (n host doubles each, null = unbounded) intersected with the handle's box rows on the state
 // variables -> lo, hi (n, +-INFINITY for a missing bound).  lo > hi is NEMPC_EINVAL, lo == hi too when `need_interior`;
 // `who` names the entry point in the message.

@@ -7,7 +7,7 @@ solver, so every Problem handed in here has `box=None`.
 Conventions (the oracle's): z = [states (H,nx) ; controls (H,nu)], g = Phi - x, Lagrangian L = f + lam.g, so a Newton
 step of the equality-constrained NLP solves
     [[H, J'], [J, 0]] [dz ; lam+] = -[grad f ; g],      H = d2f + sum_k lam_k d2g_k + reg I on the control block
-(csrc/solver.hip: Quu = Rs + barrier + reg + B'PB -- the Levenberg term sits on the controls only).
+(csrc/solver_lq_impl.h: Quu = Rs + barrier + reg + B'PB -- the Levenberg term sits on the controls only).
 """
 from __future__ import annotations
 

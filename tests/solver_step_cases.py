@@ -19,7 +19,8 @@ KINDS = {"discret": orc.DISCRET, "unity": orc.UNITY, "rk4": orc.RK4}
 
 # The smallest horizon at which plan_lq (csrc/solver.hip) no longer stages a 2/1 fp64 problem in LDS with lq_kernel =
 # "thread": per problem (48 H + 37) doubles at one damping level (39 H of iterate / tiles / blocks / steps, 9 H + 36 of one
-# attempt's gains and temporaries, made odd) against a budget of 150 KiB minus 2 n doubles:
+# attempt's gains and temporaries, made odd) against a budget of 150 KiB (kLqLdsBudget, csrc/nempc_internal.h; counted
+# here on its own) minus 2 n doubles:
 #     8 (48 H + 37) <= 153600 - 48 H   <=>   H <= 354
 H_GLOBAL = 355
 

@@ -107,8 +107,8 @@ def test_three_steps_of_a_nonlinear_solve_follow_the_newton_replay(name):
       3x2_unity  rows_mfma_kernel    rowhess_coop_kernel      0.000 0.000 0.000
       5x2_h9     rows_mfma_kernel    rowhess_coop_kernel      0.020 0.005 0.003
       6x3_fp32   rows_mfma_kernel    rk4:rowhess_coop_kernel  0.523 0.131
-    Sharpness, checked once with a local edit: with the Lagrangian block's term of Qux negated in solver_lq_kernel every
-    `thread` case here fails from step 2 on (errors 1e-9 ... 2e-1 against 2e-12) while the one-step QP test above passes."""
+    Sharpness, checked once with a local edit: with the Lagrangian block's term of Qux negated in solver_lq_kernel
+    (csrc/solver_lq_impl.h) every `thread` case here fails from step 2 on (errors 1e-9 ... 2e-1 against 2e-12) while the one-step QP test above passes."""
     case = sc.nl_case(name)
     steps = sc.NL_ROWS[name][8]
     ref = sc.nl_reference(name)
