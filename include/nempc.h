@@ -199,6 +199,28 @@ int nempc_bind_history(nempc_handle h, const void* hist_x, const void* hist_u, i
 int nempc_bind_tracking(nempc_handle h, const void* xref, const void* uref, const void* cx, const void* cu,
                         int32_t B, int64_t ld_x, int64_t ld_u);
 
+/* per-problem, per-stage lower and upper bounds on the states and controls for subsequent nempc_solve / nempc_solve_duals /
+ * nempc_kkt_residual / nempc_sensitivity calls.  The host lb / ub of those calls stay one vector for the whole batch; each
+ * of xlb, xub, ulb, uub that is given adds problem b's own rows, an array left NULL adds nothing.  The effective bounds of
+ * problem b are the intersection of the host lb / ub of the call (NULL = unbounded), the box rows and that problem's rows:
+ *    max(lb_i, box_lo, xlb_{b,t,j}) <= x_{t,j} = z[t*nx + j] <= min(ub_i, box_hi, xub_{b,t,j}),   likewise u_t with ulb, uub
+ * (x0 is data, not a variable: row t of the x arrays bounds x_t, the state the t-th step arrives at).
+ *   xlb, xub  B blocks of (H,nx), ld_x elements from one problem's block to the next (ld_x >= H*nx);
+ *   ulb, uub  B blocks of (H,nu), ld_u elements apart (ld_u >= H*nu).
+ * A leading dimension larger than one block lets a window slide over a longer per-problem schedule without a copy: bind
+ * base + k*nx (base + k*nu) for the window that starts at row k.  Device pointers of the handle's dtype, stored not copied,
+ * read in stream order by the launches that follow.  +-inf means "no bound there", and so does a value of magnitude at or
+ * above the dtype's max.  B = problems the arrays cover: a solve / KKT / sensitivity call over more problems is
+ * NEMPC_EINVAL.  All four NULL removes the binding.  nempc_eval, nempc_hess / nempc_hess_gn and nempc_rollout do not read
+ * these arrays.  The arrays live on the device, so the host check of lb / ub (lb > ub, lb == ub) cannot see them: a problem
+ * whose effective bounds have a variable with lo >= hi or a NaN fails alone, decided on the device -- nempc_solve returns it
+ * with status 1, 0 iterations and its Z exactly as handed in, the other problems of the batch are not affected; a problem
+ * with no finite effective bound is solved as an unbounded one (zl = zu = 0).  nempc_kkt_residual and nempc_sensitivity do
+ * not validate: an empty interval shows up as r[1] > 0.  nempc_solve with a binding on a rolling_window > 1 handle is
+ * NEMPC_EUNSUPPORTED (the bounds of the window state are built on the host). */
+int nempc_bind_bounds(nempc_handle h, const void* xlb, const void* xub, const void* ulb, const void* uub,
+                      int32_t B, int64_t ld_x, int64_t ld_u);
+
 /* extra constraint rows g_box = states.ravel() (a Constraint in the sense of constraints.py:36-63
  * with constant selector Jacobian); lo/hi (nx) host doubles are only reported back through
  * nempc_constraint_bounds. enabled=0 removes the rows. */

@@ -42,7 +42,7 @@ def split_activation(spec):
     return name, par
 
 EXPORTS = ["nempc_create", "nempc_destroy", "nempc_reserve", "nempc_set_weights", "nempc_set_objective", "nempc_set_terminal_weight", "nempc_set_box_rows", "nempc_bind_extra", "nempc_bind_history",
-           "nempc_bind_tracking",
+           "nempc_bind_tracking", "nempc_bind_bounds",
            "nempc_dims", "nempc_constraint_bounds", "nempc_jac_structure", "nempc_hess_structure", "nempc_eval",
            "nempc_hess", "nempc_hess_gn", "nempc_solve", "nempc_solve_duals", "nempc_kkt_residual", "nempc_sensitivity", "nempc_rollout", "nempc_last_rollout_kernel", "nempc_sync", "nempc_kernel_variant", "nempc_last_row_kernel", "nempc_last_hess_kernel", "nempc_last_error", "nempc_abi_version",
            "nempc_plan_grid", "nempc_num_cus",
@@ -97,6 +97,7 @@ def load():
     lib.nempc_bind_extra.argtypes = [vp, vp, i32]
     lib.nempc_bind_history.argtypes = [vp, vp, vp, i32]
     lib.nempc_bind_tracking.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_int64, ctypes.c_int64]
+    lib.nempc_bind_bounds.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_int64, ctypes.c_int64]
     lib.nempc_dims.argtypes = [vp, ip, ip, ip, ip]
     lib.nempc_constraint_bounds.argtypes = [vp, dp, dp]
     lib.nempc_jac_structure.argtypes = [vp, ip, ip]

@@ -139,15 +139,15 @@ class NMPC:
         return eng, X0t.contiguous(), lb, ub
 
     def _tracking_check(self, X0, L, who, **arrays):
-        """Shapes of the per-problem references / linear costs, checked before anything touches a device: (B,L,d), or (L,d)
-        for one set shared by all problems.  Returns the arrays that were given."""
+        """Shapes of the per-problem references / linear costs / bounds, checked before anything touches a device: (B,L,d), or
+        (L,d) for one set shared by all problems.  Returns the arrays that were given."""
         model = self.integrator.model
         B = 1 if len(np.shape(X0)) < 2 else int(np.shape(X0)[0])
         given = {}
         for name, v in arrays.items():
             if v is None:
                 continue
-            d = int(model.x_dim if name in ("xref", "cx") else model.u_dim)
+            d = int(model.x_dim if name in ("xref", "cx", "xlb", "xub") else model.u_dim)
             shape = tuple(int(k) for k in np.shape(v))
             if shape not in ((B, L, d), (L, d)):
                 raise ValueError(f"{who}: {name} must have shape {(B, L, d)} (one per problem) or {(L, d)} (shared), got {shape}")
@@ -155,19 +155,20 @@ class NMPC:
         return given
 
     @staticmethod
-    def _tracking_bind(eng, B, given, offset=0):
-        """Device tensors (B,L,d) of the engine's dtype for the given arrays, bound at `offset`; returns them."""
+    def _tracking_bind(eng, B, given, offset=0, bind=None):
+        """Device tensors (B,L,d) of the engine's dtype for the given arrays, bound at `offset` (by eng.bind_tracking, or by
+        `bind`: eng.bind_bounds); returns them."""
         import torch
         dev = {}
         for name, v in given.items():
             t = v.to(device=eng.device, dtype=eng.dtype) if isinstance(v, torch.Tensor) else \
                 torch.as_tensor(np.asarray(v, dtype=np.float64), dtype=eng.dtype, device=eng.device)
             dev[name] = (t if t.dim() == 3 else t[None].expand(B, -1, -1)).contiguous()
-        eng.bind_tracking(**dev, offset=offset)
+        (bind or eng.bind_tracking)(**dev, offset=offset)
         return dev
 
     def next_batch(self, X0, init_z=None, p=None, tvp=None, prev_x=None, prev_u=None, prev_tvp=None, xref=None, uref=None,
-                   cx=None, cu=None, return_duals=False, return_gain=False, **solver_opts):
+                   cx=None, cu=None, xlb=None, xub=None, ulb=None, uub=None, return_duals=False, return_gain=False, **solver_opts):
         """Solve B MPC problems at once on the device (no reference counterpart).  X0 (B,nx) NumPy
         array or device tensor.  Needs the fused device path (device integrator + QuadraticObjective; the only
         extra rows accepted are BoxStateConstraint, which become bounds on the state variables).  Models with
@@ -179,7 +180,11 @@ class NMPC:
         reference's tiled x0.  xref / cx (B,H,nx) and uref / cu (B,H,nu), NumPy arrays or device tensors, give every problem
         its own tracking reference / linear cost in place of the QuadraticObjective's (whose weights stay shared); an (H,d)
         value serves all problems; an array left out keeps the objective's.  They are bound for this call only (not with
-        rolling-window models: the device solver refuses that combination).  Returns (states (B,H,nx), u (B,H,nu),
+        rolling-window models: the device solver refuses that combination).  xlb / xub (B,H,nx) and ulb / uub (B,H,nu) in the
+        same forms give every problem its own, per-stage bounds on x_1 .. x_H and u_0 .. u_{H-1}: problem b is solved inside
+        the intersection of the DomainConstraint, the box rows and its own rows (+-inf: no bound there); bound for this call
+        only (CallbackEngine.bind_bounds), and the duals / the gain are those under the same bounds.  A problem whose own
+        bounds leave a variable no interior (lo >= hi) or hold a NaN fails alone: FAIL, its start returned.  Returns (states (B,H,nx), u (B,H,nu),
         status (B,) with Optimizer.SUCCESS / FAIL per problem) as NumPy arrays.  return_duals=True appends the multipliers the
         returned iterates carry, as CallbackEngine.solve hands them back: a dict of device tensors {"lam": (B,m), "zl": (B,n),
         "zu": (B,n)} for the bounds the controller builds from its DomainConstraint (box rows folded in).  return_gain=True
@@ -190,11 +195,14 @@ class NMPC:
         import torch
         H = self.integrator.H
         given = self._tracking_check(X0, H, "next_batch", xref=xref, uref=uref, cx=cx, cu=cu)
+        bounds = self._tracking_check(X0, H, "next_batch", xlb=xlb, xub=xub, ulb=ulb, uub=uub)
         eng, X0t, lb, ub = self._batch_engine(X0, p, tvp, prev_x, prev_u, prev_tvp, "next_batch")
         Zi = None if init_z is None else (init_z if isinstance(init_z, torch.Tensor) else eng.to_device(init_z))
         try:
             if given:
                 self._tracking_bind(eng, int(X0t.shape[0]), given)
+            if bounds:
+                self._tracking_bind(eng, int(X0t.shape[0]), bounds, bind=eng.bind_bounds)
             duals = gain = None
             if return_duals or return_gain:
                 Z, status, iters, duals = eng.solve(X0t, Zi, lb, ub, return_duals=True, **solver_opts)
@@ -207,6 +215,8 @@ class NMPC:
         finally:
             if given:       # the engine is NMPC.next's too: back to the shared objective
                 eng.bind_tracking()
+            if bounds:
+                eng.bind_bounds()
         self.last_batch_iterations = iters
         z = Z.to("cpu", torch.float64).numpy()
         B, nx, nu = z.shape[0], eng.nx, eng.nu
@@ -214,7 +224,7 @@ class NMPC:
         return res + ((duals,) if return_duals else ()) + ((gain,) if return_gain else ())
 
     def closed_loop_batch(self, X0, steps, p=None, prev_x=None, prev_u=None, disturbance=None, xref=None, uref=None, cx=None,
-                          cu=None, **solver_opts):
+                          cu=None, xlb=None, xub=None, ulb=None, uub=None, **solver_opts):
         """B closed loops of `steps` MPC steps on the device, the plant being the model itself (no reference counterpart:
         the reference's examples step their plant on the host between NMPC.next calls).  Preconditions as next_batch.  Per
         step, on device tensors only: (1) solve -- step 0 from solver_opts' init ("tile" by default), later steps from the
@@ -226,13 +236,17 @@ class NMPC:
         xref / cx (B, steps+H-1, nx) and uref / cu (B, steps+H-1, nu) (or one (steps+H-1, d) schedule for all problems) are
         per-problem references / linear costs over the whole run: step k scores its horizon against rows k .. k+H-1, bound
         by offset into the same device tensor (no copy, no synchronisation per step); left out, the QuadraticObjective's
-        (H,d) values serve every step.  Returns (X (B,steps+1,nx), U (B,steps,nu), status (steps,B)) as NumPy arrays."""
+        (H,d) values serve every step.  xlb / xub (B, steps+H-1, nx) and ulb / uub (B, steps+H-1, nu) (or one (steps+H-1, d)
+        schedule) are per-problem, time-varying bounds over the whole run in the same way: step k solves inside rows
+        k .. k+H-1 (row 0 of a u schedule bounds the control applied at step 0, row 0 of an x schedule the state it leads to),
+        intersected with the DomainConstraint and the box rows.  Returns (X (B,steps+1,nx), U (B,steps,nu), status (steps,B)) as NumPy arrays."""
         import torch
         model = self.integrator.model
         steps = int(steps)
         if steps < 1:
             raise ValueError("steps must be >= 1")
         given = self._tracking_check(X0, steps + int(self.integrator.H) - 1, "closed_loop_batch", xref=xref, uref=uref, cx=cx, cu=cu)
+        bounds = self._tracking_check(X0, steps + int(self.integrator.H) - 1, "closed_loop_batch", xlb=xlb, xub=xub, ulb=ulb, uub=uub)
         if int(getattr(model, "tvp_dim", 0)) > 0:
             raise NotImplementedError("closed_loop_batch: models with time-varying parameters (tvp_dim > 0) are not supported -- "
                                       "a closed loop of `steps` steps needs a tvp schedule of H + steps - 1 rows, longer than the "
@@ -251,9 +265,12 @@ class NMPC:
         Xs, Us, Ss, iters, Zi = [X], [], [], [], None
         try:
             track = self._tracking_bind(eng, B, given) if given else None
+            bnd = self._tracking_bind(eng, B, bounds, bind=eng.bind_bounds) if bounds else None
             for k in range(steps):
                 if track and k > 0:                               # the horizon's window of the schedules: rows k .. k+H-1
                     eng.bind_tracking(**track, offset=k)
+                if bnd and k > 0:
+                    eng.bind_bounds(**bnd, offset=k)
                 Z, status, it = eng.solve(X, Zi, lb, ub, **(solver_opts if k == 0 else warm_opts))[:3]
                 iters.append(it)
                 U = Z[:, H * nx:].reshape(B, H, nu).clone()
@@ -273,6 +290,8 @@ class NMPC:
         finally:
             if given:       # the engine is NMPC.next's too: back to the shared objective
                 eng.bind_tracking()
+            if bounds:
+                eng.bind_bounds()
         self.last_closed_loop_iterations = iters      # outer iterations of every step's solve (a list; next_batch's int is last_batch_iterations)
         return (torch.stack(Xs, dim=1).to("cpu", torch.float64).numpy(), torch.stack(Us, dim=1).to("cpu", torch.float64).numpy(),
                 torch.stack(Ss, dim=0).cpu().numpy())

@@ -31,10 +31,12 @@ NEMPC_KKT_HD inline bool kkt_finite(double x) { return x >= -1.7976931348623157e
 // Variable i (< n = H (nx + nu)) of ONE problem.  z, grad (n), tiles (H, nx, nx+nu), lam (m: H nx defect multipliers, then
 // H nx box-row multipliers when `box`) point at that problem's rows; zl / zu (n) may be null (= zeros); lb / ub (n) may be
 // null (= unbounded) and hold +-infinity for a missing bound.  A multiplier on an infinite bound counts as zero.
+// kkt_variable_terms_at takes the variable's two bounds by value (+-infinity for a missing one): the kernel hands it the
+// problem's own effective bounds when per-problem bounds are bound (nempc_bind_bounds).
 template <typename T>
-NEMPC_KKT_HD inline KktTerms kkt_variable_terms(int i, int H, int nx, int nu, bool box, const T* z, const T* grad,
-                                                const T* tiles, const T* lam, const T* zl, const T* zu, const double* lb,
-                                                const double* ub) {
+NEMPC_KKT_HD inline KktTerms kkt_variable_terms_at(int i, int H, int nx, int nu, bool box, const T* z, const T* grad,
+                                                   const T* tiles, const T* lam, const T* zl, const T* zu, double lo,
+                                                   double hi) {
     const int nin = nx + nu, hx = H * nx;
     double s = (double)grad[i];
     if (i < hx) {
@@ -53,8 +55,7 @@ NEMPC_KKT_HD inline KktTerms kkt_variable_terms(int i, int H, int nx, int nu, bo
         for (int k = 0; k < nx; ++k) s += (double)Tt[k * nin + nx + j] * (double)lt[k];
     }
     const double zi = (double)z[i];
-    const double lo = lb ? lb[i] : -1.0, hi = ub ? ub[i] : 1.0;
-    const bool flo = lb && kkt_finite(lo), fhi = ub && kkt_finite(hi);
+    const bool flo = kkt_finite(lo), fhi = kkt_finite(hi);
     const double vl = flo && zl ? (double)zl[i] : 0.0, vu = fhi && zu ? (double)zu[i] : 0.0;
     KktTerms r;
     r.s = s - vl + vu;
@@ -76,6 +77,14 @@ NEMPC_KKT_HD inline KktTerms kkt_variable_terms(int i, int H, int nx, int nu, bo
         if (-vu > r.dfeas) r.dfeas = -vu;
     }
     return r;
+}
+
+template <typename T>
+NEMPC_KKT_HD inline KktTerms kkt_variable_terms(int i, int H, int nx, int nu, bool box, const T* z, const T* grad,
+                                                const T* tiles, const T* lam, const T* zl, const T* zu, const double* lb,
+                                                const double* ub) {
+    return kkt_variable_terms_at<T>(i, H, nx, nu, box, z, grad, tiles, lam, zl, zu, lb ? lb[i] : -__builtin_huge_val(),
+                                    ub ? ub[i] : __builtin_huge_val());
 }
 
 }  // namespace nempc

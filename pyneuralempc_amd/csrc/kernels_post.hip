@@ -10,6 +10,7 @@
 #include "nempc_internal.h"
 #include "kernels_obj_impl.h"
 #include "kernels_kkt_impl.h"
+#include "bounds_bind_impl.h"
 
 namespace nempc {
 
@@ -456,7 +457,7 @@ __global__ __launch_bounds__(256) void kkt_residual_kernel(int B, int H, int nx,
                                                            const T* __restrict__ tiles, const T* __restrict__ lam,
                                                            const T* __restrict__ zl, const T* __restrict__ zu,
                                                            const double* __restrict__ lb, const double* __restrict__ ub,
-                                                           T* __restrict__ r, T* __restrict__ stat) {
+                                                           BoundBind bb, T* __restrict__ r, T* __restrict__ stat) {
     const int b = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
     if (b >= B) return;            // (the whole wave leaves: the reductions below need every lane of theirs)
     const int n = H * (nx + nu), hx = H * nx;
@@ -469,7 +470,15 @@ __global__ __launch_bounds__(256) void kkt_residual_kernel(int B, int H, int nx,
     const T* zub = zu ? zu + on : nullptr;
     double rs = 0.0, rp = 0.0, rc = 0.0, rd = 0.0;
     for (int i = lane; i < n; i += 64) {
-        const KktTerms k = kkt_variable_terms<T>(i, H, nx, nu, box != 0, zb, gradb, tb, lamb, zlb, zub, lb, ub);
+        KktTerms k;
+        if (bb.B > 0) {     // per-problem bounds bound: problem b against its own effective bounds
+            double lo = lb ? lb[i] : -std::numeric_limits<double>::infinity();
+            double hi = ub ? ub[i] : std::numeric_limits<double>::infinity();
+            bound_bind_intersect<T>(bb, b, i, hx, lo, hi);
+            k = kkt_variable_terms_at<T>(i, H, nx, nu, box != 0, zb, gradb, tb, lamb, zlb, zub, lo, hi);
+        } else {
+            k = kkt_variable_terms<T>(i, H, nx, nu, box != 0, zb, gradb, tb, lamb, zlb, zub, lb, ub);
+        }
         if (stat) stat[on + i] = (T)k.s;
         rs = fmax(rs, fabs(k.s)); rp = fmax(rp, k.pfeas); rc = fmax(rc, k.comp); rd = fmax(rd, k.dfeas);
     }
@@ -487,11 +496,11 @@ int launch_kkt_residual(Handle& h, int B, const void* Z, const void* grad, const
     if (h.cfg.dtype == NEMPC_F64)
         hipLaunchKernelGGL(kkt_residual_kernel<double>, grid, block, 0, s, B, h.cfg.H, h.cfg.nx, h.cfg.nu, h.m, h.box ? 1 : 0,
                            (const double*)Z, (const double*)grad, (const double*)g, (const double*)tiles, (const double*)lam,
-                           (const double*)zl, (const double*)zu, lb, ub, (double*)r, (double*)stat);
+                           (const double*)zl, (const double*)zu, lb, ub, h.bbind, (double*)r, (double*)stat);
     else
         hipLaunchKernelGGL(kkt_residual_kernel<float>, grid, block, 0, s, B, h.cfg.H, h.cfg.nx, h.cfg.nu, h.m, h.box ? 1 : 0,
                            (const float*)Z, (const float*)grad, (const float*)g, (const float*)tiles, (const float*)lam,
-                           (const float*)zl, (const float*)zu, lb, ub, (float*)r, (float*)stat);
+                           (const float*)zl, (const float*)zu, lb, ub, h.bbind, (float*)r, (float*)stat);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
 }

@@ -11,6 +11,7 @@
 #include <limits>
 
 #include "kernels_sens_impl.h"
+#include "bounds_bind_impl.h"
 #include "nempc_internal.h"
 
 namespace nempc {
@@ -48,6 +49,7 @@ struct SensArgs {
     const void *Z, *tiles, *blocks, *zl, *zu, *obj;
     ObjOffsets oo;
     const double *lb, *ub;
+    BoundBind bb;          // per-problem bounds (nempc_bind_bounds; bb.B == 0: none), intersected with lb / ub
     double *Kst, *Pst, *sig, *scratch;
     void *dU0, *dZ, *dlam, *gains;
     int32_t* status;
@@ -81,8 +83,9 @@ __global__ __launch_bounds__(256) void sens_kernel(SensArgs a) {
     const T* zu = a.zu ? (const T*)a.zu + (size_t)b * n : nullptr;
     bool bad = false;
     for (int i = lane; i < n; i += 64) {
-        const double lo = a.lb ? a.lb[i] : -std::numeric_limits<double>::infinity();
-        const double hi = a.ub ? a.ub[i] : std::numeric_limits<double>::infinity();
+        double lo = a.lb ? a.lb[i] : -std::numeric_limits<double>::infinity();
+        double hi = a.ub ? a.ub[i] : std::numeric_limits<double>::infinity();
+        if (a.bb.B > 0) bound_bind_intersect<T>(a.bb, b, i, H * nx, lo, hi);
         sig[i] = sens_sigma_entry((double)z[i], zl ? (double)zl[i] : 0.0, zu ? (double)zu[i] : 0.0, lo, hi, bad);
     }
     const bool undefined = __any(bad ? 1 : 0) != 0;
@@ -149,7 +152,7 @@ int launch_sensitivity(Handle& h, int B, const void* Z, const void* tiles, const
     a.stride = p.stride; a.per_problem = p.per_problem;
     a.Z = Z; a.tiles = tiles; a.blocks = blocks; a.zl = zl; a.zu = zu; a.obj = h.d_obj;
     a.oo = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
-    a.lb = lb; a.ub = ub;
+    a.lb = lb; a.ub = ub; a.bb = h.bbind;
     a.Kst = h.d_sens_ws;
     a.Pst = a.Kst + Bm * H * nu * nx;
     a.sig = a.Pst + Bm * H * nx * nx;

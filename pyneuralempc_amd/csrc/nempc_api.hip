@@ -627,6 +627,24 @@ int nempc_bind_tracking(nempc_handle hh, const void* xref, const void* uref, con
     return NEMPC_OK;
 }
 
+int nempc_bind_bounds(nempc_handle hh, const void* xlb, const void* xub, const void* ulb, const void* uub, int32_t B,
+                      int64_t ld_x, int64_t ld_u) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_bind_bounds: null handle");
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    const bool any = xlb || xub || ulb || uub;
+    if (any && B < 1) return fail(NEMPC_EINVAL, "nempc_bind_bounds: B (problems the arrays cover) must be >= 1");
+    if ((xlb || xub) && ld_x < (int64_t)h.cfg.H * h.cfg.nx)
+        return fail(NEMPC_EINVAL, "nempc_bind_bounds: ld_x must be at least H * nx");
+    if ((ulb || uub) && ld_u < (int64_t)h.cfg.H * h.cfg.nu)
+        return fail(NEMPC_EINVAL, "nempc_bind_bounds: ld_u must be at least H * nu");
+    h.bbind = BoundBind{};
+    if (any) {
+        h.bbind.xlb = xlb; h.bbind.xub = xub; h.bbind.ulb = ulb; h.bbind.uub = uub;
+        h.bbind.ld_x = ld_x; h.bbind.ld_u = ld_u; h.bbind.B = B;
+    }
+    return NEMPC_OK;
+}
+
 int nempc_set_box_rows(nempc_handle hh, int enabled, const double* lo, const double* hi) {
     if (!hh) return fail(NEMPC_EINVAL, "nempc_set_box_rows: null handle");
     Handle& h = *reinterpret_cast<Handle*>(hh);
@@ -838,6 +856,10 @@ int nempc_solve_duals(nempc_handle hh, int32_t B, const void* X0, void* Z, const
     if (h.track.on() && h.w > 1)
         return fail(NEMPC_EUNSUPPORTED, "nempc_solve: per-problem tracking data (nempc_bind_tracking) on a rolling_window > 1 handle: "
                                         "the objective table over the window state is built on the host");
+    if (h.bbind.on() && B > h.bbind.B) return fail(NEMPC_EINVAL, "nempc_solve: B exceeds the batch the bound per-problem bounds cover");
+    if (h.bbind.on() && h.w > 1)
+        return fail(NEMPC_EUNSUPPORTED, "nempc_solve: per-problem bounds (nempc_bind_bounds) on a rolling_window > 1 handle: "
+                                        "the bounds of the window state are built on the host");
     if (opts->max_iter < 1 || opts->max_linesearch < 1 || !(opts->mu_factor > 0.0 && opts->mu_factor < 1.0) ||
         !(opts->mu_init > 0.0) || !(opts->mu_min > 0.0) || opts->lq_kernel < 0 || opts->lq_kernel > 3)
         return fail(NEMPC_EINVAL, "nempc_solve: bad options");
@@ -858,6 +880,8 @@ int nempc_kkt_residual(nempc_handle hh, int32_t B, const void* Z, const void* X0
     if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_kkt_residual: B outside [0, max_batch]");
     if (B == 0) return NEMPC_OK;
     if (!Z || !X0 || !lam || !r) return fail(NEMPC_EINVAL, "nempc_kkt_residual: null argument (Z, X0, lam and r are required)");
+    if (h.bbind.on() && B > h.bbind.B)
+        return fail(NEMPC_EINVAL, "nempc_kkt_residual: B exceeds the batch the bound per-problem bounds cover");
     if (!h.d_kkt_grad || !h.d_kkt_bounds || !h.d_g_ws || !h.d_tiles_ws)
         return fail(NEMPC_ESTATE, "nempc_kkt_residual: the handle's workspaces are gone (a failed nempc_reserve)");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -885,6 +909,8 @@ int nempc_sensitivity(nempc_handle hh, int32_t B, const void* Z, const void* X0,
         return fail(NEMPC_EINVAL, "nempc_sensitivity: null argument (Z, X0, lam and status are required)");
     // (a tracking binding changes no second-order term, but the batch it covers is checked as nempc_kkt_residual's evaluation does)
     if (h.track.on() && B > h.track.B) return fail(NEMPC_EINVAL, "nempc_sensitivity: B exceeds the batch the bound tracking data cover");
+    if (h.bbind.on() && B > h.bbind.B)
+        return fail(NEMPC_EINVAL, "nempc_sensitivity: B exceeds the batch the bound per-problem bounds cover");
     if (!h.d_sens_ws || !h.d_kkt_bounds || !h.d_g_ws || !h.d_tiles_ws || !h.d_hess_ws)
         return fail(NEMPC_ESTATE, "nempc_sensitivity: the handle's workspaces are gone (a failed nempc_reserve)");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

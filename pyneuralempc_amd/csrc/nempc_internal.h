@@ -122,6 +122,15 @@ struct TrackBind {
     bool on() const { return xref || uref || cx || cu; }
 };
 
+// Per-problem, per-stage variable bounds bound by nempc_bind_bounds: base pointers (dtype of the handle; null = adds
+// nothing) and the element strides from one problem's block to the next.  B = problems covered, 0 = nothing bound.
+struct BoundBind {
+    const void *xlb = nullptr, *xub = nullptr, *ulb = nullptr, *uub = nullptr;
+    long long ld_x = 0, ld_u = 0;
+    int B = 0;
+    bool on() const { return xlb || xub || ulb || uub; }
+};
+
 // Launch geometry of the cooperative kernels: `per_cu` co-resident workgroups on each of the device's `num_cus`
 // compute units (fewer when there are fewer tiles), each owning a contiguous run of tiles_per_wg (+1 for the first
 // tiles_rem workgroups) 16-row tiles.  num_cus comes from hipDeviceProp_t::multiProcessorCount of the handle's device
@@ -150,6 +159,7 @@ struct Handle {
     const void* d_hist_x = nullptr;  // bound by nempc_bind_history
     const void* d_hist_u = nullptr;
     TrackBind track;             // bound by nempc_bind_tracking
+    BoundBind bbind;             // bound by nempc_bind_bounds
     RowGather gather() const {
         RowGather gk;
         gk.H = cfg.H; gk.nx = cfg.nx; gk.nu = cfg.nu; gk.n = n; gk.w = w; gk.rev = rev;

@@ -36,7 +36,8 @@
 // Where the code is.  This file is the host side: workspace, knobs, Solve<T> (plan_lq and the steps of an iteration) and the
 // entry points.  The device code sits in headers that only this file includes, one concern each, in this order:
 //     solver_args.h          INFO_* columns, SolverArgs, StepInfo, LQ_STAMP: the contract between driver and kernels
-//     solver_ipm_impl.h      bounds: barrier terms, dual steps, barrier value, interior start (solver_init_kernel)
+//     bounds_bind_impl.h     per-problem bounds (nempc_bind_bounds): what the binding says about one variable (shared with kernels_post / kernels_sens)
+//     solver_ipm_impl.h      bounds: barrier terms, dual steps, barrier value, interior start (solver_init_kernel, solver_init_bound_kernel)
 //     solver_merit_impl.h    convergence test, merit, trial point, acceptance, second-order correction
 //     solver_lq_scan_impl.h  LQ solve parallel in time (2/1 stages)
 //     solver_lq_impl.h       LQ solve, thread per problem: staging, Riccati sweep, post-pass
@@ -56,6 +57,7 @@
 #include "activations.h"
 #include "kernels_obj_impl.h"
 #include "solver_args.h"
+#include "bounds_bind_impl.h"
 #include "solver_ipm_impl.h"
 #include "solver_merit_impl.h"
 #include "solver_lq_scan_impl.h"
@@ -81,6 +83,9 @@ struct SolverWs {
     void *X0p = nullptr, *exp_ = nullptr;           // initial states / extras of the problems still backtracking, dense
     void *Zsoc = nullptr, *gsoc = nullptr;          // second-order-correction trial points and their defects, dense
     int* pend[2] = {nullptr, nullptr};              // ... and their indices (two lists: one read, one appended to)
+    // (cap,n) effective bounds per problem: allocated by the first solve of this workspace that has bounds bound
+    // (nempc_bind_bounds), so a handle that never binds any does not carry them
+    void *lbw = nullptr, *ubw = nullptr;
     void *lb = nullptr, *ub = nullptr, *alpha = nullptr, *phi0 = nullptr, *dir = nullptr, *hblk = nullptr, *lamn = nullptr,
          *sig = nullptr, *dz = nullptr, *Kst = nullptr, *kst = nullptr, *Pst = nullptr, *pst = nullptr,
          *tmp = nullptr;   // (info lives in infoc: it is read across iterations)
@@ -203,6 +208,7 @@ struct Solve {
     bool have_blocks = false;     // ... and so does the block buffer
     bool accept_pending = false;  // the last trial point has been evaluated, its acceptance test has not been launched
     bool published_polls = false, trace = false, compact = false;
+    bool bound_rows = false;      // per-problem bounds are bound: every kernel reads the problem's row of the working copy
     bool tracking = false;        // per-problem tracking data are bound: no launch that fuses the shared objective; f and grad from
                                   // the binding's kernel at the iterate and from the acceptance test at a trial point
     static SolverKnobs read_knobs() { static const ProcessKnobs once; return SolverKnobs{once}; }
@@ -345,6 +351,10 @@ struct Solve {
             hu[k] = std::isfinite(hi) ? (T)hi : big;
             has_bounds = has_bounds || std::isfinite(lo) || std::isfinite(hi);
         }
+        // per-problem bounds live on the device: whether a problem has a finite bound is decided there, per problem
+        // (solver_init_bound_kernel: mu = 0 for one that has none); the host plans for the barrier
+        bound_rows = h.bbind.on();
+        has_bounds = has_bounds || bound_rows;
         // (an MPC loop solves with the same bounds every step: they are uploaded when they change)
         const size_t nb = (size_t)n * sizeof(T);
         if (ws.bounds_host.size() != 2 * nb || memcmp(ws.bounds_host.data(), hl.data(), nb) != 0 ||
@@ -480,6 +490,16 @@ struct Solve {
             if ((rc = upload_roll_objective())) return rc;
             obj_dev = ws.robj;
         }
+        if (bound_rows && !ws.lbw) {     // (a rebuilt workspace starts without them; sized like its other buffers)
+            const size_t nb = (size_t)ws.cap * n * sizeof(T);
+            if ((rc = ws.alloc(&ws.lbw, nb)) || (rc = ws.alloc(&ws.ubw, nb))) return rc;
+        }
+        if (bound_rows)     // (plain models only, nempc_solve_duals: n, nx, m are the caller's)
+            hipLaunchKernelGGL(solver_init_bound_kernel<T>, dim3(B), dim3(256), 0, s, B, n, H * nx, h.bbind, (const T*)ws.lb,
+                               (const T*)ws.ub, (T*)ws.lbw, (T*)ws.ubw, (T*)ws.Zc[0], (T*)ws.muc[0], (T*)ws.nuc[0],
+                               (T*)ws.regc[0], ws.stc[0], ws.orig[0], ws.itc[0], (T*)ws.infoc[0], (T*)ws.zlc[0], (T*)ws.zuc[0],
+                               (T)o.mu_init, (T)o.reg, (const T*)Zstart, (const T*)X0start, (T*)ws.X0c[0], nx, (T*)ws.lamc[0], m);
+        else
         hipLaunchKernelGGL(solver_init_kernel<T>, dim3(gBn), dim3(256), 0, s, B, n, (T*)ws.Zc[0], (const T*)ws.lb,
                            (const T*)ws.ub, (T*)ws.muc[0], (T*)ws.nuc[0], (T*)ws.regc[0], ws.stc[0], ws.orig[0], ws.itc[0],
                            (T*)ws.infoc[0], (T*)ws.zlc[0], (T*)ws.zuc[0], (T)o.mu_init, (T)o.reg, has_bounds ? 1 : 0,
@@ -490,7 +510,8 @@ struct Solve {
         a.obj = obj_dev; a.oo = obj_offsets(H, nx, nu);
         tracking = h.track.on();
         a.trk = tracking ? h.track : TrackBind{};
-        a.lb = ws.lb; a.ub = ws.ub; a.alpha = ws.alpha; a.phi0 = ws.phi0;
+        a.lb = bound_rows ? ws.lbw : ws.lb; a.ub = bound_rows ? ws.ubw : ws.ub; a.bstride = bound_rows ? n : 0;
+        a.alpha = ws.alpha; a.phi0 = ws.phi0;
         a.dir = ws.dir; a.lsdone = ws.lsdone; a.n_active = ws.n_active; a.n_pending = ws.n_active + 1; a.n_done = ws.n_active + 2;
         a.dz = ws.dz; a.Kst = ws.Kst;
         a.dzl = ws.dzl; a.dzu = ws.dzu; a.alz = ws.alz; a.bh = ws.bh;
@@ -894,7 +915,8 @@ struct Solve {
         if (duals.any())  // (plain models only, solver_run: n, m are the caller's)
             hipLaunchKernelGGL(solver_scatter_duals_kernel<T>, dim3(B), dim3(256), 0, s, B, n, m, H * nx, (const T*)ws.Zc[cur],
                                (const T*)ws.lamc[cur], (const T*)ws.zlc[cur], (const T*)ws.zuc[cur], (const T*)ws.muc[cur],
-                               (const T*)ws.lb, (const T*)ws.ub, (const int*)ws.orig[cur], has_bounds && o.barrier == 1 ? 1 : 0,
+                               (const T*)a.lb, (const T*)a.ub, (const int*)ws.orig[cur], a.bstride,
+                               has_bounds && o.barrier == 1 ? 1 : 0,
                                (T*)duals.lam, (T*)duals.zl, (T*)duals.zu);
         NEMPC_HIP(hipGetLastError());
         NEMPC_HIP(hipStreamSynchronize(s));

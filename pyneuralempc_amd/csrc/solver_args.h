@@ -33,7 +33,11 @@ struct SolverArgs {
     // index of the problem that sits there (the buffer set's orig[]): the data are the CALLER's problem's, wherever
     // compaction or a trial list has moved it
     TrackBind trk; const int* trk_prob;
-    const void* lb; const void* ub;                                      // (n) device, dtype T, +-inf allowed
+    const void* lb; const void* ub;                                      // (n) device, dtype T, +-max for no bound
+    // ... or, with per-problem bounds bound (nempc_bind_bounds), the (B,n) working copy of every problem's effective bounds
+    // in the CALLER's order (solver_init_bound_kernel writes it): bstride = n, and the bounds of the problem in slot b are
+    // row trk_prob[b].  bstride = 0: the one shared vector
+    int bstride;
     void* mu; void* pen; void* reg; void* alpha; void* phi0; void* dir;  // (B) per problem (pen = l1 penalty)
     int lq_attempts;      // Riccati sweeps a problem may try per iteration before it sits the iteration out
     int* hpub;            // pinned host memory the acceptance kernel publishes the convergence counter to: [0] iteration
@@ -74,6 +78,16 @@ struct SolverArgs {
     double reg_raise;                                                    // ... and by which it is raised when a sweep meets a pivot that is not positive
     int max_ls;                                                          // halvings before the next LQ solve is damped
 };
+
+// the bounds of the problem in slot b of the working batch (SolverArgs::bstride; wave-uniform)
+template <typename T>
+__device__ __forceinline__ const T* solver_lb(const SolverArgs& a, int b) {
+    return a.bstride ? (const T*)a.lb + (size_t)a.trk_prob[b] * a.bstride : (const T*)a.lb;
+}
+template <typename T>
+__device__ __forceinline__ const T* solver_ub(const SolverArgs& a, int b) {
+    return a.bstride ? (const T*)a.ub + (size_t)a.trk_prob[b] * a.bstride : (const T*)a.ub;
+}
 
 template <typename T>
 struct StepInfo {   // what the Riccati kernel leaves in the info row (read from there, or handed over in registers) ...

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void solver_scatter_duals_kernel(int B, int n,
                                                                    const T* __restrict__ lamc, const T* __restrict__ zlc,
                                                                    const T* __restrict__ zuc, const T* __restrict__ muc,
                                                                    const T* __restrict__ lb, const T* __restrict__ ub,
-                                                                   const int* __restrict__ orig, int primal_barrier,
+                                                                   const int* __restrict__ orig, int bstride, int primal_barrier,
                                                                    T* __restrict__ lam_out, T* __restrict__ zl_out,
                                                                    T* __restrict__ zu_out) {
     const int slot = blockIdx.x;
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void solver_scatter_duals_kernel(int B, int n,
     const T mu = muc[slot];
     for (int i = threadIdx.x; i < n; i += 256) {
         const size_t k = (size_t)slot * n + i;
-        const T lo = lb[i], hi = ub[i];
+        const T lo = lb[(size_t)o * bstride + i], hi = ub[(size_t)o * bstride + i];
         const bool flo = lo > -std::numeric_limits<T>::max(), fhi = hi < std::numeric_limits<T>::max();
         T vl = T(0), vu = T(0);
         if (primal_barrier) {

@@ -23,7 +23,7 @@ __global__ __launch_bounds__(256) void solver_barrier_kernel(SolverArgs a) {
     T ga = T(0), ha = T(0);
     const T mu = ((const T*)a.mu)[b];
     if (mu > T(0) && a.status[b] < 0) {
-        const T z = ((const T*)a.Z)[idx], lo = ((const T*)a.lb)[i], hi = ((const T*)a.ub)[i];
+        const T z = ((const T*)a.Z)[idx], lo = solver_lb<T>(a, b)[i], hi = solver_ub<T>(a, b)[i];
         if (lo > -std::numeric_limits<T>::max()) {
             const T d = z - lo;
             ga -= mu / d;
@@ -49,8 +49,8 @@ __device__ __forceinline__ void solver_dual_body(const SolverArgs& a, int b, int
     if (!a.primal_dual) return;
     const T tau = T(0.995);
     T amax = T(1);
-    const T* lbv = lbp ? lbp : (const T*)a.lb;
-    const T* ubv = ubp ? ubp : (const T*)a.ub;
+    const T* lbv = lbp ? lbp : solver_lb<T>(a, b);
+    const T* ubv = ubp ? ubp : solver_ub<T>(a, b);
     const T* zlv = zlp ? zlp : (const T*)a.zl + (size_t)b * a.n;
     const T* zuv = zup ? zup : (const T*)a.zu + (size_t)b * a.n;
     if (mu > T(0) && status < 0)
@@ -101,7 +101,7 @@ __device__ __forceinline__ void solver_barrier_terms(const SolverArgs& a, int b,
     const int status = a.status[b];
     if (mu > T(0) && status < 0) {
         const size_t idx = (size_t)b * a.n + i;
-        const T z = ((const T*)a.Z)[idx], lo = ((const T*)a.lb)[i], hi = ((const T*)a.ub)[i];
+        const T z = ((const T*)a.Z)[idx], lo = solver_lb<T>(a, b)[i], hi = solver_ub<T>(a, b)[i];
         const bool lof = lo > -std::numeric_limits<T>::max(), hif = hi < std::numeric_limits<T>::max();
         barrier_terms_of<T>(a.primal_dual, mu, status, z, lo, hi, a.primal_dual && lof ? ((const T*)a.zl)[idx] : T(0),
                             a.primal_dual && hif ? ((const T*)a.zu)[idx] : T(0), ga, ha);
@@ -170,6 +170,68 @@ __global__ __launch_bounds__(256) void solver_init_kernel(int B, int n, T* __res
     if (zl) {   // bound multipliers on the central path of the first barrier parameter
         zl[i] = flo ? mu0 / (z - lo) : T(0);
         zu[i] = fhi ? mu0 / (hi - z) : T(0);
+    }
+}
+
+// The same start with per-problem bounds bound (nempc_bind_bounds): one workgroup per problem.  A first pass over the
+// problem's n variables forms the effective bounds -- the shared vector (host lb / ub and box rows, already intersected)
+// intersected with the problem's rows of the binding, +-inf and magnitudes at or above the dtype's max as +-max -- and
+// decides two things for the whole problem: whether any bound is finite (none: mu = 0, the problem runs as an unbounded
+// one and never walks the barrier schedule) and whether some variable has lo >= hi or a NaN bound.  Such a problem is
+// finished from the start: status 1, Z as handed in, zero multipliers, and NO bounds in the working copy, so that no
+// kernel forms a barrier term for it.  The second pass writes the working copy (lbw / ubw, (B,n), the caller's order: this
+// launch runs before any compaction) and what solver_init_kernel writes.
+template <typename T>
+__global__ __launch_bounds__(256) void solver_init_bound_kernel(int B, int n, int hx, BoundBind bb, const T* __restrict__ lb,
+                                                                const T* __restrict__ ub, T* __restrict__ lbw,
+                                                                T* __restrict__ ubw, T* __restrict__ Z, T* mu, T* nu, T* reg,
+                                                                int* status, int* orig, int* iters_done, T* info, T* zl, T* zu,
+                                                                T mu0, T reg0, const T* __restrict__ Zin,
+                                                                const T* __restrict__ X0in, T* __restrict__ X0c, int nx,
+                                                                T* __restrict__ lam0, int m) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (b >= B) return;
+    const T big = std::numeric_limits<T>::max();
+    auto effective = [&](int i, T& lo, T& hi, bool& nan) {
+        T bl, bu;
+        bound_bind_pair<T>(bb, b, i, hx, bl, bu);
+        nan = bl != bl || bu != bu;
+        lo = fmax(lb[i], fmax(bl, -big));       // (-inf -> -max; a NaN operand is dropped by fmax: `nan` has it)
+        hi = fmin(ub[i], fmin(bu, big));
+    };
+    int any = 0, bad = 0;
+    for (int i = tid; i < n; i += 256) {
+        T lo, hi; bool nan;
+        effective(i, lo, hi, nan);
+        any |= (lo > -big || hi < big) ? 1 : 0;
+        bad |= (nan || !(lo < hi)) ? 1 : 0;
+    }
+    bad = __syncthreads_or(bad);
+    any = __syncthreads_or(any);
+    for (int i = tid; i < nx; i += 256) X0c[(size_t)b * nx + i] = X0in[(size_t)b * nx + i];
+    for (int i = tid; i < m; i += 256) lam0[(size_t)b * m + i] = T(0);
+    if (tid == 0) {
+        mu[b] = any && !bad ? mu0 : T(0); nu[b] = T(1); reg[b] = reg0; status[b] = bad ? 1 : -1;
+        orig[b] = b; iters_done[b] = 0;
+        for (int k = 0; k < INFO_N; ++k) info[(size_t)b * INFO_N + k] = big;   // "no previous step"
+        info[(size_t)b * INFO_N + INFO_LSK] = T(0);
+        info[(size_t)b * INFO_N + INFO_LSR] = T(0);
+        info[(size_t)b * INFO_N + INFO_PHN] = T(0);
+        info[(size_t)b * INFO_N + INFO_PHUP] = T(0);
+    }
+    for (int i = tid; i < n; i += 256) {
+        const size_t k = (size_t)b * n + i;
+        T lo, hi; bool nan;
+        effective(i, lo, hi, nan);
+        if (bad) { lo = -big; hi = big; }
+        lbw[k] = lo; ubw[k] = hi;
+        const bool flo = lo > -big, fhi = hi < big;
+        const T z = bad ? Zin[k] : start_inside(Zin[k], lo, hi, mu0, 1);
+        Z[k] = z;
+        if (zl) {
+            zl[k] = flo ? mu0 / (z - lo) : T(0);
+            zu[k] = fhi ? mu0 / (hi - z) : T(0);
+        }
     }
 }
 

@@ -117,8 +117,8 @@ __global__ __launch_bounds__(256) void solver_lq_kernel(SolverArgs a) {
                 const int st_q = a.status[bq];
                 const T vz = in_n ? ((const T*)a.Z)[(size_t)bq * n + e] : T(0);
                 const T vgr = in_n ? ((const T*)a.grad)[(size_t)bq * n + e] : T(0);
-                const T vlo = in_n ? ((const T*)a.lb)[e] : -std::numeric_limits<T>::max();
-                const T vhi = in_n ? ((const T*)a.ub)[e] : std::numeric_limits<T>::max();
+                const T vlo = in_n ? solver_lb<T>(a, bq)[e] : -std::numeric_limits<T>::max();
+                const T vhi = in_n ? solver_ub<T>(a, bq)[e] : std::numeric_limits<T>::max();
                 const T vzl = in_n && pdl ? ((const T*)a.zl)[(size_t)bq * n + e] : T(0);
                 const T vzu = in_n && pdl ? ((const T*)a.zu)[(size_t)bq * n + e] : T(0);
                 const T vgc = e < H * nx ? ((const T*)a.g)[(size_t)bq * a.m + e] : T(0);
@@ -141,7 +141,8 @@ __global__ __launch_bounds__(256) void solver_lq_kernel(SolverArgs a) {
                     blkp[Lgr + e] = vgr + ga;
                     blkp[Lbh + e] = ha;
                     blkp[Lzl + e] = vzl; blkp[Lzu + e] = vzu;
-                    lds_lb[e] = vlo; lds_ub[e] = vhi;          // (every problem's stagers write the same values)
+                    // (every problem's stagers write the same values; per-problem bounds are read where they live)
+                    if (!a.bstride) { lds_lb[e] = vlo; lds_ub[e] = vhi; }
                 }
             }
             __syncthreads();
@@ -161,7 +162,8 @@ __global__ __launch_bounds__(256) void solver_lq_kernel(SolverArgs a) {
         }
         stage_in((const T*)a.g, H * nx, a.m, Lgc);
         if (a.primal_dual) { stage_in((const T*)a.zl, n, n, Lzl); stage_in((const T*)a.zu, n, n, Lzu); }
-        for (int e = lane; e < n; e += nthr) { lds_lb[e] = ((const T*)a.lb)[e]; lds_ub[e] = ((const T*)a.ub)[e]; }
+        if (!a.bstride)
+            for (int e = lane; e < n; e += nthr) { lds_lb[e] = ((const T*)a.lb)[e]; lds_ub[e] = ((const T*)a.ub)[e]; }
         if (a.lam_t) stage_in((const T*)a.lam, H * nx, a.m, Llc);
         stage_in((const T*)a.tiles, H * nx * nin, H * nx * nin, Ltl);
         stage_in((const T*)a.hblk, H * nin * nin, H * nin * nin, LW);
@@ -231,8 +233,8 @@ __global__ __launch_bounds__(256) void solver_lq_kernel(SolverArgs a) {
     }
 #define QS(e) (REGTAB ? Qr[REGTAB ? (e) : 0] : Qs[e])
 #define RS(e) (REGTAB ? Rr[REGTAB ? (e) : 0] : Rs[e])
-    const T* lb = (const T*)a.lb;
-    const T* ub = (const T*)a.ub;
+    const T* lb = solver_lb<T>(a, b);
+    const T* ub = solver_ub<T>(a, b);
     const T* bh = LDS ? blk + Lbh : (const T*)a.bh + (size_t)b * n;   // barrier diagonal (solver_barrier_kernel)
     T reg = ((const T*)a.reg)[b];
     T* Kst = LDS ? blk + LK : (T*)a.Kst + (size_t)b * H * nu * nx;
@@ -621,11 +623,12 @@ __global__ __launch_bounds__(256) void solver_lq_kernel(SolverArgs a) {
         {
             // norms of the steps just computed: wave w takes problems w, w + #waves, ...
             const int wv = lane >> 6, ln = lane & 63, nwv = nthr >> 6;
-            const T* lb = lds_lb;
-            const T* ub = lds_ub;
             const T tau = T(0.995);
             for (int pp = wv; pp < np; pp += nwv) {
                 const int bp = b0 + pp;
+                // the workgroup's LDS copy of the shared bounds, or this problem's own row in global memory
+                const T* lb = a.bstride ? solver_lb<T>(a, bp) : lds_lb;
+                const T* ub = a.bstride ? solver_ub<T>(a, bp) : lds_ub;
                 const T* blk = lds + (size_t)pp * a.lds_stride;
                 // the problem's scalars for the step part below: all requested now, used after the norms
                 const T* infg = (const T*)a.info + (size_t)bp * INFO_N;

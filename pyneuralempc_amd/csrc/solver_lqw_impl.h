@@ -88,8 +88,8 @@ __global__ __launch_bounds__(256) void solver_lqw_kernel(SolverArgs a) {
             const T* Qs = (const T*)a.obj + a.oo.Qs;
             const T* QTs = (const T*)a.obj + a.oo.QTs;
             const T* Rs = (const T*)a.obj + a.oo.Rs;
-            const T* lb = (const T*)a.lb;
-            const T* ub = (const T*)a.ub;
+            const T* lb = solver_lb<T>(a, b);
+            const T* ub = solver_ub<T>(a, b);
             const T* bh = blk + Lbh;                                             // barrier diagonal (solver_barrier_kernel)
             T reg = ((const T*)a.reg)[b];
             T* Kst = blk + LK;

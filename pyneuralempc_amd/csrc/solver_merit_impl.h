@@ -24,8 +24,8 @@ __device__ __forceinline__ void solver_merit0_body(const SolverArgs& a, int b, i
                                                    const T* __restrict__ zp, const T* __restrict__ gp, const StepInfo<T>& si,
                                                    int& lsd, T& al, const T* lbp = nullptr, const T* ubp = nullptr) {
     T* mu = (T*)a.mu; T* nu = (T*)a.pen; T* alpha = (T*)a.alpha; T* phi0 = (T*)a.phi0; T* dir = (T*)a.dir;
-    const T* lb = lbp ? lbp : (const T*)a.lb;
-    const T* ub = ubp ? ubp : (const T*)a.ub;
+    const T* lb = lbp ? lbp : solver_lb<T>(a, b);
+    const T* ub = ubp ? ubp : solver_ub<T>(a, b);
     const int H = a.H, nx = a.nx;
     lsd = 1;
     al = T(0);
@@ -124,8 +124,8 @@ __device__ __forceinline__ void solver_merit_body(const SolverArgs& a, const T* 
     if (b >= a.B) return;
     T* mu = (T*)a.mu; T* nu = (T*)a.pen; T* reg = (T*)a.reg; T* alpha = (T*)a.alpha; T* phi0 = (T*)a.phi0; T* dir = (T*)a.dir;
     const T* info = (const T*)a.info + (size_t)b * INFO_N;
-    const T* lb = (const T*)a.lb;
-    const T* ub = (const T*)a.ub;
+    const T* lb = solver_lb<T>(a, b);
+    const T* ub = solver_ub<T>(a, b);
     const int H = a.H, nx = a.nx;
     // objective value of the trial point, when no launch has left it in `ft` (shapes without the fused evaluation, and the
     // compiled shape whose trial launch computes the Lagrangian blocks instead): the wave has the point in hand, and a

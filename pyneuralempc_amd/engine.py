@@ -66,6 +66,7 @@ class CallbackEngine:
         self.n_extra = int(n_extra)   # tvp_dim + p_dim of the reference's Model: network inputs that are not variables
         self._extra = None
         self._tracking = None
+        self._bounds = None
         self.integrator = integrator if isinstance(integrator, int) else _lib.INTEGRATOR_IDS[integrator]
         self.DT = float(DT)
         self.kernel = kernel
@@ -131,6 +132,8 @@ class CallbackEngine:
             self.bind_history(*self._history)
         if self._tracking is not None:
             self.bind_tracking(**self._tracking[0], offset=self._tracking[1])
+        if self._bounds is not None:
+            self.bind_bounds(**self._bounds[0], offset=self._bounds[1])
         self._refresh_dims()
         self._buffers = {}
 
@@ -241,9 +244,30 @@ class CallbackEngine:
         (B,L,nu); L >= offset + H, and rows offset .. offset+H-1 of every problem are the horizon's (a window sliding over a
         longer reference needs no copy: bind the same tensors at the next offset).  The tensors are kept alive here, not
         copied.  bind_tracking() with nothing removes the binding."""
+        self._tracking = self._bind_rows(self.lib.nempc_bind_tracking, "tracking", ("xref", "uref", "cx", "cu"), (("xref", xref), ("cx", cx)),
+                                         (("uref", uref), ("cu", cu)), offset)
+
+    def bind_bounds(self, xlb=None, xub=None, ulb=None, uub=None, offset=0):
+        """Bind per-problem, per-stage lower / upper bounds on states and controls for the following solve / kkt_residual /
+        sensitivity calls (nempc_bind_bounds): problem b is solved inside the intersection of the call's shared lb / ub, the box
+        rows and its own rows xlb[b], xub[b] (on x_1 .. x_H), ulb[b], uub[b] (on u_0 .. u_{H-1}); an array left None adds
+        nothing, +-inf means no bound there.  xlb, xub: device tensors (B,L,nx); ulb, uub: (B,L,nu); L >= offset + H, and rows
+        offset .. offset+H-1 of every problem are the horizon's (a window sliding over a longer schedule needs no copy: bind
+        the same tensors at the next offset).  The tensors are kept alive here, not copied.  bind_bounds() with nothing
+        removes the binding.  eval / hess / rollout do not read it."""
+        self._bounds = self._bind_rows(self.lib.nempc_bind_bounds, "bounds", ("xlb", "xub", "ulb", "uub"), (("xlb", xlb), ("xub", xub)),
+                                       (("ulb", ulb), ("uub", uub)), offset)
+
+    def _bind_rows(self, bind, what, order, xpair, upair, offset):
+        """bind_tracking / bind_bounds: check the (B,L,d) device tensors (xpair: the two of width nx, upair: of width nu),
+        settle one leading dimension per pair and hand the row-`offset` pointers to the C function `bind` in its argument
+        `order`.  -> what to keep alive and rebind with, or None when nothing was given."""
         H, given = self.H, {}
         offset = int(offset)
-        for name, t, d in (("xref", xref, self.nx), ("uref", uref, self.nu), ("cx", cx, self.nx), ("cu", cu, self.nu)):
+        dims = {k: self.nx for k, _ in xpair}
+        dims.update({k: self.nu for k, _ in upair})
+        for name, t in xpair + upair:
+            d = dims[name]
             if t is None:
                 continue
             if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != self.dtype or t.dim() != 3
@@ -254,13 +278,13 @@ class CallbackEngine:
                 t = t.contiguous()
             given[name] = t
         if not given:
-            self._tracking = None
-            _lib.check(self.lib.nempc_bind_tracking(self._handle, None, None, None, None, 0, 0, 0))
-            return
+            _lib.check(bind(self._handle, None, None, None, None, 0, 0, 0))
+            return None
         if len({int(t.shape[0]) for t in given.values()}) != 1:
-            raise ValueError("the bound tracking tensors must cover the same batch")
+            raise ValueError(f"the bound {what} tensors must cover the same batch")
         ld = {}
-        for key, names, d in (("x", ("xref", "cx"), self.nx), ("u", ("uref", "cu"), self.nu)):
+        for key, pair, d in (("x", xpair, self.nx), ("u", upair, self.nu)):
+            names = tuple(k for k, _ in pair)
             ts = [given[k] for k in names if k in given]
             lds = {int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]) * d for t in ts}
             if len(lds) > 1:     # one leading dimension per pair in the C interface
@@ -271,12 +295,11 @@ class CallbackEngine:
                 if len(lds) > 1:
                     raise ValueError(f"{names[0]} and {names[1]} must have the same length L")
             ld[key] = lds.pop() if lds else 0
-        self._tracking = (given, offset)
         esz = 8 if self.dtype == torch.float64 else 4
-        ptr = lambda k, d: (ctypes.c_void_p(given[k].data_ptr() + offset * d * esz) if k in given else None)
+        ptr = lambda k: (ctypes.c_void_p(given[k].data_ptr() + offset * dims[k] * esz) if k in given else None)
         B = int(next(iter(given.values())).shape[0])
-        _lib.check(self.lib.nempc_bind_tracking(self._handle, ptr("xref", self.nx), ptr("uref", self.nu), ptr("cx", self.nx),
-                                                ptr("cu", self.nu), B, ld["x"], ld["u"]))
+        _lib.check(bind(self._handle, *[ptr(k) for k in order], B, ld["x"], ld["u"]))
+        return (given, offset)
 
     def _check_extra(self, B):
         if self.n_extra and (self._extra is None or self._extra.shape[0] < B):
