@@ -386,6 +386,39 @@ int nempc_sensitivity(nempc_handle h, int32_t B, const void* Z, const void* X0, 
                       const void* zu, const double* lb, const double* ub, void* dU0, void* dZ, void* dlam, void* gains,
                       int32_t* status, void* stream);
 
+/* KKT solves with caller-supplied right-hand sides (reference counterpart: none).  At a primal-dual point the matrix
+ * K = [[W + Sigma, J'], [J, 0]] of nempc_sensitivity is symmetric, so one solve
+ *     K [v ; w] = [rz ; rg]
+ * is the vector-Jacobian product of the solution map (rz = the cotangent of z*, rg = 0: the cotangent of a parameter theta is
+ * -[v ; w]' d/dtheta [grad L ; g]) as well as the forward sensitivity with respect to any parameter
+ * (right-hand side -d/dtheta [grad L ; g]).  Per right-hand side, on top of the matrices P_t, K_t, Quu_t = L D L', Qux_t of
+ * nempc_sensitivity's backward sweep and with w_t = P_t v_x[t] - p_t, p_{H-1} = r^x_{H-1}:
+ *     backward  q_t = P_t r^g_t + p_t,  k_t = Quu_t^-1 (r^u_t + B_t' q_t),  p_{t-1} = r^x_{t-1} + A_t' q_t - Qux_t' k_t
+ *     forward   v_u[t] = K_t v_x[t-1] + k_t,  v_x[t] = A_t v_x[t-1] + B_t v_u[t] - r^g_t  (v_x[-1] = 0)
+ *     pull-back gx0 = -(W_ux,0' v_u[0] + A_0' w_0) = -[v ; w]' d/dx0 [grad L ; g]
+ * nempc_sensitivity is the special case rz = e_i, rg = 0: gx0 is then row i of its dZ.
+ *   Z, X0, lam, zl, zu, lb, ub: exactly as nempc_sensitivity (bound handling, box rows, nempc_bind_bounds, the evaluation of
+ *   tiles and blocks, argument checks and codes included: rolling_window > 1 NEMPC_EUNSUPPORTED; a batch larger than a
+ *   binding covers NEMPC_EINVAL).
+ *   nrhs: right-hand sides per problem, 1 <= nrhs <= 64 (else NEMPC_EINVAL; callers chunk larger sets).
+ *   rz (B,nrhs,n) device, required: each right-hand side one contiguous row in z order (states, then controls);
+ *   rg (B,nrhs,H*nx) device, defect order, NULL = zeros.
+ *   Outputs: device, dtype of the handle; each may be NULL, at least one must be given:
+ *     v   (B,nrhs,n)      in z order
+ *     w   (B,nrhs,H*nx)   in defect order
+ *     gx0 (B,nrhs,nx)
+ *   status (B) device int32, required: the codes of nempc_sensitivity (0 / 1 / 2, 2 first).  On status != 0 every requested
+ *   output of that problem is NaN.  NO Levenberg term is ever added.
+ * One evaluation and one Lagrangian-block launch as nempc_sensitivity, then one kernel (one wave per problem, double
+ * arithmetic whatever the handle's dtype).  The working sets live in LDS when they fit; when they do not, the call keeps
+ * a per-problem region of device memory on the handle, allocated by the first call that needs it and grown when nrhs or
+ * max_batch grow: such a call allocates and SYNCHRONISES THE DEVICE, every other call is asynchronous on `stream` apart
+ * from the bound upload.  A handle that never calls this function allocates nothing for it.  The call uses
+ * nempc_sensitivity's workspaces while it runs: issue both on one stream. */
+int nempc_kkt_solve(nempc_handle h, int32_t B, const void* Z, const void* X0, const void* lam, const void* zl,
+                    const void* zu, const double* lb, const double* ub, int32_t nrhs, const void* rz, const void* rg, void* v,
+                    void* w, void* gx0, int32_t* status, void* stream);
+
 /* Forward simulation of the handle's model (no reference counterpart: the reference never integrates its model over the
  * horizon on its own -- its cold start tiles x0, optimizer/ipopt.py:149, and its examples step the plant outside the library).
  *   Z (B,n) device, in/out: the controls are read from Z[:, H*nx:] and are not written; the states Z[:, :H*nx] are

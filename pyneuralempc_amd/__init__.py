@@ -13,4 +13,5 @@ from . import optimizer
 from . import constraints
 from . import controller
 from . import parallel
+from . import autograd
 from .engine import CallbackEngine

@@ -44,7 +44,7 @@ def split_activation(spec):
 EXPORTS = ["nempc_create", "nempc_destroy", "nempc_reserve", "nempc_set_weights", "nempc_set_objective", "nempc_set_terminal_weight", "nempc_set_box_rows", "nempc_bind_extra", "nempc_bind_history",
            "nempc_bind_tracking", "nempc_bind_bounds",
            "nempc_dims", "nempc_constraint_bounds", "nempc_jac_structure", "nempc_hess_structure", "nempc_eval",
-           "nempc_hess", "nempc_hess_gn", "nempc_solve", "nempc_solve_duals", "nempc_kkt_residual", "nempc_sensitivity", "nempc_rollout", "nempc_last_rollout_kernel", "nempc_sync", "nempc_kernel_variant", "nempc_last_row_kernel", "nempc_last_hess_kernel", "nempc_last_error", "nempc_abi_version",
+           "nempc_hess", "nempc_hess_gn", "nempc_solve", "nempc_solve_duals", "nempc_kkt_residual", "nempc_sensitivity", "nempc_kkt_solve", "nempc_rollout", "nempc_last_rollout_kernel", "nempc_sync", "nempc_kernel_variant", "nempc_last_row_kernel", "nempc_last_hess_kernel", "nempc_last_error", "nempc_abi_version",
            "nempc_plan_grid", "nempc_num_cus",
            "nempc_comm_unique_id", "nempc_comm_init", "nempc_allgather_u0", "nempc_comm_size", "nempc_comm_destroy"]
 
@@ -109,6 +109,7 @@ def load():
     lib.nempc_solve_duals.argtypes = [vp, i32, vp, vp, dp, dp, ctypes.POINTER(NempcSolverOpts), vp, ip, vp, vp, vp, vp]
     lib.nempc_kkt_residual.argtypes = [vp, i32, vp, vp, vp, vp, vp, dp, dp, vp, vp, vp]
     lib.nempc_sensitivity.argtypes = [vp, i32, vp, vp, vp, vp, vp, dp, dp, vp, vp, vp, vp, vp, vp]
+    lib.nempc_kkt_solve.argtypes = [vp, i32, vp, vp, vp, vp, vp, dp, dp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.nempc_rollout.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.nempc_last_rollout_kernel.argtypes = [vp]
     lib.nempc_sync.argtypes = [vp, vp]

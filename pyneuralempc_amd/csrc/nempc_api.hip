@@ -297,6 +297,7 @@ void destroy_impl(Handle* h) {
     dev_free(h->d_kkt_grad);
     { void* q = h->d_kkt_bounds; dev_free(q); h->d_kkt_bounds = nullptr; }
     { void* q = h->d_sens_ws; dev_free(q); h->d_sens_ws = nullptr; }
+    kktsolve_free(*h);
     delete h;
 }
 
@@ -924,6 +925,36 @@ int nempc_sensitivity(nempc_handle hh, int32_t B, const void* Z, const void* X0,
     DeviceGuard dg(h.cfg.device);
     if (!dg.ok) return fail(NEMPC_EHIP, "nempc_sensitivity: hipSetDevice failed");
     return launch_sensitivity(h, B, Z, h.d_tiles_ws, h.d_hess_ws, zl, zu, dlb, dub, dU0, dZ, dlam, gains, status, s);
+}
+
+int nempc_kkt_solve(nempc_handle hh, int32_t B, const void* Z, const void* X0, const void* lam, const void* zl,
+                    const void* zu, const double* lb, const double* ub, int32_t nrhs, const void* rz, const void* rg, void* v,
+                    void* w, void* gx0, int32_t* status, void* stream) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_kkt_solve: null handle");
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    if (h.w > 1)
+        return fail(NEMPC_EUNSUPPORTED, "nempc_kkt_solve: rolling_window > 1 handles are not supported (the sweep is built "
+                                        "for the stages of a plain model)");
+    if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_kkt_solve: B outside [0, max_batch]");
+    if (nrhs < 1 || nrhs > 64) return fail(NEMPC_EINVAL, "nempc_kkt_solve: nrhs outside [1, 64]");
+    if (!v && !w && !gx0) return fail(NEMPC_EINVAL, "nempc_kkt_solve: no output asked for (v, w, gx0 all null)");
+    if (B == 0) return NEMPC_OK;
+    if (!Z || !X0 || !lam || !rz || !status)
+        return fail(NEMPC_EINVAL, "nempc_kkt_solve: null argument (Z, X0, lam, rz and status are required)");
+    if (h.track.on() && B > h.track.B) return fail(NEMPC_EINVAL, "nempc_kkt_solve: B exceeds the batch the bound tracking data cover");
+    if (h.bbind.on() && B > h.bbind.B)
+        return fail(NEMPC_EINVAL, "nempc_kkt_solve: B exceeds the batch the bound per-problem bounds cover");
+    if (!h.d_sens_ws || !h.d_kkt_bounds || !h.d_g_ws || !h.d_tiles_ws || !h.d_hess_ws)
+        return fail(NEMPC_ESTATE, "nempc_kkt_solve: the handle's workspaces are gone (a failed nempc_reserve)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const double *dlb = nullptr, *dub = nullptr;
+    if (int rc = cached_bounds(h, lb, ub, "nempc_kkt_solve", s, dlb, dub)) return rc;
+    // tiles and Lagrangian blocks exactly as nempc_sensitivity gets them
+    if (int rc = nempc_eval(hh, B, Z, X0, nullptr, nullptr, h.d_g_ws, nullptr, h.d_tiles_ws, nullptr, stream)) return rc;
+    if (int rc = nempc_hess(hh, B, Z, X0, lam, lam, nullptr, nullptr, h.d_hess_ws, stream)) return rc;
+    DeviceGuard dg(h.cfg.device);
+    if (!dg.ok) return fail(NEMPC_EHIP, "nempc_kkt_solve: hipSetDevice failed");
+    return launch_kkt_solve(h, B, Z, h.d_tiles_ws, h.d_hess_ws, zl, zu, dlb, dub, nrhs, rz, rg, v, w, gx0, status, s);
 }
 
 int nempc_rollout(nempc_handle hh, int32_t B, const void* X0, void* Z, void* f, void* stream) {

@@ -214,6 +214,8 @@ struct Handle {
     double* d_kkt_bounds = nullptr;          // (2,n) doubles: lb | ub of the last nempc_kkt_residual, +-inf kept
     std::vector<double> kkt_bounds_host;     // ... as last uploaded (empty: nothing uploaded yet)
     double* d_sens_ws = nullptr;             // nempc_sensitivity (plain models): gains | value matrices | Sigma | scratch (sens_ws_doubles)
+    double* d_kktsolve_ws = nullptr;         // nempc_kkt_solve: per-problem global working sets, when its plan needs them
+    size_t kktsolve_ws_doubles = 0;          //   (allocated and grown by the call itself, kernels_kktsolve.hip)
     void* d_rk4_stage = nullptr; // RK4 Hessian pipeline (allocated on first use): (Bmax*H, 4, nin + 2*nx*nin) stage records,
     void* d_rk4_nu = nullptr;    //   (Bmax*H, 4, nx) stage multipliers,
     void* d_rk4_ht = nullptr;    //   (Bmax*H, 4, nin, nin) contracted stage Hessians
@@ -344,9 +346,19 @@ int launch_sensitivity(Handle& h, int B, const void* Z, const void* tiles, const
                        const double* lb, const double* ub, void* dU0, void* dZ, void* dlam, void* gains, int32_t* status,
                        hipStream_t s);
 
+// ---- kernels_kktsolve.hip : KKT solves with caller-supplied right-hand sides (nempc_kkt_solve)
+size_t kktsolve_ws_doubles(const Handle& h, size_t Bmax, int nrhs);   // elements of Handle::d_kktsolve_ws (0: the plan is on-chip)
+// as launch_sensitivity, with rz (B,nrhs,n), rg (B,nrhs,H nx) or null and the outputs of nempc_kkt_solve (each may be null).
+// Uses Handle::d_sens_ws for the gains, value matrices and Sigma; grows Handle::d_kktsolve_ws (a device synchronisation)
+int launch_kkt_solve(Handle& h, int B, const void* Z, const void* tiles, const void* blocks, const void* zl, const void* zu,
+                     const double* lb, const double* ub, int nrhs, const void* rz, const void* rg, void* v, void* w, void* gx0,
+                     int32_t* status, hipStream_t s);
+void kktsolve_free(Handle& h);
+
 // ---- solver.hip : batched Gauss-Newton SQP (host driver; its kernels are in solver_args.h and the solver_*_impl.h headers,
 // which only solver.hip includes)
-// LDS bytes of a workgroup that plan_lq (solver.hip) and sens_plan (kernels_sens.hip) fill with per-problem working sets
+// LDS bytes of a workgroup that plan_lq (solver.hip), sens_plan (kernels_sens.hip) and kktsolve_plan (kernels_kktsolve.hip)
+// fill with per-problem working sets
 constexpr size_t kLqLdsBudget = (size_t)150 * 1024;
 // the caller's variable bounds (n host doubles each, null = unbounded) intersected with the handle's box rows on the state
 // variables -> lo, hi (n, +-INFINITY for a missing bound).  lo > hi is NEMPC_EINVAL, lo == hi too when `need_interior`;

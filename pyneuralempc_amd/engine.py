@@ -209,6 +209,15 @@ class CallbackEngine:
         self._objective = dict(Q=Q, R=R, xref=xref, uref=uref, cx=cx, cu=cu, QT=QT)
         self._refresh_dims()
 
+    def objective_weights(self):
+        """(Q (nx,nx), R (nu,nu), QT (nx,nx)) of the handle's objective as float64 arrays: what set_objective was given,
+        the library's defaults (I, 0.1 I) where it was given nothing, QT = Q without a terminal weight."""
+        ob = self._objective or {}
+        Q = np.eye(self.nx) if ob.get("Q") is None else np.array(np.broadcast_to(np.asarray(ob["Q"], dtype=np.float64), (self.nx, self.nx)))
+        R = 0.1 * np.eye(self.nu) if ob.get("R") is None else np.array(np.broadcast_to(np.asarray(ob["R"], dtype=np.float64), (self.nu, self.nu)))
+        QT = Q.copy() if ob.get("QT") is None else np.asarray(ob["QT"], dtype=np.float64).reshape(self.nx, self.nx).copy()
+        return Q, R, QT
+
     def bind_extra(self, E):
         """Bind the extra network inputs (B,H,n_extra) = [tvp_t ; p] per step for the following evaluations
         (reference: KerasTFModel._gather_input, model/tensorflow.py:39-47).  The tensor is kept alive here."""
@@ -672,6 +681,76 @@ class CallbackEngine:
                                                   opt(res.get("du0")), opt(res.get("dz")), opt(res.get("dlam")),
                                                   opt(res.get("gains")), ctypes.c_void_p(res["status"].data_ptr()),
                                                   self._stream()))
+        return res
+
+    def kkt_solve(self, Z, X0, lam, zl=None, zu=None, lb=None, ub=None, rz=None, rg=None, want=("v",)):
+        """Solves K [v ; w] = [rz ; rg] with the symmetric KKT matrix K = [[W + Sigma, J'], [J, 0]] of B primal-dual points
+        (nempc_kkt_solve; any points, a solver's or not).  Inputs as `sensitivity`.  rz (B,n) -- one right-hand side per
+        problem, the outputs then lose that axis -- or (B,k,n) with any k (the library takes 64 per call; larger sets go in
+        chunks), in z order; rg (B,H*nx) / (B,k,H*nx) in defect order or None (zeros).  want: any of "v" (B,k,n), "w"
+        (B,k,H*nx), "gx0" (B,k,nx) = -[v ; w]' d/dx0 [grad L ; g].  With rz the cotangent of z* (rg None), gx0 is the cotangent
+        of x0 and v carries those of the tracking data (pyneuralempc_amd.autograd); with the right-hand side
+        -d/dtheta [grad L ; g], v and w are dz*/dtheta and dlam/dtheta.  Returns a dict of new device tensors with those keys
+        plus "status" (B,) int32 as `sensitivity`'s; outputs of a problem with status != 0 are NaN.  Asynchronous on the
+        current torch stream, except that a call whose working sets do not fit on chip allocates (and synchronises the
+        device) when k or the batch grow."""
+        names = ("v", "w", "gx0")
+        want = tuple(want)
+        if not want or any(k not in names for k in want):
+            raise ValueError(f"want must name at least one of {names}")
+        if rz is None:
+            raise ValueError("rz is required")
+        B = int(Z.shape[0])
+        hx = self.H * self.nx
+        self._check_in(Z, (B, self.n), "Z")
+        self._check_in(X0, (B, self.nx), "X0")
+        self._check_in(lam, (B, self.m), "lam")
+        for name, t in (("zl", zl), ("zu", zu)):
+            if t is not None:
+                self._check_in(t, (B, self.n), name)
+        single = rz.dim() == 2
+        if single:
+            rz = rz.unsqueeze(1)
+            rg = None if rg is None else rg.unsqueeze(1)
+        if rz.dim() != 3 or rz.shape[1] < 1:
+            raise ValueError(f"rz must be (B,{self.n}) or (B,k,{self.n}) with k >= 1")
+        k = int(rz.shape[1])
+        self._check_in(rz, (B, k, self.n), "rz")
+        if rg is not None:
+            self._check_in(rg, (B, k, hx), "rg")
+        if self.rolling_window == 1:      # (a rolling-window handle is refused by the library, history bound or not)
+            self._check_extra(B)
+        self.reserve(B)
+        keep, ptrs = [], []
+        for a in (lb, ub):
+            if a is None:
+                ptrs.append(None)
+            else:
+                a, p = _as_c_double(np.broadcast_to(np.asarray(a, dtype=np.float64), (self.n,)))
+                keep.append(a)
+                ptrs.append(p)
+        shapes = {"v": (B, k, self.n), "w": (B, k, hx), "gx0": (B, k, self.nx)}
+        res = {key: torch.empty(shapes[key], dtype=self.dtype, device=self.device) for key in want}
+        res["status"] = torch.empty(B, dtype=torch.int32, device=self.device)
+        opt = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        with torch.cuda.device(self.device):
+            for c0 in range(0, k, 64):
+                c1 = min(k, c0 + 64)
+                whole = c0 == 0 and c1 == k
+                rzc = rz.contiguous() if whole else rz[:, c0:c1].contiguous()
+                rgc = None if rg is None else (rg.contiguous() if whole else rg[:, c0:c1].contiguous())
+                outs = {key: (res[key] if whole else torch.empty((B, c1 - c0) + shapes[key][2:], dtype=self.dtype, device=self.device))
+                        for key in want}
+                _lib.check(self.lib.nempc_kkt_solve(self._handle, B, ctypes.c_void_p(Z.data_ptr()), ctypes.c_void_p(X0.data_ptr()),
+                                                    ctypes.c_void_p(lam.data_ptr()), opt(zl), opt(zu), ptrs[0], ptrs[1], c1 - c0,
+                                                    ctypes.c_void_p(rzc.data_ptr()), opt(rgc), opt(outs.get("v")), opt(outs.get("w")),
+                                                    opt(outs.get("gx0")), ctypes.c_void_p(res["status"].data_ptr()), self._stream()))
+                if not whole:
+                    for key in want:
+                        res[key][:, c0:c1] = outs[key]
+        if single:
+            for key in want:
+                res[key] = res[key][:, 0]
         return res
 
     def sync(self):

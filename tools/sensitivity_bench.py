@@ -10,6 +10,8 @@ are timed at the solution with its multipliers.  Arms, alternated `rounds` times
   eval(grad, g, jac_tiles)         one evaluation
   hess(hblocks)                    the Lagrangian blocks (sensitivity - eval - hess: the sweep kernel with its launch)
   kkt_residual                     one evaluation + the residual kernel
+  sensitivity(want = dz)           the call kkt_solve is measured against: the same evaluation, block launch and backward sweep
+  kkt_solve(nrhs = 1 | 16)         adjoint solve (CallbackEngine.kkt_solve, nempc_kkt_solve), random right-hand sides, v and gx0
 and the solve's wall time per iteration (a solve ends in a stream synchronisation).  Then the first-order predictor:
 |Z(x0 + d) - Z(x0) - S d|inf over the problems whose two solves converged and whose sensitivity status is 0, d random with
 |d|inf = 1e-2 and 1e-3 (the error should fall a hundredfold: it is second order).  Records, not gates."""
@@ -84,7 +86,12 @@ for title, c in SHAPES:
              lambda: eng.sensitivity(Z, X0, d["lam"], d["zl"], d["zu"], lb, -lb, want=("du0", "dz", "dlam", "gains"))),
             ("eval(grad, g, jac_tiles)", launch_eval),
             ("hess(hblocks)", lambda: eng.hess(Z, X0, d["lam"], ones, want=("hblocks",))),
-            ("kkt_residual", lambda: eng.kkt_residual(Z, X0, d["lam"], d["zl"], d["zu"], lb, -lb))]
+            ("kkt_residual", lambda: eng.kkt_residual(Z, X0, d["lam"], d["zl"], d["zu"], lb, -lb)),
+            ("sensitivity(want = dz)", lambda: eng.sensitivity(Z, X0, d["lam"], d["zl"], d["zu"], lb, -lb, want=("dz",)))]
+    for k in (1, 16):
+        rz = eng.to_device(np.random.default_rng(6).normal(size=(B, k, n)))
+        arms.append((f"kkt_solve(nrhs = {k}, want = v, gx0)",
+                     lambda rz=rz: eng.kkt_solve(Z, X0, d["lam"], d["zl"], d["zu"], lb, -lb, rz=rz, want=("v", "gx0"))))
     res = {k: [] for k, _ in arms}
     for _ in range(args.rounds):
         for k, fn in arms:
