@@ -158,8 +158,7 @@ int launch_kkt_solve(Handle& h, int B, const void* Z, const void* tiles, const v
     const size_t need = kktsolve_ws_doubles(h, Bm, nrhs);
     if (need > h.kktsolve_ws_doubles) {
         NEMPC_HIP(hipDeviceSynchronize());      // an earlier call may still run out of the old region on some stream
-        if (h.d_kktsolve_ws) NEMPC_HIP(hipFree(h.d_kktsolve_ws));
-        h.d_kktsolve_ws = nullptr;
+        dev_free(h.d_kktsolve_ws);
         h.kktsolve_ws_doubles = 0;
         const hipError_t e = hipMalloc((void**)&h.d_kktsolve_ws, need * sizeof(double));
         if (e != hipSuccess) {
@@ -195,8 +194,7 @@ int launch_kkt_solve(Handle& h, int B, const void* Z, const void* tiles, const v
 }
 
 void kktsolve_free(Handle& h) {
-    if (h.d_kktsolve_ws) (void)hipFree(h.d_kktsolve_ws);
-    h.d_kktsolve_ws = nullptr;
+    dev_free(h.d_kktsolve_ws);
     h.kktsolve_ws_doubles = 0;
 }
 

@@ -45,10 +45,14 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
+int fail(int code, const char* who, const char* what) { return fail(code, std::string(who) + what); }
+
 struct DeviceGuard {
     int prev = -1;
     bool ok = true;
-    explicit DeviceGuard(int dev) {
+    DeviceGuard() = default;        // (nothing until set())
+    explicit DeviceGuard(int dev) { set(dev); }
+    void set(int dev) {
         if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
         if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
         if (prev == dev) prev = -1;
@@ -71,20 +75,16 @@ int upload(const Handle& h, const std::vector<double>& src, void* dst) {
     return h.cfg.dtype == NEMPC_F64 ? upload_as<double>(src, dst) : upload_as<float>(src, dst);
 }
 
-int dev_alloc(void** p, size_t bytes) {
+template <class P>
+int dev_alloc(P** p, size_t bytes) {
     *p = nullptr;
     if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(p, bytes);
+    hipError_t e = hipMalloc((void**)p, bytes);
     if (e != hipSuccess) {
         set_error(std::string("hipMalloc: ") + hipGetErrorString(e));
         return NEMPC_ENOMEM;
     }
     return NEMPC_OK;
-}
-
-void dev_free(void*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
 }
 
 // decision variable (index into z) that tile / block column d of step t reads, or -1 when that window slot is
@@ -133,15 +133,12 @@ int rebuild_structure(Handle& h) {
     if (h.box)
         for (int k = 0; k < H * nx; ++k) put(H * nx + k, k, MAP_PLUS_ONE);
 
-    void* p = h.d_dense_map;
-    dev_free(p);
-    p = h.d_sparse_map;
-    dev_free(p);
-    p = h.d_g_ws;
-    dev_free(p);
+    dev_free(h.d_dense_map);
+    dev_free(h.d_sparse_map);
+    dev_free(h.d_g_ws);
     int rc;
-    if ((rc = dev_alloc((void**)&h.d_dense_map, dense.size() * sizeof(int32_t)))) return rc;
-    if ((rc = dev_alloc((void**)&h.d_sparse_map, sparse.size() * sizeof(int32_t)))) return rc;
+    if ((rc = dev_alloc(&h.d_dense_map, dense.size() * sizeof(int32_t)))) return rc;
+    if ((rc = dev_alloc(&h.d_sparse_map, sparse.size() * sizeof(int32_t)))) return rc;
     if ((rc = dev_alloc(&h.d_g_ws, (size_t)h.cfg.max_batch * m * h.esz))) return rc;
     NEMPC_HIP(hipMemcpy(h.d_dense_map, dense.data(), dense.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     NEMPC_HIP(hipMemcpy(h.d_sparse_map, sparse.data(), sparse.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -215,15 +212,11 @@ int upload_objective(Handle& h, const ObjHost& o_in) {
         for (int r = 0; r < n; ++r)
             for (int c = 0; c < n; ++c) emit(r, c);
 
-        void* p = h.d_hess_map;
-        dev_free(p);
-        h.d_hess_map = nullptr;
-        if ((rc = dev_alloc((void**)&h.d_hess_map, hmap.size() * sizeof(int32_t)))) return rc;
+        dev_free(h.d_hess_map);
+        if ((rc = dev_alloc(&h.d_hess_map, hmap.size() * sizeof(int32_t)))) return rc;
         NEMPC_HIP(hipMemcpy(h.d_hess_map, hmap.data(), hmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         // scatter form of the tril map for the Hessian kernel's fused assembly (plain models: one block element per entry)
-        p = h.d_hess_smap;
-        dev_free(p);
-        h.d_hess_smap = nullptr;
+        dev_free(h.d_hess_smap);
         h.hess_n_orph = -1;
         if (w == 1) {
             const int nnz_t = (int)h.hess_rows.size(), be = H * nin * nin;
@@ -234,7 +227,7 @@ int upload_objective(Handle& h, const ObjHost& o_in) {
             }
             if ((int)orph.size() <= nin * nin) {
                 smap.insert(smap.end(), orph.begin(), orph.end());
-                if ((rc = dev_alloc((void**)&h.d_hess_smap, smap.size() * sizeof(int32_t)))) return rc;
+                if ((rc = dev_alloc(&h.d_hess_smap, smap.size() * sizeof(int32_t)))) return rc;
                 NEMPC_HIP(hipMemcpy(h.d_hess_smap, smap.data(), smap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
                 h.hess_n_orph = (int)orph.size();
             }
@@ -286,17 +279,17 @@ void destroy_impl(Handle* h) {
     solver_free(*h);
     comm_free(*h);
     dev_free(h->d_obj);
-    void* p = h->d_dense_map; dev_free(p); h->d_dense_map = nullptr;
-    p = h->d_sparse_map; dev_free(p); h->d_sparse_map = nullptr;
-    p = h->d_hess_map; dev_free(p); h->d_hess_map = nullptr;
-    p = h->d_hess_smap; dev_free(p); h->d_hess_smap = nullptr;
+    dev_free(h->d_dense_map);
+    dev_free(h->d_sparse_map);
+    dev_free(h->d_hess_map);
+    dev_free(h->d_hess_smap);
     dev_free(h->d_tiles_ws);
     dev_free(h->d_g_ws);
     dev_free(h->d_valu_ws);
     dev_free(h->d_hess_ws);
     dev_free(h->d_kkt_grad);
-    { void* q = h->d_kkt_bounds; dev_free(q); h->d_kkt_bounds = nullptr; }
-    { void* q = h->d_sens_ws; dev_free(q); h->d_sens_ws = nullptr; }
+    dev_free(h->d_kkt_bounds);
+    dev_free(h->d_sens_ws);
     kktsolve_free(*h);
     delete h;
 }
@@ -321,6 +314,108 @@ int cached_bounds(Handle& h, const double* lb, const double* ub, const char* who
         h.kkt_bounds_host = both;
     }
     dlb = h.d_kkt_bounds; dub = h.d_kkt_bounds + h.n;
+    return NEMPC_OK;
+}
+
+// The workspaces sized by cfg.max_batch (nempc_create, nempc_reserve), all null on entry.  Not d_g_ws: its row count is
+// rebuild_structure's.  Sized and allocated here, not inside the first callback: an allocation is a synchronising call, is not
+// stream-capture safe, and an out-of-memory belongs to create / reserve, not to the middle of a solve.
+int alloc_batch_workspaces(Handle& h) {
+    const size_t Bm = (size_t)h.cfg.max_batch;
+    int rc;
+    if ((rc = dev_alloc(&h.d_tiles_ws, Bm * h.cfg.H * h.cfg.nx * h.nin * h.esz))) return rc;
+    if (h.layered) {
+        if ((rc = layered_reserve(h))) return rc;
+    } else {
+        if ((rc = ensure_valu_ws(h))) return rc;
+        if (h.layered_hess && (rc = layered_reserve(h))) return rc;
+    }
+    if ((rc = dev_alloc(&h.d_hess_ws, Bm * h.cfg.H * h.nin * h.nin * h.esz))) return rc;
+    if ((rc = dev_alloc(&h.d_kkt_grad, Bm * h.n * h.esz))) return rc;               // nempc_kkt_residual's evaluation
+    // nempc_sensitivity's double workspaces (plain models only: the call refuses rolling windows)
+    if (h.w == 1 && (rc = dev_alloc(&h.d_sens_ws, sens_ws_doubles(h, Bm) * sizeof(double)))) return rc;
+    return NEMPC_OK;
+}
+
+// nempc_set_objective; every null argument is its default (Q = I, R = 0.1 I, zero references and linear costs)
+int set_objective(Handle& h, const double* Q, const double* R, const double* xref, const double* uref, const double* cx,
+                  const double* cu) {
+    const int nx = h.cfg.nx, nu = h.cfg.nu, H = h.cfg.H;
+    ObjHost o;
+    o.Q.assign(nx * nx, 0.0);
+    o.R.assign(nu * nu, 0.0);
+    if (Q) o.Q.assign(Q, Q + nx * nx); else for (int i = 0; i < nx; ++i) o.Q[i * nx + i] = 1.0;
+    if (R) o.R.assign(R, R + nu * nu); else for (int i = 0; i < nu; ++i) o.R[i * nu + i] = 0.1;
+    o.xref.assign(H * nx, 0.0); o.cx.assign(H * nx, 0.0);
+    o.uref.assign(H * nu, 0.0); o.cu.assign(H * nu, 0.0);
+    if (xref) o.xref.assign(xref, xref + H * nx);
+    if (uref) o.uref.assign(uref, uref + H * nu);
+    if (cx) o.cx.assign(cx, cx + H * nx);
+    if (cu) o.cu.assign(cu, cu + H * nu);
+    return upload_objective(h, o);
+}
+
+// nempc_bind_tracking / nempc_bind_bounds: xs / us = one of the two arrays of state / control rows is given
+int check_bind(const Handle& h, const char* who, bool xs, bool us, int32_t B, int64_t ld_x, int64_t ld_u) {
+    if ((xs || us) && B < 1) return fail(NEMPC_EINVAL, who, ": B (problems the arrays cover) must be >= 1");
+    if (xs && ld_x < (int64_t)h.cfg.H * h.cfg.nx) return fail(NEMPC_EINVAL, who, ": ld_x must be at least H * nx");
+    if (us && ld_u < (int64_t)h.cfg.H * h.cfg.nu) return fail(NEMPC_EINVAL, who, ": ld_u must be at least H * nu");
+    return NEMPC_OK;
+}
+
+// The network can run for B problems (nempc_eval, nempc_hess, nempc_hess_gn, nempc_rollout): weights set, extras and
+// history bound and covering the batch.  nempc_solve words two of these differently and keeps its own.
+int check_network_inputs(const Handle& h, int B, const char* who) {
+    if (!h.have_weights) return fail(NEMPC_ESTATE, who, ": call nempc_set_weights first");
+    if (h.ne > 0 && !h.d_extra) return fail(NEMPC_ESTATE, who, ": n_extra > 0 but nempc_bind_extra was not called");
+    if (h.w > 1 && !h.d_hist_x) return fail(NEMPC_ESTATE, who, ": rolling_window > 1 but nempc_bind_history was not called");
+    if ((h.ne > 0 && B > h.extra_B) || (h.w > 1 && B > h.hist_B))
+        return fail(NEMPC_EINVAL, who, ": B exceeds the batch the bound extras / history cover");
+    return NEMPC_OK;
+}
+
+// ---- the post-solve point calls (nempc_kkt_residual, nempc_sensitivity, nempc_kkt_solve): a primal-dual point
+// (Z, X0, lam, zl, zu, lb, ub) on a plain-model handle.  Each entry point runs point_enter, then its own argument checks
+// (outputs, nrhs, the empty batch, null pointers: their order against each other differs), then point_prepare, then its launch.
+int point_enter(nempc_handle hh, int32_t B, const char* who, const char* rolling_refusal) {
+    if (!hh) return fail(NEMPC_EINVAL, who, ": null handle");
+    const Handle& h = *reinterpret_cast<Handle*>(hh);
+    if (h.w > 1) return fail(NEMPC_EUNSUPPORTED, who, rolling_refusal);
+    if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, who, ": B outside [0, max_batch]");
+    return NEMPC_OK;
+}
+
+enum : unsigned {
+    POINT_TRACKING = 1,   // check the tracking binding's coverage here (without it only an evaluation with grad does)
+    POINT_GRAD = 2,       // the objective gradient into d_kkt_grad
+    POINT_BLOCKS = 4,     // the Lagrangian blocks into d_hess_ws, and the sweeps' d_sens_ws
+};
+struct PointCall {
+    const double *dlb = nullptr, *dub = nullptr;   // lb / ub on the device (cached_bounds)
+    hipStream_t s = nullptr;
+    DeviceGuard dg;                                // the handle's device, for the entry point's launch
+};
+// Coverage of the bindings, the handle's workspaces, the bounds, then the point's tiles and g from one ordinary evaluation --
+// whatever nempc_eval launches at this shape, its checks too -- and its blocks from nempc_hess's dispatch, both into buffers
+// the handle owns (not the solver's).
+int point_prepare(nempc_handle hh, const char* who, unsigned needs, int32_t B, const void* Z, const void* X0,
+                  const void* lam, const double* lb, const double* ub, void* stream, PointCall& pc) {
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    if ((needs & POINT_TRACKING) && h.track.on() && B > h.track.B)
+        return fail(NEMPC_EINVAL, who, ": B exceeds the batch the bound tracking data cover");
+    if (h.bbind.on() && B > h.bbind.B) return fail(NEMPC_EINVAL, who, ": B exceeds the batch the bound per-problem bounds cover");
+    if (((needs & POINT_GRAD) && !h.d_kkt_grad) || ((needs & POINT_BLOCKS) && (!h.d_sens_ws || !h.d_hess_ws)) ||
+        !h.d_kkt_bounds || !h.d_g_ws || !h.d_tiles_ws)
+        return fail(NEMPC_ESTATE, who, ": the handle's workspaces are gone (a failed nempc_reserve)");
+    pc.s = reinterpret_cast<hipStream_t>(stream);
+    if (int rc = cached_bounds(h, lb, ub, who, pc.s, pc.dlb, pc.dub)) return rc;
+    void* const grad = (needs & POINT_GRAD) ? h.d_kkt_grad : nullptr;
+    if (int rc = nempc_eval(hh, B, Z, X0, nullptr, grad, h.d_g_ws, nullptr, h.d_tiles_ws, nullptr, stream)) return rc;
+    // (blocks only: the objective factor, which nempc_hess asks for and only its assembly reads, is not used -- any pointer)
+    if (needs & POINT_BLOCKS)
+        if (int rc = nempc_hess(hh, B, Z, X0, lam, lam, nullptr, nullptr, h.d_hess_ws, stream)) return rc;
+    pc.dg.set(h.cfg.device);
+    if (!pc.dg.ok) return fail(NEMPC_EHIP, who, ": hipSetDevice failed");
     return NEMPC_OK;
 }
 
@@ -445,35 +540,10 @@ int nempc_create(const nempc_config* cfg, nempc_handle* out) {
         }
     }
 
-    int rc = NEMPC_OK;
-    const size_t Bm = (size_t)cfg->max_batch;
-    do {
-        if ((rc = dev_alloc(&h->d_tiles_ws, Bm * cfg->H * cfg->nx * h->nin * h->esz))) break;
-        // workspaces are sized and allocated HERE (and in nempc_reserve), not inside the first callback: an allocation is a
-        // synchronising call, is not stream-capture safe, and an out-of-memory belongs to create, not to the middle of a solve
-        if (h->layered) {
-            if ((rc = layered_reserve(*h))) break;
-        } else {
-            if ((rc = ensure_valu_ws(*h))) break;
-            if (h->layered_hess && (rc = layered_reserve(*h))) break;
-        }
-        if ((rc = dev_alloc(&h->d_hess_ws, Bm * cfg->H * h->nin * h->nin * h->esz))) break;
-        if ((rc = dev_alloc(&h->d_kkt_grad, Bm * h->n * h->esz))) break;               // nempc_kkt_residual's evaluation
-        if ((rc = dev_alloc((void**)&h->d_kkt_bounds, (size_t)2 * h->n * sizeof(double)))) break;
-        // nempc_sensitivity's double workspaces (plain models only: the call refuses rolling windows)
-        if (h->w == 1 && (rc = dev_alloc((void**)&h->d_sens_ws, sens_ws_doubles(*h, Bm) * sizeof(double)))) break;
-        if ((rc = rebuild_structure(*h))) break;
-        ObjHost o;
-        const int nx = cfg->nx, nu = cfg->nu, H = cfg->H;
-        o.Q.assign(nx * nx, 0.0);
-        o.R.assign(nu * nu, 0.0);
-        for (int i = 0; i < nx; ++i) o.Q[i * nx + i] = 1.0;
-        for (int i = 0; i < nu; ++i) o.R[i * nu + i] = 0.1;
-        o.xref.assign(H * nx, 0.0); o.cx.assign(H * nx, 0.0);
-        o.uref.assign(H * nu, 0.0); o.cu.assign(H * nu, 0.0);
-        if ((rc = upload_objective(*h, o))) break;
-    } while (0);
-    if (rc) {
+    int rc;
+    if ((rc = alloc_batch_workspaces(*h)) || (rc = dev_alloc(&h->d_kkt_bounds, (size_t)2 * h->n * sizeof(double))) ||
+        (rc = rebuild_structure(*h)) ||                                          // (d_g_ws with the maps)
+        (rc = set_objective(*h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) {
         std::string keep = g_last_error;
         destroy_impl(h);
         set_error(keep);
@@ -501,25 +571,12 @@ int nempc_reserve(nempc_handle hh, int32_t max_batch) {
     // an evaluation may still be running out of the old workspaces on some stream
     NEMPC_HIP(hipDeviceSynchronize());
     h.cfg.max_batch = max_batch;
-    const size_t Bm = (size_t)max_batch;
     rk4hess_free(h);      // sized lazily from max_batch on their next use
     solver_free(h);
     dev_free(h.d_tiles_ws); dev_free(h.d_valu_ws); dev_free(h.d_hess_ws); dev_free(h.d_g_ws); dev_free(h.d_kkt_grad);
-    { void* q = h.d_sens_ws; dev_free(q); h.d_sens_ws = nullptr; }
-    int rc = NEMPC_OK;
-    do {
-        if ((rc = dev_alloc(&h.d_tiles_ws, Bm * h.cfg.H * h.cfg.nx * h.nin * h.esz))) break;
-        if (h.layered) {
-            if ((rc = layered_reserve(h))) break;
-        } else {
-            if ((rc = ensure_valu_ws(h))) break;
-            if (h.layered_hess && (rc = layered_reserve(h))) break;
-        }
-        if ((rc = dev_alloc(&h.d_hess_ws, Bm * h.cfg.H * h.nin * h.nin * h.esz))) break;
-        if ((rc = dev_alloc(&h.d_g_ws, Bm * h.m * h.esz))) break;
-        if ((rc = dev_alloc(&h.d_kkt_grad, Bm * h.n * h.esz))) break;
-        if (h.w == 1 && (rc = dev_alloc((void**)&h.d_sens_ws, sens_ws_doubles(h, Bm) * sizeof(double)))) break;
-    } while (0);
+    dev_free(h.d_sens_ws);
+    int rc = alloc_batch_workspaces(h);
+    if (!rc) rc = dev_alloc(&h.d_g_ws, (size_t)max_batch * h.m * h.esz);
     if (rc) h.cfg.max_batch = 0;   // workspaces are gone: every evaluation is refused until a reserve succeeds
     return rc;
 }
@@ -561,19 +618,7 @@ int nempc_set_objective(nempc_handle hh, const double* Q, const double* R, const
     Handle& h = *reinterpret_cast<Handle*>(hh);
     DeviceGuard dg(h.cfg.device);
     if (!dg.ok) return fail(NEMPC_EHIP, "nempc_set_objective: hipSetDevice failed");
-    const int nx = h.cfg.nx, nu = h.cfg.nu, H = h.cfg.H;
-    ObjHost o;
-    o.Q.assign(nx * nx, 0.0);
-    o.R.assign(nu * nu, 0.0);
-    if (Q) o.Q.assign(Q, Q + nx * nx); else for (int i = 0; i < nx; ++i) o.Q[i * nx + i] = 1.0;
-    if (R) o.R.assign(R, R + nu * nu); else for (int i = 0; i < nu; ++i) o.R[i * nu + i] = 0.1;
-    o.xref.assign(H * nx, 0.0); o.cx.assign(H * nx, 0.0);
-    o.uref.assign(H * nu, 0.0); o.cu.assign(H * nu, 0.0);
-    if (xref) o.xref.assign(xref, xref + H * nx);
-    if (uref) o.uref.assign(uref, uref + H * nu);
-    if (cx) o.cx.assign(cx, cx + H * nx);
-    if (cu) o.cu.assign(cu, cu + H * nu);
-    return upload_objective(h, o);
+    return set_objective(h, Q, R, xref, uref, cx, cu);
 }
 
 int nempc_set_terminal_weight(nempc_handle hh, const double* QT) {
@@ -614,17 +659,9 @@ int nempc_bind_tracking(nempc_handle hh, const void* xref, const void* uref, con
                         int64_t ld_x, int64_t ld_u) {
     if (!hh) return fail(NEMPC_EINVAL, "nempc_bind_tracking: null handle");
     Handle& h = *reinterpret_cast<Handle*>(hh);
-    const bool any = xref || uref || cx || cu;
-    if (any && B < 1) return fail(NEMPC_EINVAL, "nempc_bind_tracking: B (problems the arrays cover) must be >= 1");
-    if ((xref || cx) && ld_x < (int64_t)h.cfg.H * h.cfg.nx)
-        return fail(NEMPC_EINVAL, "nempc_bind_tracking: ld_x must be at least H * nx");
-    if ((uref || cu) && ld_u < (int64_t)h.cfg.H * h.cfg.nu)
-        return fail(NEMPC_EINVAL, "nempc_bind_tracking: ld_u must be at least H * nu");
-    h.track = TrackBind{};
-    if (any) {
-        h.track.xref = xref; h.track.uref = uref; h.track.cx = cx; h.track.cu = cu;
-        h.track.ld_x = ld_x; h.track.ld_u = ld_u; h.track.B = B;
-    }
+    const bool xs = xref || cx, us = uref || cu;
+    if (int rc = check_bind(h, "nempc_bind_tracking", xs, us, B, ld_x, ld_u)) return rc;
+    h.track = (xs || us) ? TrackBind{xref, uref, cx, cu, ld_x, ld_u, B} : TrackBind{};
     return NEMPC_OK;
 }
 
@@ -632,17 +669,9 @@ int nempc_bind_bounds(nempc_handle hh, const void* xlb, const void* xub, const v
                       int64_t ld_x, int64_t ld_u) {
     if (!hh) return fail(NEMPC_EINVAL, "nempc_bind_bounds: null handle");
     Handle& h = *reinterpret_cast<Handle*>(hh);
-    const bool any = xlb || xub || ulb || uub;
-    if (any && B < 1) return fail(NEMPC_EINVAL, "nempc_bind_bounds: B (problems the arrays cover) must be >= 1");
-    if ((xlb || xub) && ld_x < (int64_t)h.cfg.H * h.cfg.nx)
-        return fail(NEMPC_EINVAL, "nempc_bind_bounds: ld_x must be at least H * nx");
-    if ((ulb || uub) && ld_u < (int64_t)h.cfg.H * h.cfg.nu)
-        return fail(NEMPC_EINVAL, "nempc_bind_bounds: ld_u must be at least H * nu");
-    h.bbind = BoundBind{};
-    if (any) {
-        h.bbind.xlb = xlb; h.bbind.xub = xub; h.bbind.ulb = ulb; h.bbind.uub = uub;
-        h.bbind.ld_x = ld_x; h.bbind.ld_u = ld_u; h.bbind.B = B;
-    }
+    const bool xs = xlb || xub, us = ulb || uub;
+    if (int rc = check_bind(h, "nempc_bind_bounds", xs, us, B, ld_x, ld_u)) return rc;
+    h.bbind = (xs || us) ? BoundBind{xlb, xub, ulb, uub, ld_x, ld_u, B} : BoundBind{};
     return NEMPC_OK;
 }
 
@@ -711,12 +740,8 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
     if (!Z) return fail(NEMPC_EINVAL, "nempc_eval: Z is null");
     const bool need_rows = g || jac_dense || jac_tiles || jac_sparse;
     if (need_rows && !X0) return fail(NEMPC_EINVAL, "nempc_eval: X0 is null");
-    if (need_rows && !h.have_weights) return fail(NEMPC_ESTATE, "nempc_eval: call nempc_set_weights first");
-    if (need_rows && h.ne > 0 && !h.d_extra) return fail(NEMPC_ESTATE, "nempc_eval: n_extra > 0 but nempc_bind_extra was not called");
-    if (need_rows && h.w > 1 && !h.d_hist_x)
-        return fail(NEMPC_ESTATE, "nempc_eval: rolling_window > 1 but nempc_bind_history was not called");
-    if (need_rows && ((h.ne > 0 && B > h.extra_B) || (h.w > 1 && B > h.hist_B)))
-        return fail(NEMPC_EINVAL, "nempc_eval: B exceeds the batch the bound extras / history cover");
+    if (need_rows)
+        if (int rc = check_network_inputs(h, B, "nempc_eval")) return rc;
     // per-problem tracking data (nempc_bind_tracking): the launches that fuse the shared objective get no f / grad (ff, gf)
     // and the binding's own kernel follows them
     const bool trk = (f || grad) && h.track.on();
@@ -775,12 +800,7 @@ int nempc_hess(nempc_handle hh, int32_t B, const void* Z, const void* X0, const 
     if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_hess: B outside [0, max_batch]");
     if (B == 0) return NEMPC_OK;
     if (!Z || !X0 || !lambda || !sigma) return fail(NEMPC_EINVAL, "nempc_hess: null input");
-    if (!h.have_weights) return fail(NEMPC_ESTATE, "nempc_hess: call nempc_set_weights first");
-    if (h.ne > 0 && !h.d_extra) return fail(NEMPC_ESTATE, "nempc_hess: n_extra > 0 but nempc_bind_extra was not called");
-    if (h.w > 1 && !h.d_hist_x)
-        return fail(NEMPC_ESTATE, "nempc_hess: rolling_window > 1 but nempc_bind_history was not called");
-    if ((h.ne > 0 && B > h.extra_B) || (h.w > 1 && B > h.hist_B))
-        return fail(NEMPC_EINVAL, "nempc_hess: B exceeds the batch the bound extras / history cover");
+    if (int rc = check_network_inputs(h, B, "nempc_hess")) return rc;
     DeviceGuard dg(h.cfg.device);
     if (!dg.ok) return fail(NEMPC_EHIP, "nempc_hess: hipSetDevice failed");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -809,12 +829,7 @@ int nempc_hess_gn(nempc_handle hh, int32_t B, const void* Z, const void* X0, con
     if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_hess_gn: B outside [0, max_batch]");
     if (B == 0) return NEMPC_OK;
     if (!Z || !X0 || !sigma) return fail(NEMPC_EINVAL, "nempc_hess_gn: null input");
-    if (!h.have_weights) return fail(NEMPC_ESTATE, "nempc_hess_gn: call nempc_set_weights first");
-    if (h.ne > 0 && !h.d_extra) return fail(NEMPC_ESTATE, "nempc_hess_gn: n_extra > 0 but nempc_bind_extra was not called");
-    if (h.w > 1 && !h.d_hist_x)
-        return fail(NEMPC_ESTATE, "nempc_hess_gn: rolling_window > 1 but nempc_bind_history was not called");
-    if ((h.ne > 0 && B > h.extra_B) || (h.w > 1 && B > h.hist_B))
-        return fail(NEMPC_EINVAL, "nempc_hess_gn: B exceeds the batch the bound extras / history cover");
+    if (int rc = check_network_inputs(h, B, "nempc_hess_gn")) return rc;
     DeviceGuard dg(h.cfg.device);
     if (!dg.ok) return fail(NEMPC_EHIP, "nempc_hess_gn: hipSetDevice failed");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -873,88 +888,51 @@ int nempc_solve_duals(nempc_handle hh, int32_t B, const void* X0, void* Z, const
 
 int nempc_kkt_residual(nempc_handle hh, int32_t B, const void* Z, const void* X0, const void* lam, const void* zl,
                        const void* zu, const double* lb, const double* ub, void* r, void* stat, void* stream) {
-    if (!hh) return fail(NEMPC_EINVAL, "nempc_kkt_residual: null handle");
-    Handle& h = *reinterpret_cast<Handle*>(hh);
-    if (h.w > 1)
-        return fail(NEMPC_EUNSUPPORTED, "nempc_kkt_residual: rolling_window > 1 handles are not supported (the band product is "
-                                        "built for the tiles of a plain model)");
-    if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_kkt_residual: B outside [0, max_batch]");
+    const char* const who = "nempc_kkt_residual";
+    if (int rc = point_enter(hh, B, who, ": rolling_window > 1 handles are not supported (the band product is built for the "
+                                         "tiles of a plain model)")) return rc;
     if (B == 0) return NEMPC_OK;
     if (!Z || !X0 || !lam || !r) return fail(NEMPC_EINVAL, "nempc_kkt_residual: null argument (Z, X0, lam and r are required)");
-    if (h.bbind.on() && B > h.bbind.B)
-        return fail(NEMPC_EINVAL, "nempc_kkt_residual: B exceeds the batch the bound per-problem bounds cover");
-    if (!h.d_kkt_grad || !h.d_kkt_bounds || !h.d_g_ws || !h.d_tiles_ws)
-        return fail(NEMPC_ESTATE, "nempc_kkt_residual: the handle's workspaces are gone (a failed nempc_reserve)");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const double *dlb = nullptr, *dub = nullptr;
-    if (int rc = cached_bounds(h, lb, ub, "nempc_kkt_residual", s, dlb, dub)) return rc;
-    // one ordinary evaluation: whatever nempc_eval launches for grad, g and the compact tiles at this shape (its checks too)
-    if (int rc = nempc_eval(hh, B, Z, X0, nullptr, h.d_kkt_grad, h.d_g_ws, nullptr, h.d_tiles_ws, nullptr, stream)) return rc;
-    DeviceGuard dg(h.cfg.device);
-    if (!dg.ok) return fail(NEMPC_EHIP, "nempc_kkt_residual: hipSetDevice failed");
-    return launch_kkt_residual(h, B, Z, h.d_kkt_grad, h.d_g_ws, h.d_tiles_ws, lam, zl, zu, dlb, dub, r, stat, s);
+    // (no tracking check of its own: its evaluation asks for grad, and nempc_eval checks the binding then)
+    PointCall pc;
+    if (int rc = point_prepare(hh, who, POINT_GRAD, B, Z, X0, lam, lb, ub, stream, pc)) return rc;
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    return launch_kkt_residual(h, B, Z, h.d_kkt_grad, h.d_g_ws, h.d_tiles_ws, lam, zl, zu, pc.dlb, pc.dub, r, stat, pc.s);
 }
 
 int nempc_sensitivity(nempc_handle hh, int32_t B, const void* Z, const void* X0, const void* lam, const void* zl,
                       const void* zu, const double* lb, const double* ub, void* dU0, void* dZ, void* dlam, void* gains,
                       int32_t* status, void* stream) {
-    if (!hh) return fail(NEMPC_EINVAL, "nempc_sensitivity: null handle");
-    Handle& h = *reinterpret_cast<Handle*>(hh);
-    if (h.w > 1)
-        return fail(NEMPC_EUNSUPPORTED, "nempc_sensitivity: rolling_window > 1 handles are not supported (the sweep is built "
-                                        "for the stages of a plain model)");
-    if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_sensitivity: B outside [0, max_batch]");
+    const char* const who = "nempc_sensitivity";
+    if (int rc = point_enter(hh, B, who, ": rolling_window > 1 handles are not supported (the sweep is built for the stages "
+                                         "of a plain model)")) return rc;
     if (!dU0 && !dZ && !dlam && !gains) return fail(NEMPC_EINVAL, "nempc_sensitivity: no output asked for (dU0, dZ, dlam, gains all null)");
     if (B == 0) return NEMPC_OK;
     if (!Z || !X0 || !lam || !status)
         return fail(NEMPC_EINVAL, "nempc_sensitivity: null argument (Z, X0, lam and status are required)");
     // (a tracking binding changes no second-order term, but the batch it covers is checked as nempc_kkt_residual's evaluation does)
-    if (h.track.on() && B > h.track.B) return fail(NEMPC_EINVAL, "nempc_sensitivity: B exceeds the batch the bound tracking data cover");
-    if (h.bbind.on() && B > h.bbind.B)
-        return fail(NEMPC_EINVAL, "nempc_sensitivity: B exceeds the batch the bound per-problem bounds cover");
-    if (!h.d_sens_ws || !h.d_kkt_bounds || !h.d_g_ws || !h.d_tiles_ws || !h.d_hess_ws)
-        return fail(NEMPC_ESTATE, "nempc_sensitivity: the handle's workspaces are gone (a failed nempc_reserve)");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const double *dlb = nullptr, *dub = nullptr;
-    if (int rc = cached_bounds(h, lb, ub, "nempc_sensitivity", s, dlb, dub)) return rc;
-    // the tiles from one ordinary evaluation, the Lagrangian blocks from nempc_hess's dispatch (their checks too), both into
-    // buffers the handle owns (not the solver's)
-    if (int rc = nempc_eval(hh, B, Z, X0, nullptr, nullptr, h.d_g_ws, nullptr, h.d_tiles_ws, nullptr, stream)) return rc;
-    // (blocks only: the objective factor, which nempc_hess asks for and only its assembly reads, is not used -- any pointer)
-    if (int rc = nempc_hess(hh, B, Z, X0, lam, lam, nullptr, nullptr, h.d_hess_ws, stream)) return rc;
-    DeviceGuard dg(h.cfg.device);
-    if (!dg.ok) return fail(NEMPC_EHIP, "nempc_sensitivity: hipSetDevice failed");
-    return launch_sensitivity(h, B, Z, h.d_tiles_ws, h.d_hess_ws, zl, zu, dlb, dub, dU0, dZ, dlam, gains, status, s);
+    PointCall pc;
+    if (int rc = point_prepare(hh, who, POINT_TRACKING | POINT_BLOCKS, B, Z, X0, lam, lb, ub, stream, pc)) return rc;
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    return launch_sensitivity(h, B, Z, h.d_tiles_ws, h.d_hess_ws, zl, zu, pc.dlb, pc.dub, dU0, dZ, dlam, gains, status, pc.s);
 }
 
 int nempc_kkt_solve(nempc_handle hh, int32_t B, const void* Z, const void* X0, const void* lam, const void* zl,
                     const void* zu, const double* lb, const double* ub, int32_t nrhs, const void* rz, const void* rg, void* v,
                     void* w, void* gx0, int32_t* status, void* stream) {
-    if (!hh) return fail(NEMPC_EINVAL, "nempc_kkt_solve: null handle");
-    Handle& h = *reinterpret_cast<Handle*>(hh);
-    if (h.w > 1)
-        return fail(NEMPC_EUNSUPPORTED, "nempc_kkt_solve: rolling_window > 1 handles are not supported (the sweep is built "
-                                        "for the stages of a plain model)");
-    if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_kkt_solve: B outside [0, max_batch]");
+    const char* const who = "nempc_kkt_solve";
+    if (int rc = point_enter(hh, B, who, ": rolling_window > 1 handles are not supported (the sweep is built for the stages "
+                                         "of a plain model)")) return rc;
     if (nrhs < 1 || nrhs > 64) return fail(NEMPC_EINVAL, "nempc_kkt_solve: nrhs outside [1, 64]");
     if (!v && !w && !gx0) return fail(NEMPC_EINVAL, "nempc_kkt_solve: no output asked for (v, w, gx0 all null)");
     if (B == 0) return NEMPC_OK;
     if (!Z || !X0 || !lam || !rz || !status)
         return fail(NEMPC_EINVAL, "nempc_kkt_solve: null argument (Z, X0, lam, rz and status are required)");
-    if (h.track.on() && B > h.track.B) return fail(NEMPC_EINVAL, "nempc_kkt_solve: B exceeds the batch the bound tracking data cover");
-    if (h.bbind.on() && B > h.bbind.B)
-        return fail(NEMPC_EINVAL, "nempc_kkt_solve: B exceeds the batch the bound per-problem bounds cover");
-    if (!h.d_sens_ws || !h.d_kkt_bounds || !h.d_g_ws || !h.d_tiles_ws || !h.d_hess_ws)
-        return fail(NEMPC_ESTATE, "nempc_kkt_solve: the handle's workspaces are gone (a failed nempc_reserve)");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const double *dlb = nullptr, *dub = nullptr;
-    if (int rc = cached_bounds(h, lb, ub, "nempc_kkt_solve", s, dlb, dub)) return rc;
     // tiles and Lagrangian blocks exactly as nempc_sensitivity gets them
-    if (int rc = nempc_eval(hh, B, Z, X0, nullptr, nullptr, h.d_g_ws, nullptr, h.d_tiles_ws, nullptr, stream)) return rc;
-    if (int rc = nempc_hess(hh, B, Z, X0, lam, lam, nullptr, nullptr, h.d_hess_ws, stream)) return rc;
-    DeviceGuard dg(h.cfg.device);
-    if (!dg.ok) return fail(NEMPC_EHIP, "nempc_kkt_solve: hipSetDevice failed");
-    return launch_kkt_solve(h, B, Z, h.d_tiles_ws, h.d_hess_ws, zl, zu, dlb, dub, nrhs, rz, rg, v, w, gx0, status, s);
+    PointCall pc;
+    if (int rc = point_prepare(hh, who, POINT_TRACKING | POINT_BLOCKS, B, Z, X0, lam, lb, ub, stream, pc)) return rc;
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    return launch_kkt_solve(h, B, Z, h.d_tiles_ws, h.d_hess_ws, zl, zu, pc.dlb, pc.dub, nrhs, rz, rg, v, w, gx0, status, pc.s);
 }
 
 int nempc_rollout(nempc_handle hh, int32_t B, const void* X0, void* Z, void* f, void* stream) {
@@ -963,13 +941,9 @@ int nempc_rollout(nempc_handle hh, int32_t B, const void* X0, void* Z, void* f, 
     if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_rollout: B outside [0, max_batch]");
     if (B == 0) return NEMPC_OK;
     if (!Z || !X0) return fail(NEMPC_EINVAL, "nempc_rollout: null argument");
-    if (!h.have_weights) return fail(NEMPC_ESTATE, "nempc_rollout: call nempc_set_weights first");
+    if (int rc = check_network_inputs(h, B, "nempc_rollout")) return rc;
+    // (cannot fire on a live handle -- nempc_create uploads the default objective -- so its place among the checks is free)
     if (f && !h.have_objective) return fail(NEMPC_ESTATE, "nempc_rollout: f asked for but the handle has no objective");
-    if (h.ne > 0 && !h.d_extra) return fail(NEMPC_ESTATE, "nempc_rollout: n_extra > 0 but nempc_bind_extra was not called");
-    if (h.w > 1 && !h.d_hist_x)
-        return fail(NEMPC_ESTATE, "nempc_rollout: rolling_window > 1 but nempc_bind_history was not called");
-    if ((h.ne > 0 && B > h.extra_B) || (h.w > 1 && B > h.hist_B))
-        return fail(NEMPC_EINVAL, "nempc_rollout: B exceeds the batch the bound extras / history cover");
     if (f && h.track.on() && B > h.track.B)
         return fail(NEMPC_EINVAL, "nempc_rollout: B exceeds the batch the bound tracking data cover");
     const int which = env_int("NEMPC_ROLLOUT_KERNEL", 0);

@@ -34,6 +34,13 @@ inline bool env_set(const char* name) { return getenv(name) != nullptr; }       
         if (_e != hipSuccess) return ::nempc::hip_fail(_e, #call); \
     } while (0)
 
+// frees a device allocation and nulls the pointer that named it (so that no later free sees the address again)
+template <class P>
+void dev_free(P*& p) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+}
+
 // How one (problem, step) row reads its network inputs: plain models read [x_{t-1} | u_t]; rolling-window models
 // (model/tensorflow.py:112-130 rolling_input) read the last w states and controls, reaching into x0 and the bound
 // history before the horizon.  Tile / block column d indexes the window in the network's input order.

@@ -38,6 +38,11 @@ def _as_c_double(a):
     return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
+def _ptr(t):
+    """device pointer of a tensor for the C ABI; None stays None (an optional argument)"""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
 class CallbackEngine:
     def __init__(self, weights, biases, H, nx, nu, integrator="discret", DT=1.0, dtype=torch.float64,
                  device="cuda", max_batch=1, kernel="auto", n_extra=0, rolling_window=1, forward_rolling=True,
@@ -567,14 +572,8 @@ class CallbackEngine:
             Z = Z_init.clone()
             if init == "rollout":
                 self.rollout(X0, Z=Z)
-        keep, ptrs = [], []
-        for v in (lb, ub):
-            if v is None:
-                ptrs.append(None)
-            else:
-                a, p = _as_c_double(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n,)))
-                keep.append(a)
-                ptrs.append(p)
+        keep = []
+        ptrs = [self._host_vector(v, keep) for v in (lb, ub)]
         its_dev = torch.zeros(B, dtype=torch.int32, device=self.device) if return_iterations else None
         opts = _lib.NempcSolverOpts(max_iter=max_iter, max_linesearch=max_linesearch, check_every=check_every,
                                     lq_kernel={"auto": 0, "thread": 1, "wave": 2, "scan": 3}[lq_kernel],
@@ -605,6 +604,37 @@ class CallbackEngine:
         res = (Z, status, iters.value) + ((its_dev,) if return_iterations else ()) + ((duals,) if return_duals else ())
         return res
 
+    def _host_vector(self, v, keep):
+        """lb / ub: (n) host vector (or what broadcasts to one) -> pointer to doubles for the C ABI, None stays None; the
+        array the pointer names goes into `keep`"""
+        if v is None:
+            return None
+        a, p = _as_c_double(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n,)))
+        keep.append(a)
+        return p
+
+    def _check_point(self, B, Z, X0, lam, zl, zu):
+        self._check_in(Z, (B, self.n), "Z")
+        self._check_in(X0, (B, self.nx), "X0")
+        self._check_in(lam, (B, self.m), "lam")
+        for name, t in (("zl", zl), ("zu", zu)):
+            if t is not None:
+                self._check_in(t, (B, self.n), name)
+
+    def _point(self, Z, X0, lam, zl, zu, lb, ub, checked=False):
+        """A primal-dual point for nempc_kkt_residual / nempc_sensitivity / nempc_kkt_solve: shape checks (unless the caller
+        made them, with checks of its own behind them), bound extras, workspaces for the batch.  -> (B, the seven C
+        arguments after B, the host arrays to keep alive over the call)."""
+        B = int(Z.shape[0])
+        if not checked:
+            self._check_point(B, Z, X0, lam, zl, zu)
+        if self.rolling_window == 1:      # (a rolling-window handle is refused by the library, history bound or not)
+            self._check_extra(B)
+        self.reserve(B)
+        keep = []
+        bounds = [self._host_vector(v, keep) for v in (lb, ub)]
+        return B, (_ptr(Z), _ptr(X0), _ptr(lam), _ptr(zl), _ptr(zu), *bounds), keep
+
     def kkt_residual(self, Z, X0, lam, zl=None, zu=None, lb=None, ub=None, want_stat=False):
         """KKT residuals of B primal-dual points (nempc_kkt_residual; any points, a solver's or not).  Z (B,n), X0 (B,nx),
         lam (B,m) device tensors; zl, zu (B,n) multipliers of z >= lb, z <= ub or None (zeros); lb / ub (n) host vectors as in
@@ -612,31 +642,11 @@ class CallbackEngine:
         primal feasibility, complementarity, dual feasibility] per problem, or (r, stat (B,n)) with the stationarity vector
         when want_stat (the engine's own output tensors, reused between calls like `eval`'s).  One callback evaluation and
         one reduction kernel; asynchronous on the current torch stream."""
-        B = int(Z.shape[0])
-        self._check_in(Z, (B, self.n), "Z")
-        self._check_in(X0, (B, self.nx), "X0")
-        self._check_in(lam, (B, self.m), "lam")
-        for name, t in (("zl", zl), ("zu", zu)):
-            if t is not None:
-                self._check_in(t, (B, self.n), name)
-        if self.rolling_window == 1:      # (a rolling-window handle is refused by the library, history bound or not)
-            self._check_extra(B)
-        self.reserve(B)
-        keep, ptrs = [], []
-        for v in (lb, ub):
-            if v is None:
-                ptrs.append(None)
-            else:
-                a, p = _as_c_double(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n,)))
-                keep.append(a)
-                ptrs.append(p)
+        B, point, keep = self._point(Z, X0, lam, zl, zu, lb, ub)
         r = self._out("kkt_r", (B, 4))
         stat = self._out("kkt_stat", (B, self.n)) if want_stat else None
-        opt = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.nempc_kkt_residual(self._handle, B, ctypes.c_void_p(Z.data_ptr()), ctypes.c_void_p(X0.data_ptr()),
-                                                   ctypes.c_void_p(lam.data_ptr()), opt(zl), opt(zu), ptrs[0], ptrs[1],
-                                                   ctypes.c_void_p(r.data_ptr()), opt(stat), self._stream()))
+            _lib.check(self.lib.nempc_kkt_residual(self._handle, B, *point, _ptr(r), _ptr(stat), self._stream()))
         return (r, stat) if want_stat else r
 
     def sensitivity(self, Z, X0, lam, zl=None, zu=None, lb=None, ub=None, want=("du0",)):
@@ -652,34 +662,14 @@ class CallbackEngine:
         want = tuple(want)
         if not want or any(k not in names for k in want):
             raise ValueError(f"want must name at least one of {names}")
-        B = int(Z.shape[0])
-        self._check_in(Z, (B, self.n), "Z")
-        self._check_in(X0, (B, self.nx), "X0")
-        self._check_in(lam, (B, self.m), "lam")
-        for name, t in (("zl", zl), ("zu", zu)):
-            if t is not None:
-                self._check_in(t, (B, self.n), name)
-        if self.rolling_window == 1:      # (a rolling-window handle is refused by the library, history bound or not)
-            self._check_extra(B)
-        self.reserve(B)
-        keep, ptrs = [], []
-        for v in (lb, ub):
-            if v is None:
-                ptrs.append(None)
-            else:
-                a, p = _as_c_double(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n,)))
-                keep.append(a)
-                ptrs.append(p)
+        B, point, keep = self._point(Z, X0, lam, zl, zu, lb, ub)
         shapes = {"du0": (B, self.nu, self.nx), "dz": (B, self.n, self.nx), "dlam": (B, self.H * self.nx, self.nx),
                   "gains": (B, self.H, self.nu, self.nx)}
         res = {k: torch.empty(shapes[k], dtype=self.dtype, device=self.device) for k in want}
         res["status"] = torch.empty(B, dtype=torch.int32, device=self.device)
-        opt = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.nempc_sensitivity(self._handle, B, ctypes.c_void_p(Z.data_ptr()), ctypes.c_void_p(X0.data_ptr()),
-                                                  ctypes.c_void_p(lam.data_ptr()), opt(zl), opt(zu), ptrs[0], ptrs[1],
-                                                  opt(res.get("du0")), opt(res.get("dz")), opt(res.get("dlam")),
-                                                  opt(res.get("gains")), ctypes.c_void_p(res["status"].data_ptr()),
+            _lib.check(self.lib.nempc_sensitivity(self._handle, B, *point, _ptr(res.get("du0")), _ptr(res.get("dz")),
+                                                  _ptr(res.get("dlam")), _ptr(res.get("gains")), _ptr(res["status"]),
                                                   self._stream()))
         return res
 
@@ -700,14 +690,8 @@ class CallbackEngine:
             raise ValueError(f"want must name at least one of {names}")
         if rz is None:
             raise ValueError("rz is required")
-        B = int(Z.shape[0])
-        hx = self.H * self.nx
-        self._check_in(Z, (B, self.n), "Z")
-        self._check_in(X0, (B, self.nx), "X0")
-        self._check_in(lam, (B, self.m), "lam")
-        for name, t in (("zl", zl), ("zu", zu)):
-            if t is not None:
-                self._check_in(t, (B, self.n), name)
+        B, hx = int(Z.shape[0]), self.H * self.nx
+        self._check_point(B, Z, X0, lam, zl, zu)
         single = rz.dim() == 2
         if single:
             rz = rz.unsqueeze(1)
@@ -718,21 +702,10 @@ class CallbackEngine:
         self._check_in(rz, (B, k, self.n), "rz")
         if rg is not None:
             self._check_in(rg, (B, k, hx), "rg")
-        if self.rolling_window == 1:      # (a rolling-window handle is refused by the library, history bound or not)
-            self._check_extra(B)
-        self.reserve(B)
-        keep, ptrs = [], []
-        for a in (lb, ub):
-            if a is None:
-                ptrs.append(None)
-            else:
-                a, p = _as_c_double(np.broadcast_to(np.asarray(a, dtype=np.float64), (self.n,)))
-                keep.append(a)
-                ptrs.append(p)
+        B, point, keep = self._point(Z, X0, lam, zl, zu, lb, ub, checked=True)
         shapes = {"v": (B, k, self.n), "w": (B, k, hx), "gx0": (B, k, self.nx)}
         res = {key: torch.empty(shapes[key], dtype=self.dtype, device=self.device) for key in want}
         res["status"] = torch.empty(B, dtype=torch.int32, device=self.device)
-        opt = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         with torch.cuda.device(self.device):
             for c0 in range(0, k, 64):
                 c1 = min(k, c0 + 64)
@@ -741,10 +714,8 @@ class CallbackEngine:
                 rgc = None if rg is None else (rg.contiguous() if whole else rg[:, c0:c1].contiguous())
                 outs = {key: (res[key] if whole else torch.empty((B, c1 - c0) + shapes[key][2:], dtype=self.dtype, device=self.device))
                         for key in want}
-                _lib.check(self.lib.nempc_kkt_solve(self._handle, B, ctypes.c_void_p(Z.data_ptr()), ctypes.c_void_p(X0.data_ptr()),
-                                                    ctypes.c_void_p(lam.data_ptr()), opt(zl), opt(zu), ptrs[0], ptrs[1], c1 - c0,
-                                                    ctypes.c_void_p(rzc.data_ptr()), opt(rgc), opt(outs.get("v")), opt(outs.get("w")),
-                                                    opt(outs.get("gx0")), ctypes.c_void_p(res["status"].data_ptr()), self._stream()))
+                _lib.check(self.lib.nempc_kkt_solve(self._handle, B, *point, c1 - c0, _ptr(rzc), _ptr(rgc), _ptr(outs.get("v")),
+                                                    _ptr(outs.get("w")), _ptr(outs.get("gx0")), _ptr(res["status"]), self._stream()))
                 if not whole:
                     for key in want:
                         res[key][:, c0:c1] = outs[key]
