@@ -54,6 +54,7 @@ extern "C" {
 #define NEMPC_EHIP (-3)     /* a HIP runtime call failed */
 #define NEMPC_ESTATE (-4)   /* call order: weights / objective not set yet */
 #define NEMPC_EUNSUPPORTED (-5)
+#define NEMPC_EFULL (-6)    /* nempc_jac_dense_resident: the handle's table is full; not fatal, nothing changed */
 
 /* dtype */
 #define NEMPC_F64 0
@@ -248,6 +249,28 @@ int nempc_hess_structure(nempc_handle h, int32_t* rows, int32_t* cols);
  *   jac_sparse (B,nnz_jac)    values in nempc_jac_structure order */
 int nempc_eval(nempc_handle h, int32_t B, const void* Z, const void* X0, void* f, void* grad,
                void* g, void* jac_dense, void* jac_tiles, void* jac_sparse, void* stream);
+
+/* Declares jac -- (B,m,n) of the handle's dtype, device memory -- a RESIDENT dense-Jacobian buffer of this handle.
+ * Which entries of the dense Jacobian are structural zeros (98 % of them at H = 20, 2 states, 1 control) depends on the
+ * shape and the box rows only, and callers re-evaluate into the same buffer: the zeros need to be written once.
+ *   The call fills the buffer with zeros and returns when the fill is complete: it synchronises the device (a set-up
+ *   call, not for a captured stream); evaluations on any stream may follow without further ordering.
+ *   From then on nempc_eval(..., jac_dense == jac, ...) with at most B problems may write ONLY THE STRUCTURAL NON-ZEROS
+ *   (problems beyond the evaluated ones are not touched).  The results are those of the full-matrix path, bit for bit.
+ *   The one-launch evaluation of the compiled shapes and the assembly launch behind the generic, layered and
+ *   wave-per-tile rows do so; a writer that does not (the cooperative kernel's one-launch dense form) writes the full
+ *   matrix into a resident buffer as into any other.
+ *   CONTRACT: while the buffer is registered, nobody but nempc_eval of this handle writes it.  The caller may read it.
+ *   Unregister it (below) before freeing it or handing it to anyone who writes: the address may come back from the
+ *   allocator as somebody else's buffer.
+ *   B == 0 removes the registration of jac (a pointer that is not registered: NEMPC_OK, nothing happens).
+ *   The table holds 8 buffers per handle.  A ninth registration returns NEMPC_EFULL and changes nothing: not an error
+ *   (nempc_last_error is not set), the buffer simply stays on the full-matrix path.
+ *   nempc_set_box_rows (m and the pattern change) and nempc_destroy drop every registration of the handle.
+ *   A pointer that is not registered behaves as ever: the full matrix is written by every call.
+ *   NEMPC_JAC_RESIDENT=0 in the environment (read once per process) makes nempc_eval ignore the table (A/B switch).
+ * The ABI version stays 8: nothing existing changed. */
+int nempc_jac_dense_resident(nempc_handle h, void* jac, int32_t B);
 
 /* Lagrangian Hessian values, IpoptProblem.hessian ipopt.py:66-86:
  *   hvals (B,nnz_hess) = (sigma_b * d2f + sum_i lambda_{b,i} d2g_i)[rows, cols]

@@ -8,6 +8,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NEMPC_LIB") or os.path.join(PKG, "libnempc.so")
 
 ABI_VERSION = 8
+OK, EINVAL, EFULL = 0, -1, -6       # NEMPC_OK, NEMPC_EINVAL; NEMPC_EFULL: nempc_jac_dense_resident's table is full (not fatal)
 COMM_ID_BYTES = 128
 MAX_LAYERS = 8
 F64, F32 = 0, 1
@@ -43,6 +44,7 @@ def split_activation(spec):
 
 EXPORTS = ["nempc_create", "nempc_destroy", "nempc_reserve", "nempc_set_weights", "nempc_set_objective", "nempc_set_terminal_weight", "nempc_set_box_rows", "nempc_bind_extra", "nempc_bind_history",
            "nempc_bind_tracking", "nempc_bind_bounds",
+           "nempc_jac_dense_resident",
            "nempc_dims", "nempc_constraint_bounds", "nempc_jac_structure", "nempc_hess_structure", "nempc_eval",
            "nempc_hess", "nempc_hess_gn", "nempc_solve", "nempc_solve_duals", "nempc_kkt_residual", "nempc_sensitivity", "nempc_kkt_solve", "nempc_rollout", "nempc_last_rollout_kernel", "nempc_sync", "nempc_kernel_variant", "nempc_last_row_kernel", "nempc_last_hess_kernel", "nempc_last_error", "nempc_abi_version",
            "nempc_plan_grid", "nempc_num_cus",
@@ -98,6 +100,11 @@ def load():
     lib.nempc_bind_history.argtypes = [vp, vp, vp, i32]
     lib.nempc_bind_tracking.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_int64, ctypes.c_int64]
     lib.nempc_bind_bounds.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_int64, ctypes.c_int64]
+    # (an older library of the same ABI loaded through NEMPC_LIB -- the parent side of an A/B -- has no such export: the
+    # engine then registers nothing and every evaluation writes the full matrix, which is what that library does anyway)
+    have_resident = hasattr(lib, "nempc_jac_dense_resident")
+    if have_resident:
+        lib.nempc_jac_dense_resident.argtypes = [vp, vp, i32]
     lib.nempc_dims.argtypes = [vp, ip, ip, ip, ip]
     lib.nempc_constraint_bounds.argtypes = [vp, dp, dp]
     lib.nempc_jac_structure.argtypes = [vp, ip, ip]
@@ -127,7 +134,7 @@ def load():
     lib.nempc_last_error.restype = ctypes.c_char_p
     lib.nempc_abi_version.argtypes = []
     for name in EXPORTS:
-        if name != "nempc_last_error":
+        if name != "nempc_last_error" and (name != "nempc_jac_dense_resident" or have_resident):
             getattr(lib, name).restype = ctypes.c_int
     if lib.nempc_abi_version() != ABI_VERSION:
         raise RuntimeError("libnempc.so ABI version mismatch; rebuild it")

@@ -256,12 +256,13 @@ static MfmaParams base_params(Handle& h, int B, const void* Z, const void* X0, v
 // Whole hessian-free evaluation (g, dense jac, f, grad [, tiles]) in ONE launch where a fixed-shape kernel covers the
 // problem; NEMPC_EUNSUPPORTED (no error message, nothing launched) tells nempc_eval to take the two-launch path.
 int launch_eval_fused(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* jac, void* f,
-                      void* grad, hipStream_t s, void* sparse) {
+                      void* grad, hipStream_t s, void* sparse, bool jac_resident) {
     if (!h.mfma.blob || !h.d_obj || (!jac && !f && !grad && !sparse)) return NEMPC_EUNSUPPORTED;
     if (sparse && (h.w != 1 || jac)) return NEMPC_EUNSUPPORTED;
     MfmaParams p = base_params(h, B, Z, X0, g, tiles);
     p.fuse_obj = true;
     p.fuse_jac = jac; p.fuse_f = f; p.fuse_grad = grad;
+    p.jac_resident = jac && jac_resident;
     p.fuse_sparse = sparse; p.sp_nnz = (int)h.jac_rows.size();
     p.obj = h.d_obj;
     p.oo = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);

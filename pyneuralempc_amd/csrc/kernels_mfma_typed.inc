@@ -151,8 +151,13 @@ int launch_coopfx(const MfmaParams& p, hipStream_t s) {
     const unsigned pack = (unsigned)a.tiles_per_wg | ((unsigned)a.tiles_rem << 8) | ((unsigned)a.zp_max << 18) |
                           (a.f ? 1u << 28 : 0u) | (a.grad ? 1u << 29 : 0u) | ((a.tiles || a.jac || a.jac_sp || GN) ? 1u << 30 : 0u) |
                           (a.box ? 1u << 31 : 0u);
+    // pjac is the pointer the background zeros go to (the non-zeros go to a.jac, read in the epilogue).  A resident matrix
+    // (nempc_jac_dense_resident) holds its zeros already: the kernel is told there is no background to write.  Same kernel,
+    // same registers, no new argument; what is left of the background is the epilogue's vmcnt(0), which then finds only the
+    // next pass's input loads (waited for two lines further down anyway) and the previous pass's few stores outstanding.
+    void* const bg = FUSE && !p.jac_resident ? a.jac : nullptr;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MT * 64), bytes, s, a.Z, a.X0, a.small, a.wslice, a.P, pack, a.R, a.invH,
-                       (unsigned)a.H | ((unsigned)grid << 16), FUSE ? a.jac : nullptr, a);
+                       (unsigned)a.H | ((unsigned)grid << 16), bg, a);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
 }

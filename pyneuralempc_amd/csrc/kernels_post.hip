@@ -184,6 +184,28 @@ __global__ __launch_bounds__(256) void post_sparse_kernel(int nb_asm, int B, int
     vals[e] = map_value<T>(map[k], tiles + (size_t)b * tile_elems);
 }
 
+// dense contract into a RESIDENT matrix (nempc_jac_dense_resident: its structural zeros are in place): the same flat stream
+// over the structural non-zeros, each value to its place in the problem's dense matrix (pos[k] = row * n + col); the
+// objective on the blocks after them when it is asked for.
+template <typename T>
+__global__ __launch_bounds__(256) void post_scatter_kernel(int nb_asm, int B, int nnz, unsigned long long magic64, int mn,
+                                                           int tile_elems, const int32_t* __restrict__ map,
+                                                           const int32_t* __restrict__ pos, const T* __restrict__ tiles,
+                                                           T* __restrict__ jac, int H, int nx, int nu, ObjOffsets o,
+                                                           const T* __restrict__ P, const T* __restrict__ Z,
+                                                           T* __restrict__ f, T* __restrict__ grad) {
+    if ((int)blockIdx.x >= nb_asm) {
+        const int b = ((int)blockIdx.x - nb_asm) * 4 + (threadIdx.x >> 6);
+        if (b < B) objective_body<T>(b, threadIdx.x & 63, H, nx, nu, o, P, Z, f, grad);
+        return;
+    }
+    const unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (unsigned long long)B * nnz) return;
+    const unsigned b = (unsigned)__umul64hi(e, magic64);      // e / nnz, exact for e * nnz < 2^64
+    const unsigned k = (unsigned)(e - (unsigned long long)b * nnz);
+    jac[(size_t)b * mn + pos[k]] = map_value<T>(map[k], tiles + (size_t)b * tile_elems);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void assemble_sparse_kernel(int nnz, int tile_elems, const int32_t* __restrict__ map,
                                                               const T* __restrict__ tiles, T* __restrict__ vals) {
@@ -284,7 +306,26 @@ int launch_post_flat(Handle& h, int B, unsigned magic, const void* tiles, void* 
     return NEMPC_OK;
 }
 
-int launch_assemble_dense(Handle& h, int B, const void* tiles, void* jac, hipStream_t s) {
+// the structural non-zeros of the dense matrix alone, [+ the objective]: the target is resident (post_scatter_kernel)
+template <typename T>
+int launch_post_scatter(Handle& h, int B, const void* tiles, void* jac, const void* Z, void* f, void* grad, hipStream_t s) {
+    const int nnz = (int)h.jac_rows.size();
+    const int te = h.cfg.H * h.cfg.nx * h.nin;
+    const unsigned long long total = (unsigned long long)B * nnz;
+    const int nb_asm = (int)((total + 255) / 256), nb_obj = (f || grad) ? (B + 3) / 4 : 0;
+    const unsigned long long magic = ~0ull / (unsigned long long)nnz + 1;      // (as launch_post_sparse)
+    ObjOffsets o = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
+    hipLaunchKernelGGL(post_scatter_kernel<T>, dim3((unsigned)(nb_asm + nb_obj)), dim3(256), 0, s, nb_asm, B, nnz, magic,
+                       h.m * h.n, te, h.d_sparse_map, h.d_sparse_pos, (const T*)tiles, (T*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
+                       (const T*)h.d_obj, (const T*)Z, (T*)f, (T*)grad);
+    NEMPC_HIP(hipGetLastError());
+    return NEMPC_OK;
+}
+
+int launch_assemble_dense(Handle& h, int B, const void* tiles, void* jac, hipStream_t s, bool resident) {
+    if (resident)
+        return h.cfg.dtype == NEMPC_F64 ? launch_post_scatter<double>(h, B, tiles, jac, nullptr, nullptr, nullptr, s)
+                                        : launch_post_scatter<float>(h, B, tiles, jac, nullptr, nullptr, nullptr, s);
     unsigned magic = 0;
     if (flat_ok(h, B, jac, &magic))
         return h.cfg.dtype == NEMPC_F64 ? launch_post_flat<double>(h, B, magic, tiles, jac, nullptr, nullptr, nullptr, s)
@@ -303,7 +344,11 @@ int launch_assemble_dense(Handle& h, int B, const void* tiles, void* jac, hipStr
     return NEMPC_OK;
 }
 
-int launch_post(Handle& h, int B, const void* tiles, void* jac, const void* Z, void* f, void* grad, hipStream_t s) {
+int launch_post(Handle& h, int B, const void* tiles, void* jac, const void* Z, void* f, void* grad, hipStream_t s,
+                bool resident) {
+    if (resident)
+        return h.cfg.dtype == NEMPC_F64 ? launch_post_scatter<double>(h, B, tiles, jac, Z, f, grad, s)
+                                        : launch_post_scatter<float>(h, B, tiles, jac, Z, f, grad, s);
     unsigned magic = 0;
     if (flat_ok(h, B, jac, &magic))
         return h.cfg.dtype == NEMPC_F64 ? launch_post_flat<double>(h, B, magic, tiles, jac, Z, f, grad, s)

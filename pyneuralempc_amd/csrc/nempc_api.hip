@@ -107,7 +107,9 @@ int rebuild_structure(Handle& h) {
     const int H = h.cfg.H, nx = h.cfg.nx, nu = h.cfg.nu, nin = h.nin, n = h.n;
     h.m = H * nx + (h.box ? H * nx : 0);
     const int m = h.m;
-    std::vector<int32_t> dense((size_t)m * n, MAP_ZERO), sparse;
+    // the dense map changes: a resident dense Jacobian of the old shape holds non-zeros where the new one has none
+    h.jac_resident.drop_all();
+    std::vector<int32_t> dense((size_t)m * n, MAP_ZERO), sparse, pos;
     h.jac_rows.clear();
     h.jac_cols.clear();
     auto put = [&](int r, int c, int32_t code) {
@@ -115,6 +117,7 @@ int rebuild_structure(Handle& h) {
         h.jac_rows.push_back(r);
         h.jac_cols.push_back(c);
         sparse.push_back(code);
+        pos.push_back(r * n + c);
     };
     std::vector<std::pair<int, int32_t>> ent;
     for (int t = 0; t < H; ++t)
@@ -135,13 +138,16 @@ int rebuild_structure(Handle& h) {
 
     dev_free(h.d_dense_map);
     dev_free(h.d_sparse_map);
+    dev_free(h.d_sparse_pos);
     dev_free(h.d_g_ws);
     int rc;
     if ((rc = dev_alloc(&h.d_dense_map, dense.size() * sizeof(int32_t)))) return rc;
     if ((rc = dev_alloc(&h.d_sparse_map, sparse.size() * sizeof(int32_t)))) return rc;
+    if ((rc = dev_alloc(&h.d_sparse_pos, pos.size() * sizeof(int32_t)))) return rc;
     if ((rc = dev_alloc(&h.d_g_ws, (size_t)h.cfg.max_batch * m * h.esz))) return rc;
     NEMPC_HIP(hipMemcpy(h.d_dense_map, dense.data(), dense.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     NEMPC_HIP(hipMemcpy(h.d_sparse_map, sparse.data(), sparse.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    NEMPC_HIP(hipMemcpy(h.d_sparse_pos, pos.data(), pos.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     return NEMPC_OK;
 }
 
@@ -281,6 +287,7 @@ void destroy_impl(Handle* h) {
     dev_free(h->d_obj);
     dev_free(h->d_dense_map);
     dev_free(h->d_sparse_map);
+    dev_free(h->d_sparse_pos);
     dev_free(h->d_hess_map);
     dev_free(h->d_hess_smap);
     dev_free(h->d_tiles_ws);
@@ -557,6 +564,7 @@ int nempc_destroy(nempc_handle hh) {
     if (!hh) return NEMPC_OK;
     Handle* h = reinterpret_cast<Handle*>(hh);
     DeviceGuard dg(h->cfg.device);
+    h->jac_resident.drop_all();
     destroy_impl(h);
     return NEMPC_OK;
 }
@@ -691,6 +699,27 @@ int nempc_set_box_rows(nempc_handle hh, int enabled, const double* lo, const dou
     return rebuild_structure(h);
 }
 
+int nempc_jac_dense_resident(nempc_handle hh, void* jac, int32_t B) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_jac_dense_resident: null handle");
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    if (B < 0 || B > h.cfg.max_batch) return fail(NEMPC_EINVAL, "nempc_jac_dense_resident: B outside [0, max_batch]");
+    if (B == 0) {                     // removal; a pointer the table does not hold is not an error
+        h.jac_resident.remove(jac);
+        return NEMPC_OK;
+    }
+    if (!jac) return fail(NEMPC_EINVAL, "nempc_jac_dense_resident: jac is null");
+    if (!h.jac_resident.find(jac) && h.jac_resident.count() == kJacResidentSlots) return NEMPC_EFULL;   // (no message: not an error)
+    DeviceGuard dg(h.cfg.device);
+    if (!dg.ok) return fail(NEMPC_EHIP, "nempc_jac_dense_resident: hipSetDevice failed");
+    // a set-up call: whatever still runs on any stream is over before the fill, and the fill before the call returns
+    h.jac_resident.remove(jac);
+    NEMPC_HIP(hipDeviceSynchronize());
+    NEMPC_HIP(hipMemset(jac, 0, (size_t)B * h.m * h.n * h.esz));
+    NEMPC_HIP(hipDeviceSynchronize());
+    h.jac_resident.add(jac, B);
+    return NEMPC_OK;
+}
+
 int nempc_dims(nempc_handle hh, int32_t* n, int32_t* m, int32_t* nnz_jac, int32_t* nnz_hess) {
     if (!hh) return fail(NEMPC_EINVAL, "nempc_dims: null handle");
     Handle& h = *reinterpret_cast<Handle*>(hh);
@@ -751,6 +780,9 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
     DeviceGuard dg(h.cfg.device);
     if (!dg.ok) return fail(NEMPC_EHIP, "nempc_eval: hipSetDevice failed");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // a resident dense Jacobian (nempc_jac_dense_resident) has its structural zeros in place: the writers below leave them
+    static const int resident_on = env_int("NEMPC_JAC_RESIDENT", 1);
+    const bool jres = jac_dense && resident_on && h.jac_resident.resident(jac_dense, B);
     auto then_tracking = [&](int r) { return r == NEMPC_OK && trk ? launch_objective_tracking(h, B, Z, f, grad, nullptr, s) : r; };
     int rc;
     if (need_rows) {
@@ -761,7 +793,7 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
         // compiled shape: rows, objective and (dense contract) the dense assembly in ONE launch; without a derivative
         // output (g with f / grad: what a line-search trial needs) the same launch runs its forward passes only
         if (!jac_sparse && (jac_dense || ff || gf) && h.variant == NEMPC_KERNEL_MFMA) {
-            rc = launch_eval_fused(h, B, Z, X0, gout, jac_tiles, jac_dense, ff, gf, s);
+            rc = launch_eval_fused(h, B, Z, X0, gout, jac_tiles, jac_dense, ff, gf, s, nullptr, jres);
             if (rc != NEMPC_EUNSUPPORTED) return then_tracking(rc);
         }
         // sparse contract (what a real Ipopt run wants: SURVEY 8f-2; the reference hands cyipopt the dense (m, n),
@@ -777,6 +809,8 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
         // dense contract on any shape the cooperative kernel takes (plain models): the dense rows AND the objective leave
         // from the row launch itself -- no assembly launch, no tile round trip through memory, no objective launch
         if (jac_dense && !jac_sparse && h.variant == NEMPC_KERNEL_MFMA) {
+            // (a resident matrix gets its zeros from this launch all the same: correct, and measured not worth a flag in
+            // rows_coop_kernel -- DESIGN 5.2)
             rc = launch_rows_mfma_dense(h, B, Z, X0, gout, jac_tiles, jac_dense, ff, gf, s);
             if (rc != NEMPC_EUNSUPPORTED) return then_tracking(rc);
         }
@@ -786,8 +820,8 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
         // sparse contract with the objective and without the dense matrix: one fused launch
         if (jac_sparse && !jac_dense && (ff || gf)) return launch_post_sparse(h, B, tiles, jac_sparse, Z, ff, gf, s);
         if (jac_sparse && (rc = launch_assemble_sparse(h, B, tiles, jac_sparse, s))) return rc;
-        if (jac_dense && (ff || gf)) return launch_post(h, B, tiles, jac_dense, Z, ff, gf, s);
-        if (jac_dense && (rc = launch_assemble_dense(h, B, tiles, jac_dense, s))) return rc;
+        if (jac_dense && (ff || gf)) return launch_post(h, B, tiles, jac_dense, Z, ff, gf, s, jres);
+        if (jac_dense && (rc = launch_assemble_dense(h, B, tiles, jac_dense, s, jres))) return rc;
     }
     if ((f || grad) && (rc = launch_objective(h, B, Z, f, grad, s))) return rc;
     return NEMPC_OK;

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "jac_resident.h"
 #include "nempc.h"
 
 namespace nempc {
@@ -207,6 +208,8 @@ struct Handle {
     std::vector<int32_t> jac_rows, jac_cols, hess_rows, hess_cols;
     int32_t* d_dense_map = nullptr;   // (m*n)
     int32_t* d_sparse_map = nullptr;  // (nnz_jac)
+    int32_t* d_sparse_pos = nullptr;  // (nnz_jac) where each structural non-zero sits in one problem's dense matrix: row * n + col
+    JacResidentTable jac_resident;    // dense-Jacobian buffers whose structural zeros are in place (nempc_jac_dense_resident)
     int32_t* d_hess_map = nullptr;    // (nnz_hess + n*n, w) per-row block elements summed into each entry; -1 = none
     int32_t* d_hess_smap = nullptr;   // plain models: (H*nin*nin) block element -> tril entry (-1 none), then the entries no
     int hess_n_orph = -1;             //   block reaches (hess_n_orph of them; -1: no fused assembly for this handle)
@@ -299,7 +302,7 @@ bool mfma_hess_on_layered(const Handle& h);        // AUTO: rows on the register
 int mfma_pack_weights(Handle& h, const double* const* W, const double* const* b);
 int launch_rows_mfma(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, hipStream_t s);
 int launch_eval_fused(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* jac, void* f,
-                      void* grad, hipStream_t s, void* sparse = nullptr);
+                      void* grad, hipStream_t s, void* sparse = nullptr, bool jac_resident = false);
 int launch_rows_mfma_sparse(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* sparse, void* f,
                             void* grad, hipStream_t s);
 int launch_rows_mfma_dense(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* jac, void* f,
@@ -332,9 +335,11 @@ int launch_objective(Handle& h, int B, const void* Z, void* f, void* grad, hipSt
 int launch_objective_tracking(Handle& h, int B, const void* Z, void* f, void* grad, const int* prob, hipStream_t s);
 int launch_assemble_hess_gn(Handle& h, int B, const void* tiles, const void* w, const void* sigma, void* hvals, void* hdense,
                             hipStream_t s);
-int launch_assemble_dense(Handle& h, int B, const void* tiles, void* jac, hipStream_t s);
+// resident: jac's structural zeros are in place (nempc_jac_dense_resident), only the non-zeros are written
+int launch_assemble_dense(Handle& h, int B, const void* tiles, void* jac, hipStream_t s, bool resident = false);
 int launch_assemble_sparse(Handle& h, int B, const void* tiles, void* vals, hipStream_t s);
-int launch_post(Handle& h, int B, const void* tiles, void* jac, const void* Z, void* f, void* grad, hipStream_t s);
+int launch_post(Handle& h, int B, const void* tiles, void* jac, const void* Z, void* f, void* grad, hipStream_t s,
+                bool resident = false);
 int launch_post_sparse(Handle& h, int B, const void* tiles, void* vals, const void* Z, void* f, void* grad,
                        hipStream_t s);
 int launch_assemble_hess(Handle& h, int B, const void* blocks, const void* sigma, void* hvals, void* hdense,

@@ -100,6 +100,7 @@ class CallbackEngine:
     # ------------------------------------------------------------------ handle management
     def _create(self, max_batch):
         self._destroy()
+        self._buffers = {}          # (their registrations went with the handle)
         cfg = _lib.NempcConfig()
         cfg.abi_version = _lib.ABI_VERSION
         cfg.device = self.device.index
@@ -168,7 +169,7 @@ class CallbackEngine:
         if B > self.max_batch:
             _lib.check(self.lib.nempc_reserve(self._handle, int(B)))
             self.max_batch = int(B)
-            self._buffers = {}
+            self._drop_buffers()
 
     @property
     def kernel_variant(self):
@@ -322,6 +323,7 @@ class CallbackEngine:
             raise ValueError("You must give history window with set_prev_data before calling any inferance function.")
 
     def set_box_rows(self, lo, hi):
+        self._drop_buffers()        # m changes: the next evaluation allocates (and registers) afresh
         if lo is None:
             _lib.check(self.lib.nempc_set_box_rows(self._handle, 0, None, None))
             self._box = None
@@ -331,7 +333,6 @@ class CallbackEngine:
             _lib.check(self.lib.nempc_set_box_rows(self._handle, 1, pa, pb))
             self._box = (lo, hi)
         self._refresh_dims()
-        self._buffers = {}
 
     # ------------------------------------------------------------------ structure / bounds (host)
     def constraint_bounds(self):
@@ -367,7 +368,26 @@ class CallbackEngine:
         if buf is None:
             buf = torch.empty(shape, dtype=self.dtype, device=self.device)
             self._buffers[key] = buf
+            if name == "jac_dense":
+                # the engine's own dense Jacobian is written by nempc_eval of this handle and by nobody else: a resident
+                # buffer (nempc_jac_dense_resident zero-fills it now; the evaluations write the structural non-zeros only).
+                # A full table or a failed registration leaves it on the full-matrix path, which is correct as well.
+                fn = getattr(self.lib, "nempc_jac_dense_resident", None)
+                if fn is not None:
+                    with torch.cuda.device(self.device):
+                        fn(self._handle, ctypes.c_void_p(buf.data_ptr()), int(shape[0]))
         return buf
+
+    def _drop_buffers(self):
+        """Forget the reusable output tensors.  A registered dense Jacobian is unregistered first: once the tensor is gone
+        the allocator may hand its address to somebody else, and a registration left behind would let an evaluation
+        into that address skip the zeros."""
+        fn = getattr(self.lib, "nempc_jac_dense_resident", None)
+        if fn is not None and self._handle:
+            for (name, _), buf in self._buffers.items():
+                if name == "jac_dense":
+                    fn(self._handle, ctypes.c_void_p(buf.data_ptr()), 0)
+        self._buffers = {}
 
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -376,7 +396,10 @@ class CallbackEngine:
         """One batched callback evaluation.  Z (B,n), X0 (B,nx) device tensors.  Returns a dict with
         the requested outputs (device tensors, reused between calls unless `out` supplies them):
         f (B,), grad (B,n), g (B,m), jac_dense (B,m,n), jac_tiles (B,H,nx,w*(nx+nu)), jac_sparse (B,nnz_jac).
-        Asynchronous on the current torch stream."""
+        Asynchronous on the current torch stream.
+        The engine's own output tensors are READ-ONLY for the caller: its jac_dense is a resident buffer whose structural
+        zeros are written once, when it is created, and every evaluation writes the non-zeros only -- whatever a caller
+        writes into it stays there.  Tensors passed through `out` are the caller's: they get the full matrix every call."""
         B = int(Z.shape[0])
         self._check_in(Z, (B, self.n), "Z")
         self._check_in(X0, (B, self.nx), "X0")
@@ -406,7 +429,9 @@ class CallbackEngine:
         """Pre-validated evaluation for hot loops: returns (launch, outputs) where launch() re-evaluates the
         callbacks at the CURRENT contents of Z / X0 into the fixed `outputs` tensors (caller-supplied through `out`,
         else the engine's reusable buffers) with one ctypes call (no per-call allocation or checking).  Valid while
-        Z, X0 and the outputs stay alive and the workspaces are not re-sized (reserve / set_box_rows)."""
+        Z, X0 and the outputs stay alive and the workspaces are not re-sized (reserve / set_box_rows).
+        As with eval, outputs the engine owns are read-only for the caller; outputs passed through `out` may be
+        overwritten between launches (each launch rewrites them in full)."""
         B = int(Z.shape[0])
         res = self.eval(Z, X0, want, out=out)             # validates, allocates outputs, warms the kernels
         ptr = {k: (ctypes.c_void_p(res[k].data_ptr()) if k in res else None)

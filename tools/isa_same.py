@@ -19,7 +19,8 @@ def pieces(path, maps):
     body, meta = text.split("\t.amdgpu_metadata\n")
     out = {}
     body, _, out["tail"] = body.partition("\t.section\t.AMDGPU.gpr_maximums")      # (what follows the last kernel)
-    for chunk in re.split(r"\n(?=\t\.section\t\.text\.\S+\n\t\.globl\t)", body)[1:]:
+    # (a kernel's section line is followed by .globl, or -- template kernels, comdat -- by a .protected line first)
+    for chunk in re.split(r"\n(?=\t\.section\t\.text\.\S+\n(?:\t\.protected\t[^\n]*\n)?\t\.globl\t)", "\n" + body)[1:]:
         seen = {}           # labels numbered through the whole file (long-branch targets): by appearance inside the kernel instead
         chunk = re.sub(r"(\.Lpost_getpc)(\d+)", lambda m: m.group(1) + str(seen.setdefault(m.group(2), len(seen))), chunk)
         out["code " + re.search(r"\.globl\t(\S+)", chunk).group(1)] = chunk
