@@ -515,6 +515,11 @@ int nempc_last_row_kernel(nempc_handle h);
  * sum: integrator/rk4.py:181-285); 0 = none yet */
 int nempc_last_hess_kernel(nempc_handle h);
 
+/* LQ kernel the handle's most recent nempc_solve planned for its iterations: 1 thread per problem, working set in global
+ * memory (it does not fit the LDS budget; a requested wave or scan kernel ends here too), 2 thread per problem, working set
+ * staged in LDS, 3 wave per problem in LDS, 4 parallel-in-time scan (2-state / 1-control stages, fp64); 0 = none yet */
+int nempc_last_lq_kernel(nempc_handle h);
+
 const char* nempc_last_error(void);
 int nempc_abi_version(void);
 

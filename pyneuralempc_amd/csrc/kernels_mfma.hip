@@ -65,6 +65,11 @@ bool mfma_supported(const Handle& h) {
     // network outputs on one 16-row block; inputs (window + extras) on up to kMaxKs k-steps, the window itself on up
     // to two 16-row blocks of the last reverse step (wave-per-tile kernels; the cooperative ones take <= 16)
     if (h.cfg.nx > 16 || h.nin + h.ne > 4 * kMaxKs || h.nin > 32) return false;
+    // one wave's scratch is the least LDS any row kernel asks for (the streamed wave-per-tile kernel with one wave per
+    // workgroup); with the RK4 chain's four Jacobian slots an fp64 16-state / 20-input stage needs 168.5 KiB, more than the
+    // CU's 160 KiB, and every launch of it was refused (hipFuncSetAttribute: invalid argument) -- such shapes are not ours
+    const size_t esz = h.cfg.dtype == NEMPC_F64 ? sizeof(double) : sizeof(float);
+    if ((size_t)((scratch_elems(h) + 1) & ~1) * esz > (size_t)160 * 1024) return false;
     return padded_width(h) != 0;
 }
 

@@ -1039,6 +1039,11 @@ int nempc_last_hess_kernel(nempc_handle hh) {
     return reinterpret_cast<Handle*>(hh)->last_hess_kernel;
 }
 
+int nempc_last_lq_kernel(nempc_handle hh) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_last_lq_kernel: null handle");
+    return reinterpret_cast<Handle*>(hh)->last_lq_kernel;
+}
+
 int nempc_last_row_kernel(nempc_handle hh) {
     if (!hh) return fail(NEMPC_EINVAL, "nempc_last_row_kernel: null handle");
     return reinterpret_cast<Handle*>(hh)->last_row_kernel;

@@ -38,6 +38,7 @@
 //     solver_args.h          INFO_* columns, SolverArgs, StepInfo, LQ_STAMP: the contract between driver and kernels
 //     bounds_bind_impl.h     per-problem bounds (nempc_bind_bounds): what the binding says about one variable (shared with kernels_post / kernels_sens)
 //     solver_ipm_impl.h      bounds: barrier terms, dual steps, barrier value, interior start (solver_init_kernel, solver_init_bound_kernel)
+//     solver_soc_impl.h      second-order correction: the state recursion (host / device, nothing of HIP: tests/soc_check.cpp)
 //     solver_merit_impl.h    convergence test, merit, trial point, acceptance, second-order correction
 //     solver_lq_scan_impl.h  LQ solve parallel in time (2/1 stages)
 //     solver_lq_impl.h       LQ solve, thread per problem: staging, Riccati sweep, post-pass
@@ -59,6 +60,7 @@
 #include "solver_args.h"
 #include "bounds_bind_impl.h"
 #include "solver_ipm_impl.h"
+#include "solver_soc_impl.h"
 #include "solver_merit_impl.h"
 #include "solver_lq_scan_impl.h"
 #include "solver_lq_impl.h"
@@ -461,6 +463,8 @@ struct Solve {
                                             : ((nx == 6 && nu == 3) ? solver_lqw_kernel<T, 6, 3> : solver_lqw_kernel<T, 0, 0>);
         if constexpr (sizeof(T) == 8)
             if (lq_scan && a.use_lds && !lq_wave) lqk = solver_lq_kernel<T, 2, 1, true, true>;
+        // what ran, for nempc_last_lq_kernel: a forced wave (or scan) kernel whose working set does not fit is plan 1
+        h.last_lq_kernel = !a.use_lds ? 1 : (lq_wave ? 3 : (sizeof(T) == 8 && lq_scan ? 4 : 2));
         const size_t lds_max = a.use_lds ? lds_bytes(std::min(std::max(max_ppw(), 1), 16)) : 0;
         NEMPC_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lqk), lds_max));
         return NEMPC_OK;
@@ -771,7 +775,7 @@ struct Solve {
                 // rejected problems, accepted at the rejected trial's step length; what is still rejected backtracks as before
                 const int* lin = ws.pend[(1 + pflip) & 1];
                 int* lout = ws.pend[pflip & 1];
-                hipLaunchKernelGGL(solver_soc_kernel<T>, dim3(pending), dim3(64), 0, s, n, nx, nu, H, m, (int)ex_per, lin, (const T*)ws.Zt,
+                hipLaunchKernelGGL(solver_soc_kernel<T>, dim3(pending), dim3(64), (size_t)2 * nx * sizeof(T), s, n, nx, nu, H, m, (int)ex_per, lin, (const T*)ws.Zt,
                                    (const T*)ws.gt, (const T*)ws.tiles, (const T*)X0c, (const T*)extra_all, (T*)ws.Zsoc, (T*)ws.X0p,
                                    (T*)ws.exp_, a.n_pending);
                 if (ex_per) h.d_extra = ws.exp_;

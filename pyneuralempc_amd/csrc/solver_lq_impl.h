@@ -24,6 +24,17 @@ __device__ __forceinline__ float inv_sqrt_pos(float d) {
     return fmaf(0.5f * y, r, y);
 }
 
+// Accumulator of the sweeps' sums (products of the value function, the tiles and the steps; shared with solver_lqw_impl.h).
+// Stages whose dimensions are compile-time constants sum 2 .. 6 terms per entry and keep T.  The run-time-dimension
+// instantiation serves the wide stages, where an entry is a sum over up to nx terms: in fp32 at 64 states that sum alone
+// lost more than ten times what a NumPy float32 sweep loses on the same step (the rows 64x8_fp32 of
+// tests/solver_step_cases.py missed their tolerances by 1.28 and 1.11; a CPU float32 replay of the kernel's order reproduces
+// the device's figures to three digits), so there it runs in double and is rounded to T once per entry.  T = double: no change.
+template <typename T, int NX> struct LqAcc { using type = T; };
+template <> struct LqAcc<float, 0> { using type = double; };
+template <typename A, typename T>
+__device__ __forceinline__ A lq_fma(T x, T y, A acc) { return fma((A)x, (A)y, acc); }
+
 // One thread per problem.  The sweep is a long chain of tiny dependent matrix products: straight from global
 // memory every operand costs a ~600-cycle round trip (measured 720 us per call at B=1024, 2/1, H=20).  So a
 // workgroup first copies the whole working set of its `ppw` problems (iterate, gradient, defects, tiles,
@@ -40,6 +51,7 @@ __global__ __launch_bounds__(256) void solver_lq_kernel(SolverArgs a) {
     T* lds = reinterpret_cast<T*>(lds_raw);
     const int lane = threadIdx.x;
     constexpr bool FIX = NX > 0;
+    using Acc = typename LqAcc<T, NX>::type;
     const int H = a.H, nx = FIX ? NX : a.nx, nu = FIX ? NU : a.nu, nin = nx + nu, n = a.n;
     const int ppw = LDS ? a.ppw : 64;
     const int spec = LDS ? a.spec : 1;
@@ -314,21 +326,24 @@ __global__ __launch_bounds__(256) void solver_lq_kernel(SolverArgs a) {
             if (t > 0 || FIX)     // (fixed shapes: unconditional -- a guard turns into a select per entry and stage)
                 #pragma unroll
                 for (int j = 0; j < nx; ++j) {
-                    T v = T(0);
+                    Acc v_acc = T(0);
                     #pragma unroll
-                    for (int k = 0; k < nx; ++k) v = fma(TMP(oP + i * nx + k), AT(k * nin + j), v);
+                    for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(TMP(oP + i * nx + k), AT(k * nin + j), v_acc);
+                    const T v = (T)v_acc;
                     TMP(oPA + i * nx + j) = v;
                 }
             #pragma unroll
             for (int j = 0; j < nu; ++j) {
-                T v = T(0);
+                Acc v_acc = T(0);
                 #pragma unroll
-                for (int k = 0; k < nx; ++k) v = fma(TMP(oP + i * nx + k), AT(k * nin + nx + j), v);
+                for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(TMP(oP + i * nx + k), AT(k * nin + nx + j), v_acc);
+                const T v = (T)v_acc;
                 TMP(oPB + i * nu + j) = v;
             }
-            T v = TMP(op + i);
+            Acc v_acc = TMP(op + i);
             #pragma unroll
-            for (int k = 0; k < nx; ++k) v = fma(TMP(oP + i * nx + k), GC(k), v);
+            for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(TMP(oP + i * nx + k), GC(k), v_acc);
+            const T v = (T)v_acc;
             TMP(oPc + i) = v;
         }
         // Quu = Rs + barrier + reg + B' PB ; qu = gu + barrier + B' Pc ; Qux = B' PA
@@ -338,21 +353,24 @@ __global__ __launch_bounds__(256) void solver_lq_kernel(SolverArgs a) {
             ha = BHU(i);
             #pragma unroll
             for (int j = 0; j < nu; ++j) {
-                T v = RS(i * nu + j) + WT((nx + i) * nin + nx + j) + (i == j ? ha + reg : T(0));
+                Acc v_acc = RS(i * nu + j) + WT((nx + i) * nin + nx + j) + (i == j ? ha + reg : T(0));
                 #pragma unroll
-                for (int k = 0; k < nx; ++k) v = fma(AT(k * nin + nx + i), TMP(oPB + k * nu + j), v);
+                for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(AT(k * nin + nx + i), TMP(oPB + k * nu + j), v_acc);
+                const T v = (T)v_acc;
                 TMP(oQuu + i * nu + j) = v;
             }
-            T v = GRU(i);
+            Acc v_acc = GRU(i);
             #pragma unroll
-            for (int k = 0; k < nx; ++k) v = fma(AT(k * nin + nx + i), TMP(oPc + k), v);
+            for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(AT(k * nin + nx + i), TMP(oPc + k), v_acc);
+            const T v = (T)v_acc;
             TMP(oqu + i) = v;
             if (t > 0 || FIX)     // (fixed shapes: unconditional -- a guard turns into a select per entry and stage)
                 #pragma unroll
                 for (int j = 0; j < nx; ++j) {
-                    T w = WT((nx + i) * nin + j);
+                    Acc w_acc = WT((nx + i) * nin + j);
                     #pragma unroll
-                    for (int k = 0; k < nx; ++k) w = fma(AT(k * nin + nx + i), TMP(oPA + k * nx + j), w);
+                    for (int k = 0; k < nx; ++k) w_acc = lq_fma<Acc>(AT(k * nin + nx + i), TMP(oPA + k * nx + j), w_acc);
+                    const T w = (T)w_acc;
                     TMP(oQux + i * nx + j) = w;
                 }
         }
@@ -408,18 +426,20 @@ __global__ __launch_bounds__(256) void solver_lq_kernel(SolverArgs a) {
                 ha = BHX(i);
                 #pragma unroll
                 for (int j = 0; j < nx; ++j) {
-                    T v = QS(i * nx + j) + WT(i * nin + j) + (i == j ? ha : T(0));
+                    Acc v_acc = QS(i * nx + j) + WT(i * nin + j) + (i == j ? ha : T(0));
                     #pragma unroll
-                    for (int k = 0; k < nx; ++k) v = fma(AT(k * nin + i), TMP(oPA + k * nx + j), v);
+                    for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(AT(k * nin + i), TMP(oPA + k * nx + j), v_acc);
                     #pragma unroll
-                    for (int k = 0; k < nu; ++k) v = fma(TMP(oQux + k * nx + i), TMP(oK + k * nx + j), v);
+                    for (int k = 0; k < nu; ++k) v_acc = lq_fma<Acc>(TMP(oQux + k * nx + i), TMP(oK + k * nx + j), v_acc);
+                    const T v = (T)v_acc;
                     TMP(oPn + i * nx + j) = v;
                 }
-                T v = GRX(i);
+                Acc v_acc = GRX(i);
                 #pragma unroll
-                for (int k = 0; k < nx; ++k) v = fma(AT(k * nin + i), TMP(oPc + k), v);
+                for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(AT(k * nin + i), TMP(oPc + k), v_acc);
                 #pragma unroll
-                for (int k = 0; k < nu; ++k) v = fma(TMP(oQux + k * nx + i), TMP(okv + k), v);
+                for (int k = 0; k < nu; ++k) v_acc = lq_fma<Acc>(TMP(oQux + k * nx + i), TMP(okv + k), v_acc);
+                const T v = (T)v_acc;
                 TMP(opn + i) = v;
             }
             #pragma unroll
@@ -545,27 +565,30 @@ __global__ __launch_bounds__(256) void solver_lq_kernel(SolverArgs a) {
         const T* At = tl + (size_t)t * nx * nin;
         #pragma unroll
         for (int i = 0; i < nu; ++i) {
-            T v = kst[(size_t)t * nu + i];
+            Acc v_acc = kst[(size_t)t * nu + i];
             if (t > 0)
                 #pragma unroll
-                for (int k = 0; k < nx; ++k) v = fma(Kst[(size_t)t * nu * nx + i * nx + k], TMP(odx + k), v);
+                for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(Kst[(size_t)t * nu * nx + i * nx + k], TMP(odx + k), v_acc);
+            const T v = (T)v_acc;
             TMP(odu + i) = v;
         }
         #pragma unroll
         for (int i = 0; i < nx; ++i) {
-            T v = gc[t * nx + i];
+            Acc v_acc = gc[t * nx + i];
             if (t > 0)
                 #pragma unroll
-                for (int k = 0; k < nx; ++k) v = fma(At[i * nin + k], TMP(odx + k), v);
+                for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(At[i * nin + k], TMP(odx + k), v_acc);
             #pragma unroll
-            for (int k = 0; k < nu; ++k) v = fma(At[i * nin + nx + k], TMP(odu + k), v);
+            for (int k = 0; k < nu; ++k) v_acc = lq_fma<Acc>(At[i * nin + nx + k], TMP(odu + k), v_acc);
+            const T v = (T)v_acc;
             TMP(odxn + i) = v;
         }
         #pragma unroll
         for (int i = 0; i < nx; ++i) {
-            T lam = pst[(size_t)t * nx + i];
+            Acc lam_acc = pst[(size_t)t * nx + i];
             #pragma unroll
-            for (int k = 0; k < nx; ++k) lam = fma(Pst[(size_t)t * nx * nx + i * nx + k], TMP(odxn + k), lam);
+            for (int k = 0; k < nx; ++k) lam_acc = lq_fma<Acc>(Pst[(size_t)t * nx * nx + i * nx + k], TMP(odxn + k), lam_acc);
+            const T lam = (T)lam_acc;
             lamn[t * nx + i] = lam;
             const T d = TMP(odxn + i);
             dz[t * nx + i] = d;

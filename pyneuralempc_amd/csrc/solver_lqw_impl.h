@@ -14,6 +14,7 @@ namespace {
 template <typename T, int NX, int NU>
 __global__ __launch_bounds__(256) void solver_lqw_kernel(SolverArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    using Acc = typename LqAcc<T, NX>::type;       // (the sums' accumulator: solver_lq_impl.h)
     T* lds = reinterpret_cast<T*>(lds_raw);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int H = a.H, nx = NX > 0 ? NX : a.nx, nu = NX > 0 ? NU : a.nu, nin = nx + nu, n = a.n;
@@ -131,8 +132,9 @@ __global__ __launch_bounds__(256) void solver_lqw_kernel(SolverArgs a) {
                         if (r < nx * nx) {
                             if (t > 0) {
                                 const int i = r / nx, j = r - i * nx;
-                                T v = T(0);
-                                for (int k = 0; k < nx; ++k) v = fma(tb[oP + i * nx + k], At[k * nin + j], v);
+                                Acc v_acc = T(0);
+                                for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(tb[oP + i * nx + k], At[k * nin + j], v_acc);
+                                const T v = (T)v_acc;
                                 tb[oPA + r] = v;
                             }
                             continue;
@@ -140,14 +142,16 @@ __global__ __launch_bounds__(256) void solver_lqw_kernel(SolverArgs a) {
                         r -= nx * nx;
                         if (r < nx * nu) {
                             const int i = r / nu, j = r - i * nu;
-                            T v = T(0);
-                            for (int k = 0; k < nx; ++k) v = fma(tb[oP + i * nx + k], At[k * nin + nx + j], v);
+                            Acc v_acc = T(0);
+                            for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(tb[oP + i * nx + k], At[k * nin + nx + j], v_acc);
+                            const T v = (T)v_acc;
                             tb[oPB + r] = v;
                             continue;
                         }
                         r -= nx * nu;
-                        T v = tb[op + r];
-                        for (int k = 0; k < nx; ++k) v = fma(tb[oP + r * nx + k], gc[t * nx + k], v);
+                        Acc v_acc = tb[op + r];
+                        for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(tb[oP + r * nx + k], gc[t * nx + k], v_acc);
+                        const T v = (T)v_acc;
                         tb[oPc + r] = v;
                     }
                     wsync();
@@ -158,8 +162,9 @@ __global__ __launch_bounds__(256) void solver_lqw_kernel(SolverArgs a) {
                             const int i = r / nu, j = r - i * nu;
                             T ga = T(0), ha = T(0);
                             if (i == j) ha = bh[uo + t * nu + i];
-                            T v = Rs[i * nu + j] + Wt[(nx + i) * nin + nx + j] + (i == j ? ha + reg : T(0));
-                            for (int k = 0; k < nx; ++k) v = fma(At[k * nin + nx + i], tb[oPB + k * nu + j], v);
+                            Acc v_acc = Rs[i * nu + j] + Wt[(nx + i) * nin + nx + j] + (i == j ? ha + reg : T(0));
+                            for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(At[k * nin + nx + i], tb[oPB + k * nu + j], v_acc);
+                            const T v = (T)v_acc;
                             tb[oQuu + r] = v;
                             continue;
                         }
@@ -167,16 +172,18 @@ __global__ __launch_bounds__(256) void solver_lqw_kernel(SolverArgs a) {
                         if (r < nu) {
                             T ga = T(0), ha = T(0);
                             ha = bh[uo + t * nu + r];
-                            T v = gr[uo + t * nu + r] + ga;
-                            for (int k = 0; k < nx; ++k) v = fma(At[k * nin + nx + r], tb[oPc + k], v);
+                            Acc v_acc = gr[uo + t * nu + r] + ga;
+                            for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(At[k * nin + nx + r], tb[oPc + k], v_acc);
+                            const T v = (T)v_acc;
                             tb[oqu + r] = v;
                             continue;
                         }
                         r -= nu;
                         if (t > 0) {
                             const int i = r / nx, j = r - i * nx;
-                            T w = Wt[(nx + i) * nin + j];
-                            for (int k = 0; k < nx; ++k) w = fma(At[k * nin + nx + i], tb[oPA + k * nx + j], w);
+                            Acc w_acc = Wt[(nx + i) * nin + j];
+                            for (int k = 0; k < nx; ++k) w_acc = lq_fma<Acc>(At[k * nin + nx + i], tb[oPA + k * nx + j], w_acc);
+                            const T w = (T)w_acc;
                             tb[oQux + r] = w;
                         }
                     }
@@ -229,17 +236,19 @@ __global__ __launch_bounds__(256) void solver_lqw_kernel(SolverArgs a) {
                                 const int i = e / nx, j = e - i * nx;
                                 T ga = T(0), ha = T(0);
                                 if (i == j) ha = bh[(t - 1) * nx + i];
-                                T v = Qs[i * nx + j] + Wt[i * nin + j] + (i == j ? ha : T(0));
-                                for (int k = 0; k < nx; ++k) v = fma(At[k * nin + i], tb[oPA + k * nx + j], v);
-                                for (int k = 0; k < nu; ++k) v = fma(tb[oQux + k * nx + i], tb[oK + k * nx + j], v);
+                                Acc v_acc = Qs[i * nx + j] + Wt[i * nin + j] + (i == j ? ha : T(0));
+                                for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(At[k * nin + i], tb[oPA + k * nx + j], v_acc);
+                                for (int k = 0; k < nu; ++k) v_acc = lq_fma<Acc>(tb[oQux + k * nx + i], tb[oK + k * nx + j], v_acc);
+                                const T v = (T)v_acc;
                                 tb[oPn + e] = v;
                             } else {
                                 const int i = e - nx * nx;
                                 T ga = T(0), ha = T(0);
                                 ha = bh[(t - 1) * nx + i];
-                                T v = gr[(t - 1) * nx + i] + ga;
-                                for (int k = 0; k < nx; ++k) v = fma(At[k * nin + i], tb[oPc + k], v);
-                                for (int k = 0; k < nu; ++k) v = fma(tb[oQux + k * nx + i], tb[okv + k], v);
+                                Acc v_acc = gr[(t - 1) * nx + i] + ga;
+                                for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(At[k * nin + i], tb[oPc + k], v_acc);
+                                for (int k = 0; k < nu; ++k) v_acc = lq_fma<Acc>(tb[oQux + k * nx + i], tb[okv + k], v_acc);
+                                const T v = (T)v_acc;
                                 tb[opn + i] = v;
                             }
                         }
@@ -279,24 +288,27 @@ __global__ __launch_bounds__(256) void solver_lqw_kernel(SolverArgs a) {
             for (int t = 0; t < H; ++t) {
                 const T* At = tl + (size_t)t * nx * nin;
                 for (int i = lane; i < nu; i += 64) {
-                    T v = kst[(size_t)t * nu + i];
+                    Acc v_acc = kst[(size_t)t * nu + i];
                     if (t > 0)
-                        for (int k = 0; k < nx; ++k) v = fma(Kst[(size_t)t * nu * nx + i * nx + k], tb[odx + k], v);
+                        for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(Kst[(size_t)t * nu * nx + i * nx + k], tb[odx + k], v_acc);
+                    const T v = (T)v_acc;
                     tb[odu + i] = v;
                 }
                 wsync();
                 for (int i = lane; i < nx; i += 64) {
-                    T v = gc[t * nx + i];
+                    Acc v_acc = gc[t * nx + i];
                     if (t > 0)
-                        for (int k = 0; k < nx; ++k) v = fma(At[i * nin + k], tb[odx + k], v);
-                    for (int k = 0; k < nu; ++k) v = fma(At[i * nin + nx + k], tb[odu + k], v);
+                        for (int k = 0; k < nx; ++k) v_acc = lq_fma<Acc>(At[i * nin + k], tb[odx + k], v_acc);
+                    for (int k = 0; k < nu; ++k) v_acc = lq_fma<Acc>(At[i * nin + nx + k], tb[odu + k], v_acc);
+                    const T v = (T)v_acc;
                     tb[odxn + i] = v;
                 }
                 wsync();
                 for (int i = lane; i < nx + nu; i += 64) {
                     if (i < nx) {
-                        T lam = pst[(size_t)t * nx + i];
-                        for (int k = 0; k < nx; ++k) lam = fma(Pst[(size_t)t * nx * nx + i * nx + k], tb[odxn + k], lam);
+                        Acc lam_acc = pst[(size_t)t * nx + i];
+                        for (int k = 0; k < nx; ++k) lam_acc = lq_fma<Acc>(Pst[(size_t)t * nx * nx + i * nx + k], tb[odxn + k], lam_acc);
+                        const T lam = (T)lam_acc;
                         lam_inf = fmax(lam_inf, fabs(lam));
                         lamn[t * nx + i] = lam;
                         const T d = tb[odxn + i], zz = z[t * nx + i], lo = lb[t * nx + i], hi = ub[t * nx + i];

@@ -383,25 +383,15 @@ __global__ __launch_bounds__(64) void solver_soc_kernel(int n, int nx, int nu, i
                                                         const T* __restrict__ tiles, const T* __restrict__ X0,
                                                         const T* __restrict__ ex, T* __restrict__ Zs, T* __restrict__ X0p,
                                                         T* __restrict__ exp_, int* __restrict__ n_pending) {
+    // dynamic LDS: dx_{t-1} and dx_t, 2 nx elements (soc_correct_row, solver_soc_impl.h: any nx, a lane walks the states
+    // lane, lane + 64, ...)
+    extern __shared__ __attribute__((aligned(16))) unsigned char soc_lds_raw[];
     const int slot = blockIdx.x, lane = threadIdx.x;
     if (slot == 0 && lane == 0) *n_pending = 0;
     const int b = list[slot];
-    const int nin = nx + nu;
-    const T* zt = Zt + (size_t)b * n;                   // (the rejected trial ran over every active problem: slot == problem)
-    const T* ct = gt + (size_t)b * m;
-    T* zs = Zs + (size_t)slot * n;
-    T dx = T(0);                                        // lane i < nx: dx_{t-1}[i]
-    for (int t = 0; t < H; ++t) {
-        const T* At = tiles + ((size_t)b * H + t) * nx * nin;        // row i: dPhi_i / d[x_{t-1} | u_t]
-        T acc = lane < nx ? ct[t * nx + lane] : T(0);
-        for (int e = 0; e < nx; ++e) {
-            const T de = __shfl(dx, e);
-            if (lane < nx) acc = fma(At[lane * nin + e], de, acc);
-        }
-        dx = acc;
-        if (lane < nx) zs[t * nx + lane] = zt[t * nx + lane] + dx;
-    }
-    for (int i = H * nx + lane; i < n; i += 64) zs[i] = zt[i];
+    // (the rejected trial ran over every active problem: slot == problem)
+    soc_correct_row<T>(lane, 64, [] { __syncthreads(); }, nx, nu, H, Zt + (size_t)b * n, gt + (size_t)b * m,
+                       tiles + (size_t)b * H * nx * (nx + nu), Zs + (size_t)slot * n, reinterpret_cast<T*>(soc_lds_raw));
     for (int i = lane; i < nx; i += 64) X0p[(size_t)slot * nx + i] = X0[(size_t)b * nx + i];
     for (int i = lane; i < ex_per; i += 64) exp_[(size_t)slot * ex_per + i] = ex[(size_t)b * ex_per + i];
 }

@@ -193,6 +193,12 @@ class CallbackEngine:
                 5: "layered_gemm_kernel"}[v % 10]
         return ("rk4:" + name) if v >= 10 and name else name
 
+    @property
+    def last_lq_kernel(self):
+        """LQ plan of the most recent solve: "thread_global" (thread per problem, working set in global memory),
+        "thread_lds", "wave_lds", "scan"; None before the first solve."""
+        return {0: None, 1: "thread_global", 2: "thread_lds", 3: "wave_lds", 4: "scan"}[self.lib.nempc_last_lq_kernel(self._handle)]
+
     # ------------------------------------------------------------------ parameters
     def set_objective(self, Q=None, R=None, xref=None, uref=None, cx=None, cu=None, QT=None):
         """Quadratic + linear stage cost; QT (nx,nx) is the state weight of the last step (terminal cost), None = Q."""

@@ -1,7 +1,7 @@
 """Per-problem, time-varying bounds of the bounded convex QPs  --  TEST INFRASTRUCTURE, not a test.
 
 Shared by tests/test_bounds_cpu.py (the fixture checks itself) and tests/test_gpu_bounds.py (nempc_bind_bounds against the
-exact active-set solutions).  The two rows of solver_step_cases.BOUNDED_ROWS keep their networks, objectives and starts
+exact active-set solutions).  The two small rows of solver_step_cases.BOUNDED_ROWS (ROWS below) keep their networks, objectives and starts
 (solver_step_cases.bounded_case); what changes is where the limits come from: every problem gets a SCHEDULE of L = H + 3 rows
 of its own, handed over through the binding alone -- no box rows, no host lb / ub:
 
@@ -21,6 +21,13 @@ import numpy as np
 import kkt_reference as kkt
 import solver_step_cases as sc
 
+# The rows this construction serves: the two bounded rows of small stages.  The wide rows of BOUNDED_ROWS (20x4_h6,
+# 40x10_h3) are not formed here: the schedule's moving control limits leave inactive controls so close to a limit in their
+# references that the inactive bounds' pull on the last barrier sub-problem (inactive_pull, below) exceeds the end-point
+# bound itself at the tests' MU_MIN -- 20x4_h6, offset 3, problem 3: 2.7e-6 against a bound of 4.3e-7 -- so condition C of
+# tests/test_bounds_cpu.py fails on the reference alone, before any solver runs.  Their shared-bounds form is checked in
+# tests/test_gpu_solver_steps.py and tests/test_gpu_duals.py.
+ROWS = ("2x1_h12", "3x2_h7")
 EXTRA_ROWS = 3
 OFFSETS = (0, EXTRA_ROWS)
 SCALES = (1.0, 0.8, 1.25, 0.6)

@@ -25,13 +25,37 @@ KINDS = {"discret": orc.DISCRET, "unity": orc.UNITY, "rk4": orc.RK4}
 H_GLOBAL = 355
 
 
-def lds_bytes_2x1_thread(H):
-    """(bytes one problem needs, budget) of the 2/1 fp64 thread-per-problem sweep at one damping level -- plan_lq's sizes."""
-    nx, nu, nin, n = 2, 1, 3, 3 * H
+def lds_bytes(nx, nu, H, dtype="float64", levels=1):
+    """(bytes one problem needs, budget of a workgroup) of the LQ sweep with `levels` damping levels side by side --
+    plan_lq's sizes (csrc/solver.hip): the working set is staged in LDS when the first is at most the second."""
+    nin = nx + nu
+    n = H * nin
+    size = {"float64": 8, "float32": 4}[dtype]
     tmp = 3 * nx * nx + 3 * nx * nu + nu * nu + 5 * nx + 3 * nu + 1 + (nx + 1) * nu
     att = H * nu * nx + H * nu + H * nx * nx + H * nx + tmp
-    per = (2 * n + 2 * H * nx + H * nx * nin + H * nin * nin + n + n + H * nx + 2 * n + att) | 1
-    return 8 * per, 150 * 1024 - 2 * n * 8
+    per = (2 * n + 2 * H * nx + H * nx * nin + H * nin * nin + n + n + H * nx + 2 * n + levels * att) | 1
+    return size * per, 150 * 1024 - 2 * n * size
+
+
+def lds_bytes_2x1_thread(H):
+    """(bytes one problem needs, budget) of the 2/1 fp64 thread-per-problem sweep at one damping level -- plan_lq's sizes."""
+    return lds_bytes(2, 1, H, "float64", 1)
+
+
+def expected_lq_plan(nx, nu, H, dtype, kernel, scan_default=True):
+    """The plan (CallbackEngine.last_lq_kernel: "thread_global" | "thread_lds" | "wave_lds" | "scan") the size formula
+    predicts for a requested lq_kernel -- plan_lq's decision restated: the wave kernel is
+    wanted when forced, or under "auto" at nx (nx + nu) >= 12, and then sweeps one damping level; the thread kernel asks for
+    three levels side by side and gives them up one by one until the problem fits; whatever was asked for, a working set
+    over the budget runs thread per problem from global memory.  The scan is built for 2/1 fp64 stages with H <= 63 and is
+    what "auto" takes there (scan_default: the solver's NEMPC_LQ_SCAN knob, on unless the environment says otherwise)."""
+    wave = kernel == "wave" or (kernel in ("auto", "scan") and nx * (nx + nu) >= 12)
+    scan_fits = dtype == "float64" and (nx, nu) == (2, 1) and H + 1 <= 64
+    scan = scan_fits and (kernel == "scan" or (kernel == "auto" and scan_default))
+    need, budget = lds_bytes(nx, nu, H, dtype, 0 if scan else 1)
+    if need > budget:
+        return "thread_global"
+    return "wave_lds" if wave else ("scan" if scan else "thread_lds")
 
 
 # ---- (a) one Newton step on an equality-constrained convex QP: linear networks.
@@ -46,12 +70,23 @@ QP_ROWS = {
     "roll3_rev":     (2, 1, [8], "discret", 1.0, (10,), ("auto",), "float64", 3, False, 0),
     "2x1_extras":    (2, 1, [8], "discret", 1.0, (10,), ("auto",), "float64", 1, True, 2),
     "2x1_fp32":      (2, 1, [32], "discret", 1.0, (20,), ("thread", "wave"), "float32", 1, True, 0),
+    # wide stages: more matrix entries than lanes, every LQ plan (lds_bytes: fp64 bytes per problem against ~150 KiB)
+    "12x5_discret":  (12, 5, [16], "discret", 1.0, (4,), ("thread", "wave", "auto"), "float64", 1, True, 0),    # 33 KB: several per workgroup
+    "3x8_discret":   (3, 8, [8], "discret", 1.0, (5,), ("thread", "wave", "auto"), "float64", 1, True, 0),      # nu > nx: 8 x 8 Quu
+    "16x4_rk4":      (16, 4, [8], "rk4", 0.1, (4,), ("thread", "wave", "auto"), "float64", 1, True, 0),         # 48 KB
+    "20x4_discret":  (20, 4, [8], "discret", 1.0, (6,), ("thread", "wave", "auto"), "float64", 1, True, 0),     # 98 KB: one per workgroup, > 64 KiB
+    "33x3_unity":    (33, 3, [8], "unity", 1.0, (3,), ("thread", "wave"), "float64", 1, True, 0),               # 127 KB, nx > 32
+    "40x10_discret": (40, 10, [8], "discret", 1.0, (3,), ("thread", "auto"), "float64", 1, True, 0),            # 221 KB: global memory
+    "40x10_fp32":    (40, 10, [8], "discret", 1.0, (3,), ("thread", "wave"), "float32", 1, True, 0),            # 111 KB: the same shape in LDS
+    "64x8_discret":  (64, 8, [8], "discret", 1.0, (1, 3), ("auto",), "float64", 1, True, 0),                    # global memory (H = 3)
+    "64x8_fp32":     (64, 8, [8], "discret", 1.0, (1,), ("thread", "wave"), "float32", 1, True, 0),             # 119 KB: LDS at 64 states
+    "70x3_discret":  (70, 3, [8], "discret", 1.0, (2,), ("auto",), "float64", 1, True, 0),                      # more states than lanes
 }
 # (one seed for every row.  It matters at H = 355 only: of the seeds 0..11 this one gives the 2/1 Discret dynamics I + 0.1 W the
 #  smallest spectral radius, 1.0007 -- a mode of 1.015 grows 200-fold over 355 stages and takes the conditioning with it)
 QP_SEED = 1
 QP_CASES = [(name, H) for name, row in QP_ROWS.items() for H in row[5]]
-QP_RANDOM_START = {("2x1_discret", 20), ("6x3_rk4", 8)}      # also run from a random Z_init
+QP_RANDOM_START = {("2x1_discret", 20), ("6x3_rk4", 8), ("12x5_discret", 4), ("20x4_discret", 6)}      # also run from a random Z_init
 
 # ---- (b) three steps of a nonlinear solve: tanh networks, output layer scaled by 0.1, X0 in +-0.5, 8 problems
 # name: (nx, nu, hidden, integrator, DT, H, lq kernels, dtype, steps)
@@ -62,8 +97,18 @@ NL_ROWS = {
     "3x2_unity": (3, 2, [24], "unity", 1.0, 7, ("thread", "wave", "auto"), "float64", 3),
     "5x2_h9":    (5, 2, [16, 16], "discret", 1.0, 9, ("thread", "wave", "auto"), "float64", 3),
     "6x3_fp32":  (6, 3, [32, 32], "rk4", 0.1, 8, ("thread", "wave", "auto"), "float32", 2),
+    # wide stages (seed 0).  16x4_rk4 and 70x3_h2: some reference steps are below STOP_STEP by the third step
+    "12x5_h4":   (12, 5, [16], "discret", 1.0, 4, ("thread", "wave", "auto"), "float64", 3),
+    "20x4_h6":   (20, 4, [24], "discret", 1.0, 6, ("thread", "wave", "auto"), "float64", 3),
+    "16x4_rk4":  (16, 4, [16, 16], "rk4", 0.1, 4, ("wave", "auto"), "float64", 3),
+    "40x10_h3":  (40, 10, [16], "discret", 1.0, 3, ("auto",), "float64", 3),
+    "70x3_h2":   (70, 3, [16], "discret", 1.0, 2, ("auto",), "float64", 3),
 }
 NL_B = 8
+# Problems (of NL_B) whose reference steps 1..3 are all at least STOP_STEP, i.e. that are still compared at the third step,
+# where that is not at least 5 (the bar of the multiplier test): wide stages converge faster than the small ones
+# (asserted from the reference in tests/test_kkt_reference_cpu.py; steps 1 and 2 compare every problem on every row)
+NL_STEP3_COMPARED = {"16x4_rk4": 2}
 GATE_EIG = 0.05          # reduced-Hessian eigenvalue below which the sweep could restart with damping
 STOP_STEP = 1e-6         # a reference step below this is at the convergence test: the solver rightly stands still
 
@@ -87,15 +132,15 @@ class Case:
     """One shape: the network, the objective, BMAX starts and per-problem oracle Problems."""
 
     def __init__(self, name, nx, nu, hidden, integ, DT, H, kernels, dtype, window=1, forward=True, n_extra=0,
-                 act="linear", seed=0, B=BMAX, scale_b=False, x0_range=0.5):
+                 act="linear", seed=0, B=BMAX, scale_b=False, x0_range=0.5, out_scale=0.1):
         self.name, self.nx, self.nu, self.H, self.integ, self.DT = name, nx, nu, H, integ, DT
         self.kernels, self.dtype, self.window, self.forward, self.n_extra, self.B = kernels, dtype, window, forward, n_extra, B
         n_in = window * (nx + nu) + n_extra
         net = orc.MLP.random(n_in, hidden, nx, seed=seed, activations=act)
         if integ == "discret" or act != "linear":
-            net.W[-1] *= 0.1
+            net.W[-1] *= out_scale
             if scale_b:
-                net.b[-1] *= 0.1
+                net.b[-1] *= out_scale
         net.W = [_round(w, dtype) for w in net.W]
         net.b = [_round(b, dtype) for b in net.b]
         self.net = net
@@ -201,7 +246,17 @@ def nl_reference(name):
 BOUNDED_ROWS = {
     "2x1_h12": (2, 1, [32], "discret", 1.0, 12, 1),
     "3x2_h7":  (3, 2, [8], "unity", 1.0, 7, 1),
+    "20x4_h6": (20, 4, [8], "discret", 1.0, 6, 1),
+    "40x10_h3": (40, 10, [8], "discret", 1.0, 3, 1),
 }
+# The rows the central-path consumers keep (tests/test_sensitivity_reference_cpu.py, tests/test_kkt_solve_reference_cpu.py and
+# the bounded test of test_gpu_sensitivity.py): they place a synthetic point at mu = 2.5e-9 next to
+# the exact solution and hold the float64 references to absolute bars there (riccati - dense <= 1e-5, dense - active set <=
+# 1e-4).  On the wide rows the float64 references alone miss those bars -- 15 .. 17 active bounds with multipliers down to
+# 1.2e-3 put Sigma up to 2.5e11 into P: dense - active set is 3.5e-4 (20x4_h6) and 5.3e-3 (40x10_h3), the affine recursion is
+# 1.6e-5 from the dense solve on 20x4_h6 problem 2 -- so those constructions cannot form the wide cases; the wide rows'
+# end points, multipliers and certificates are checked in test_gpu_solver_steps.py and test_gpu_duals.py.
+BOUNDED_SMALL = ("2x1_h12", "3x2_h7")
 BOUNDED_B = 4
 STATE_WIDE = 5.0
 NU_MIN = 1e-3            # smallest active bound multiplier the reference must show (strict complementarity with a margin)
@@ -265,3 +320,71 @@ def bounded_case(name):
 def bounded_reference(name):
     case, lbe, ube, _ = bounded_case(name)
     return [kkt.qp_solution(case.problem(b), case.X0[b], lbe, ube) for b in range(case.B)]
+
+
+# ---- (d) second-order correction of a rejected full step (solver_soc_kernel): tanh networks, output layer NOT scaled down,
+# 8 problems, X0 in +-SOC_X0_RANGE, start = the roll-out of seeded controls in +-SOC_U_RANGE.
+# The start is feasible on purpose.  From the cold start the first full step removes defects of order one and lowers the l1
+# merit for every problem at every scale tried on the CPU (output layer x 1, 2, 4; X0 in +-0.5 .. +-30; seeds 0, 1); the
+# correction is for the Maratos setting: at a feasible point a full step along the curved constraints leaves second-order
+# defects, the penalty 1.5 |lam+|inf (13 .. 43 here) times them outweighs the objective's decrease and the step is rejected.
+# name: (nx, nu, hidden, integrator, DT, H)
+SOC_ROWS = {
+    "6x3_rk4": (6, 3, [32, 32], "rk4", 0.1, 8),
+    "64x8_h3": (64, 8, [16], "discret", 1.0, 3),
+    "70x3_h2": (70, 3, [16], "discret", 1.0, 2),
+}
+SOC_B, SOC_SEED, SOC_X0_RANGE, SOC_U_RANGE = 8, 0, 1.0, 0.5
+MAX_LINESEARCH = 6       # CallbackEngine.solve's default: trial lengths 1, 1/2, .., 2^-5
+
+
+@functools.lru_cache(maxsize=None)
+def soc_case(name):
+    nx, nu, hidden, integ, DT, H = SOC_ROWS[name]
+    return Case(name, nx, nu, hidden, integ, DT, H, ("auto",), "float64", act="tanh", seed=SOC_SEED, B=SOC_B,
+                x0_range=SOC_X0_RANGE, out_scale=1.0)
+
+
+def rollout(prob, x0, U):
+    """z = [x_1 .. x_H ; U] with x_t = Phi(x_{t-1}, u_t): zero defects."""
+    H, nx = prob.H, prob.nx
+    z = np.concatenate([np.zeros(H * nx), np.asarray(U, dtype=np.float64).ravel()])
+    for t in range(H):
+        z[t * nx:(t + 1) * nx] = prob.tiles(z, x0)[1][t]
+    return z
+
+
+def soc_correction(prob, z0, zt, x0):
+    """The state-only recursion dx_t = A_t dx_{t-1} + c+_t with the Jacobian tiles at z0 and the defects at the trial point
+    zt, as a z-shaped vector (zero on the controls)."""
+    H, nx = prob.H, prob.nx
+    dphi = prob.tiles(z0, x0)[2]
+    c = prob.constraints(zt, x0)[:H * nx].reshape(H, nx)
+    out, dx = np.zeros(prob.n), np.zeros(nx)
+    for t in range(H):
+        dx = dphi[t][:, :nx] @ dx + c[t]
+        out[t * nx:(t + 1) * nx] = dx
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def soc_reference(name):
+    """Per problem: z0 (the feasible start), dz (the dense Newton step from it), tol (step_tolerance of that step), raises
+    (the full step raises the l1 merit under the solver's penalty max(1, 1.5 |lam+|inf + 1e-3)) and cands: the finite set of
+    points one iteration with inner-loop backtracking can return, [(label, point)] -- the full step, the corrected point,
+    z0 + 2^-k dz for k = 1 .. MAX_LINESEARCH, and z0 itself."""
+    case = soc_case(name)
+    H, nx, nu = case.H, case.nx, case.nu
+    rng = np.random.default_rng(SOC_SEED + 300)
+    out = []
+    for b in range(case.B):
+        prob, x0 = case.problem(b), case.X0[b]
+        z0 = rollout(prob, x0, rng.uniform(-SOC_U_RANGE, SOC_U_RANGE, size=(H, nu)))
+        dz, lam, _, eig = kkt.newton_step(prob, z0, x0, np.zeros(H * nx), REG)
+        dzr, _ = kkt.riccati_step(prob, z0, x0, np.zeros(H * nx), REG, np.float64)
+        pen = max(1.0, 1.5 * float(np.abs(lam).max()) + 1e-3)
+        cands = [("full", z0 + dz), ("corrected", z0 + dz + soc_correction(prob, z0, z0 + dz, x0))]
+        cands += [(f"half^{k}", z0 + 2.0 ** -k * dz) for k in range(1, MAX_LINESEARCH + 1)] + [("start", z0)]
+        out.append(dict(z0=z0, dz=dz, eig=eig, pen=pen, cands=cands, tol=step_tolerance(float(np.abs(dzr - dz).max()), z0 + dz),
+                        raises=kkt.l1_merit(prob, z0 + dz, x0, pen) > kkt.l1_merit(prob, z0, x0, pen)))
+    return out

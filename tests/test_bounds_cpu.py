@@ -74,7 +74,7 @@ def test_closed_loop_batch_wants_steps_plus_horizon_minus_one_rows():
         mpc.closed_loop_batch(np.zeros((3, 2)), 3, xlb=np.zeros((3, 6, 2)), uub=np.zeros((6, 1)))
 
 
-@pytest.mark.parametrize("name", list(sc.BOUNDED_ROWS))
+@pytest.mark.parametrize("name", list(bc.ROWS))
 def test_the_schedules_are_what_the_module_says(name):
     case, s = bc.schedule(name)
     L = case.H + bc.EXTRA_ROWS
@@ -86,7 +86,7 @@ def test_the_schedules_are_what_the_module_says(name):
 
 
 @pytest.mark.parametrize("offset", bc.OFFSETS)
-@pytest.mark.parametrize("name", list(sc.BOUNDED_ROWS))
+@pytest.mark.parametrize("name", list(bc.ROWS))
 def test_the_references_solve_with_strict_complementarity_and_away_from_the_shared_solutions(name, offset):
     """Condition A: every reference solves (kkt.qp_solution raises otherwise) and its smallest active multiplier is >= NU_MIN.
     Condition B: each solution differs from the same problem's solution under bounded_case's shared bounds by more than 100

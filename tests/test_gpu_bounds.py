@@ -61,7 +61,7 @@ def _flat(arrays, b, rows):
 # 4. / 5. bounded convex QPs: exact end points per problem, duals and certificate
 # --------------------------------------------------------------------------------------------------------------------
 QP_KERNELS = {"2x1_h12": ("thread", "wave", "scan"), "3x2_h7": ("thread", "wave")}
-QP_CASES = [(n, k) for n in sc.BOUNDED_ROWS for k in QP_KERNELS[n]]
+QP_CASES = [(n, k) for n in bc.ROWS for k in QP_KERNELS[n]]
 
 
 @functools.lru_cache(maxsize=None)

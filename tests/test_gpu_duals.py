@@ -50,10 +50,19 @@ PARITY_ROWS = {
     "5x2_one_layer": ("qp", "5x2_one_layer", 9, {}, False, False),
     "2x1_extras": ("qp", "2x1_extras", 10, {}, False, False),
     "2x1_fp32": ("qp", "2x1_fp32", 20, {}, False, False),
+    "12x5_H4": ("qp", "12x5_discret", 4, {}, False, False),
+    "3x8_H5": ("qp", "3x8_discret", 5, {}, False, False),
+    "20x4_H6": ("qp", "20x4_discret", 6, {}, False, False),
+    "40x10_fp32": ("qp", "40x10_fp32", 3, {}, False, False),
+    "64x8_H3": ("qp", "64x8_discret", 3, {}, False, False),
+    "70x3_H2": ("qp", "70x3_discret", 2, {}, False, False),
     "tanh_2x1_h20": ("nl", "2x1_h20", 20, {}, False, False),
     "tanh_6x3_rk4": ("nl", "6x3_rk4", 8, {}, False, False),
     "tanh_2x1_h20_box": ("nl", "2x1_h20", 20, {}, True, False),
     "tanh_6x3_rk4_box": ("nl", "6x3_rk4", 8, {}, True, False),
+    "tanh_16x4_rk4": ("nl", "16x4_rk4", 4, {}, False, False),
+    "tanh_40x10_h3_box": ("nl", "40x10_h3", 3, {}, True, False),
+    "tanh_70x3_h2": ("nl", "70x3_h2", 2, {}, False, False),
     "tanh_2x1_h20_tracking": ("nl", "2x1_h20", 20, {}, False, True),
     "tanh_2x1_h20_valu": ("nl", "2x1_h20", 20, {"kernel": "valu"}, False, False),
     "tanh_2x1_h20_layered": ("nl", "2x1_h20", 20, {"kernel": "layered"}, False, False),
@@ -173,7 +182,14 @@ QP_W1 = [(name, H) for name, H in sc.QP_CASES if sc.QP_ROWS[name][8] == 1]
 @pytest.mark.parametrize("name,H", QP_W1)
 def test_one_newton_step_returns_the_multipliers_of_that_step(name, H):
     """Linear networks, max_iter = 1: lam[:, :H nx] is lam+ of the dense Newton step (qp_reference), for every lq kernel of
-    the row and B in {1, 2, 3, 16}; zl, zu are exactly zero (no bounds); no problem is left out."""
+    the row and B in {1, 2, 3, 16}; zl, zu are exactly zero (no bounds); no problem is left out.
+
+    Observed on an MI355X, largest error / tolerance on the wide rows: 12x5 0.006, 3x8 0.004, 16x4_rk4 0.006, 20x4 0.025,
+    33x3 0.003, 40x10 0.011, 40x10_fp32 0.199, 64x8 H=1 0.001, H=3 0.013, 70x3 0.008, 64x8_fp32 0.901.  The last one was
+    1.108 (problem 4: 1.865e-06 against 1.683e-06) while the run-time-dimension LQ kernels summed 64 float32 terms per
+    multiplier in float32; they now accumulate in double on fp32 handles (the 64x8_fp32 note in
+    tests/test_gpu_solver_steps.py).  What is left is the float32 objective gradient, which enters lam+ one to one at
+    H = 1 and is within 1.1e-06 of the float64 one."""
     case = sc.qp_case(name, H)
     ref, e_lam = sc.qp_reference(name, H), _qp_lam_error(name, H)
     eng = case.engine()
@@ -214,13 +230,16 @@ def test_multipliers_along_a_nonlinear_solve_follow_the_newton_replay(name):
     """tanh networks, max_iter = 1, 2, 3: the returned lam is lam+ of replay step k, as Z is the iterate after it.  The 2 x 64
     rows run the fused-accept schedule (trial multipliers carried), the 6/3 rows the inner-loop line search.  A problem is
     no longer compared once a reference step is below STOP_STEP (the existing rule); steps 1 and 2 compare all 8 problems,
-    step 3 at least 5.
+    step 3 at least 5 (16x4_rk4: the 2 that solver_step_cases.NL_STEP3_COMPARED counts from the reference).
 
     Observed on an MI355X at FACTOR = 10 (problems compared per step; largest error / tolerance after 1 / 2 / 3 steps; the
     test prints both per row):
       2x1_h20    8 8 8   0.057 0.009 0.007      3x2_unity  8 8 5   0.000 0.000 0.000
       2x1_h63    8 8 8   0.101 0.091 0.031      5x2_h9     8 8 8   0.035 0.010 0.011
       6x3_rk4    8 8 7   0.019 0.010 0.006      6x3_fp32   8 8     0.299 0.194
+      12x5_h4    8 8 8   0.004 0.005 0.005      40x10_h3   8 8 8   0.007 0.006 0.007
+      20x4_h6    8 8 8   0.024 0.012 0.011      70x3_h2    8 8 6   0.006 0.007 0.006
+      16x4_rk4   8 8 2   0.006 0.007 0.007
     No ratio is above 1, so the factor stays 10."""
     case = sc.nl_case(name)
     steps = sc.NL_ROWS[name][8]
@@ -249,7 +268,7 @@ def test_multipliers_along_a_nonlinear_solve_follow_the_newton_replay(name):
                 if not e <= tol:
                     bad.append(f"{k} b={b} after {it} steps: |lam - lam+| = {e:.3e} > {tol:.3e} (ratio {e / tol:.1f})")
             compared[it - 1] = nb
-            assert nb == case.B if it <= 2 else nb >= 5, (name, it, nb)
+            assert nb == case.B if it <= 2 else nb >= sc.NL_STEP3_COMPARED.get(name, 5), (name, it, nb)
     print(f"[nl duals {name}] problems compared per step {compared.tolist()}, |lam+|inf up to {lam_max:.1f}, "
           f"error / tolerance per step {np.round(worst, 3).tolist()} (factor {FACTOR:g})")
     assert not bad, "\n".join(bad)

@@ -58,6 +58,9 @@ ROWS = {
     "3x2_unity_H7": ("qp", "3x2_unity", 7, {}, False, False),
     "2x1_extras": ("qp", "2x1_extras", 10, {}, False, False),
     "2x1_fp32": ("qp", "2x1_fp32", 20, {}, False, False),
+    "3x8_H5": ("qp", "3x8_discret", 5, {}, False, False),              # (wide rows of the step tables: nu > nx,
+    "20x4_H6": ("qp", "20x4_discret", 6, {}, False, False),            #  a 98 KB solver working set,
+    "70x3_H2": ("qp", "70x3_discret", 2, {}, False, False),            #  more states than lanes)
     "tanh_2x1_h20": ("nl", "2x1_h20", 20, {}, False, False),
     "tanh_2x1_h20_valu": ("nl", "2x1_h20", 20, {"kernel": "valu"}, False, False),
     "tanh_2x1_h20_layered": ("nl", "2x1_h20", 20, {"kernel": "layered"}, False, False),

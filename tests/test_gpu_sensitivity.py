@@ -62,6 +62,9 @@ ROWS = {
     "5x2_one_layer": ("qp", "5x2_one_layer", 9, {}, False, False),
     "2x1_extras": ("qp", "2x1_extras", 10, {}, False, False),
     "2x1_fp32": ("qp", "2x1_fp32", 20, {}, False, False),
+    "3x8_H5": ("qp", "3x8_discret", 5, {}, False, False),              # (wide rows of the step tables: nu > nx,
+    "20x4_H6": ("qp", "20x4_discret", 6, {}, False, False),            #  a 98 KB solver working set,
+    "70x3_H2": ("qp", "70x3_discret", 2, {}, False, False),            #  more states than lanes)
     "tanh_2x1_h20": ("nl", "2x1_h20", 20, {}, False, False),
     "tanh_2x1_h20_valu": ("nl", "2x1_h20", 20, {"kernel": "valu"}, False, False),
     "tanh_2x1_h20_layered": ("nl", "2x1_h20", 20, {"kernel": "layered"}, False, False),
@@ -279,7 +282,7 @@ def test_sensitivities_at_solver_solutions(name):
 # --------------------------------------------------------------------------------------------------------------------
 # 4. bounded QP
 # --------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(sc.BOUNDED_ROWS))
+@pytest.mark.parametrize("name", list(sc.BOUNDED_SMALL))      # (why not the wide rows: solver_step_cases.BOUNDED_SMALL)
 def test_bounded_qp_sensitivities_approach_the_active_set_limit(name):
     """The set-up of test_bounded_qp_solution_carries_a_kkt_certificate (primal-dual, mu_min = 1e-9) at the returned
     (Z, lam, zl, zu): tier B with sigma_of(...); then the device result against `active_set` of the exact solution within

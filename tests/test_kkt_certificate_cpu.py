@@ -17,14 +17,15 @@ import solver_step_cases as sc
 @pytest.mark.parametrize("name", list(sc.BOUNDED_ROWS))
 def test_reference_solutions_of_the_bounded_qp_are_kkt_points(name):
     """The exact active-set solutions of the bounded QPs (sc.bounded_reference) under the certificate: all four residuals
-    <= 1e-12.  Measured: stationarity <= 1e-14, defects <= 2e-14, 3 to 10 active bounds per problem."""
+    <= 1e-12.  Measured: stationarity <= 1e-14, defects <= 2e-14, 3 to 10 active bounds per problem (4 to 17 on the wide rows)."""
     case, lbe, ube, _ = sc.bounded_case(name)
     for b, (z, lam, nlo, nhi) in enumerate(sc.bounded_reference(name)):
         r, s = cert.residuals(case.problem(b), z, case.X0[b], lam, nlo, nhi, lbe, ube)      # (no box rows here: m = H nx)
         nact = int((nlo > 0).sum() + (nhi > 0).sum())
         print(f"[certificate {name}] b={b}: r = {r.tolist()}, {nact} active bounds")
         assert (r <= 1e-12).all(), (b, r)
-        assert 3 <= nact <= 10
+        lo, hi = (4, 17) if name in ("20x4_h6", "40x10_h3") else (3, 10)       # (the wide rows: 4 to 17)
+        assert lo <= nact <= hi
         assert s.shape == (case.n,)
 
 

@@ -50,7 +50,7 @@ def test_affine_recursion_equals_the_dense_solve_at_converged_points(name):
         assert e <= 1e-11 * (1.0 + np.abs(S).max())
 
 
-@pytest.mark.parametrize("name", list(sc.BOUNDED_ROWS))
+@pytest.mark.parametrize("name", list(sc.BOUNDED_SMALL))      # (why not the wide rows: solver_step_cases.BOUNDED_SMALL)
 def test_affine_recursion_holds_on_the_central_path_of_the_bounded_qps(name):
     """Synthetic central-path points (mu = 2.5e-9) next to the exact solutions of the bounded QPs, three random right-hand
     sides with rg: affine_riccati == dense_solve within 1e-5 absolutely (the bar of the sensitivity reference's own test: a

@@ -55,7 +55,7 @@ def test_reference_is_self_consistent_at_converged_points(name):
                                        rtol=0, atol=1e-11 * scale)
 
 
-@pytest.mark.parametrize("name", list(sc.BOUNDED_ROWS))
+@pytest.mark.parametrize("name", list(sc.BOUNDED_SMALL))      # (why not the wide rows: solver_step_cases.BOUNDED_SMALL)
 def test_reference_recursion_holds_on_the_central_path_of_the_bounded_qps(name):
     """Synthetic central-path points (mu = 2.5e-9) next to the exact solutions of the bounded QPs: riccati == dense within
     1e-5 absolutely (observed 8.4e-8 on 2x1_h12 problem 0, whose capped state puts Sigma = 1.8e11 inside P where it cancels in
