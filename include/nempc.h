@@ -442,6 +442,37 @@ int nempc_kkt_solve(nempc_handle h, int32_t B, const void* Z, const void* X0, co
                     const void* zu, const double* lb, const double* ub, int32_t nrhs, const void* rz, const void* rg, void* v,
                     void* w, void* gx0, int32_t* status, void* stream);
 
+/* Gradient with respect to the network's weights and biases (reference counterpart: none -- the reference never
+ * differentiates anything with respect to its model's parameters).  With theta = all weights and biases, xi_{b,t} =
+ * [x_{t-1} | u_t | extras_t] the network input of row (b,t), Phi_t the integrator map of the handle, T_t its Jacobian tile
+ * and v_[t] = [v_x[t-1] | v_u[t]] (v_x[-1] = 0):
+ *     S(theta) = sum_b keep_b sum_t ( w_{b,t} . Phi_t(xi_{b,t}; theta) + lam_{b,t} . ( T_t(xi_{b,t}; theta) v_{b,[t]} ) )
+ *     gtheta   = dS / dtheta          (Z, X0, lam, v, w held fixed)
+ * g = Phi - x and neither the objective nor the bound terms depend on theta, so gtheta = [v ; w]' d/dtheta [grad L ; g]: with
+ * (v, w) from nempc_kkt_solve the cotangent of theta behind the solution map is -gtheta.  With lam = v = NULL the second term
+ * drops and gtheta is the gradient of any defect-weighted loss (w = 2 (Phi - x_next): one-step prediction training).
+ *   nempc_n_params: P = sum_l (in_l + 1) * out_l.
+ *   Z (B,n), X0 (B,nx) device, required; w (B,H*nx) device, defect order, required;
+ *   lam (B,m), v (B,n) device, both or neither (one without the other: NEMPC_EINVAL); box-row entries of lam are not read;
+ *   skip (B) device int32, optional: a problem with skip[b] != 0 contributes exact zeros -- nothing of it is read, its
+ *   lam / v / w may hold NaN, and the result is, to the bit, that of the batch without it;
+ *   gtheta (P) device, dtype of the handle, OVERWRITTEN (not accumulated into): [W_0 (in_0,out_0) row-major | b_0 | W_1 | b_1
+ *   | ...], the layout of nempc_set_weights.
+ * Any network the generic row kernel takes (any widths up to 1024, up to 8 layers, any activation on any layer, extras: inputs
+ * of zero tangent whose rows of W_0 receive gradient all the same), Discret / Unity / RK4 (cfg.DT; u and the extras held over
+ * the four stages), both dtypes, whatever the handle's row-kernel variant.  One thread-per-row sweep in dual numbers leaves
+ * per layer the inputs (a, a.) and pre-activation cotangents (d, d.); dW_l = sum_r a_r (x) d._r + a._r (x) d_r is then a product
+ * over all rows on the matrix cores, split over the chip by rows, the partial sums added in a fixed order: no atomics, the
+ * result is the same to the bit from call to call.  Rows go in chunks of NEMPC_WGRAD_CHUNK_ROWS (environment, read per
+ * call; default: as many as 256 MiB of factors hold), rounded up to whole K slices.
+ * Asynchronous on `stream`, except a call that has to allocate or grow the handle's workspace for it: that call
+ * SYNCHRONISES THE DEVICE (the first call, and one after max_batch or the chunk size grew).  A handle that never calls this
+ * function allocates nothing for it.  Reads the extras binding (B beyond what it covers: NEMPC_EINVAL); rolling_window > 1:
+ * NEMPC_EUNSUPPORTED; argument checks and codes otherwise as nempc_eval.  The ABI version stays 8: nothing existing changed. */
+int nempc_n_params(nempc_handle h, int64_t* P);
+int nempc_weight_grad(nempc_handle h, int32_t B, const void* Z, const void* X0, const void* lam, const void* v,
+                      const void* w, const int32_t* skip, void* gtheta, void* stream);
+
 /* Forward simulation of the handle's model (no reference counterpart: the reference never integrates its model over the
  * horizon on its own -- its cold start tiles x0, optimizer/ipopt.py:149, and its examples step the plant outside the library).
  *   Z (B,n) device, in/out: the controls are read from Z[:, H*nx:] and are not written; the states Z[:, :H*nx] are

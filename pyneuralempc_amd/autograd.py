@@ -1,5 +1,6 @@
 """torch.autograd through the batched solver: `solve(eng, X0, xref=..., cu=...)` returns the solver's Z as a tensor that
-`loss.backward()` differentiates with respect to the initial states and the per-problem tracking data.
+`loss.backward()` differentiates with respect to the initial states, the per-problem tracking data and -- with `weights=` --
+the weights and biases of the network.
 
 The backward pass is one adjoint KKT solve (CallbackEngine.kkt_solve, nempc_kkt_solve): at the returned primal-dual point the
 KKT matrix K = [[W + Sigma, J'], [J, 0]] is symmetric, so with K [v ; w] = [Zbar ; 0] the cotangent of a parameter theta is
@@ -9,14 +10,21 @@ KKT matrix K = [[W + Sigma, J'], [J, 0]] is symmetric, so with K [v ; w] = [Zbar
     xrefbar[t] = Qs_t v_x[t]              Qs = Q + Q', QT + QT' at t = H-1
     urefbar[t] = Rs v_u[t]                Rs = R + R'
     cxbar      = -v_x,      cubar = -v_u
+    thetabar   = -gtheta                  gtheta = [v ; w]' d/dtheta [grad L ; g]   (CallbackEngine.weight_grad, nempc_weight_grad:
+                                          the objective and the bound terms do not depend on theta, g = Phi - x does)
 
-NOT differentiated: the network's weights, the extra inputs p / tvp, the weights Q / R / QT, and the bounds lb / ub (on the
+The weights are SHARED by the batch, so their cotangent is a sum over the problems.  A failed problem (solver status 1, or a
+KKT solve that reports status != 0) is always left out of that sum -- one NaN would poison every parameter --, whatever
+`on_fail` says: `on_fail` keeps its meaning for the per-problem inputs only.
+
+NOT differentiated: the extra inputs p / tvp, the weights Q / R / QT, and the bounds lb / ub (on the
 central path the gradients with respect to a lower / an upper bound are Sigma_l * v and Sigma_u * v, Sigma_l = zl / (z - lb),
 Sigma_u = zu / (ub - z): a caller who needs them forms them from `kkt_solve`'s v and the duals of `eng.solve`).
 
 The module uses torch and four members of the engine only -- `solve(X0, lb=, ub=, return_duals=True, ...)`,
-`kkt_solve(...)`, `bind_tracking(...)` and `objective_weights()` -- and assumes nothing about the device: any object that
-offers them works (tests/test_autograd_cpu.py runs it on a float64 CPU stub).
+`kkt_solve(...)`, `bind_tracking(...)` and `objective_weights()`, with `weights=` also `set_weights(weights, biases)` and
+`weight_grad(Z, X0, w, lam=, v=, skip=, flat=True)` -- and assumes nothing about the device: any object that
+offers them works (tests/test_autograd_cpu.py and tests/test_weight_grad_autograd_cpu.py run it on float64 CPU stubs).
 """
 import torch
 
@@ -25,7 +33,10 @@ _NAMES = ("xref", "uref", "cx", "cu")
 
 class _Solve(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, eng, opts, X0, xref, uref, cx, cu):
+    def forward(ctx, eng, opts, X0, xref, uref, cx, cu, *weights):
+        if weights:
+            host = [t.detach().to(device="cpu", dtype=torch.float64).numpy() for t in weights]
+            eng.set_weights(host[0::2], host[1::2])
         given = {k: t.detach().contiguous() for k, t in zip(_NAMES, (xref, uref, cx, cu)) if t is not None}
         X0d = X0.detach().contiguous()
         if given:
@@ -34,6 +45,7 @@ class _Solve(torch.autograd.Function):
         Z, status, duals = res[0], res[1], res[-1]
         # (clones: the point must survive whatever the engine does with its tensors until backward)
         ctx.eng, ctx.opts, ctx.given = eng, opts, given
+        ctx.wmeta = [(tuple(t.shape), t.device, t.dtype) for t in weights]
         ctx.saved = (Z.detach().clone(), X0d, duals["lam"].clone(), duals["zl"].clone(), duals["zu"].clone(), status.clone())
         ctx.mark_non_differentiable(status)
         return Z, status
@@ -45,7 +57,10 @@ class _Solve(torch.autograd.Function):
         Z, X0, lam, zl, zu, status = ctx.saved
         if ctx.given:
             eng.bind_tracking(**ctx.given)
-        out = eng.kkt_solve(Z, X0, lam, zl, zu, opts["lb"], opts["ub"], rz=gZ.contiguous(), want=("v", "gx0"))
+        need = ctx.needs_input_grad
+        need_theta = any(need[7:])
+        out = eng.kkt_solve(Z, X0, lam, zl, zu, opts["lb"], opts["ub"], rz=gZ.contiguous(),
+                            want=("v", "gx0", "w") if need_theta else ("v", "gx0"))
         v, gx0 = out["v"], out["gx0"]
         B, nx = X0.shape
         Q, R, QT = (torch.as_tensor(a, dtype=torch.float64).to(device=v.device, dtype=v.dtype) for a in eng.objective_weights())
@@ -58,8 +73,7 @@ class _Solve(torch.autograd.Function):
         def done(g):
             return torch.where(failed.reshape((B,) + (1,) * (g.dim() - 1)), torch.full_like(g, fill), g)
 
-        need = ctx.needs_input_grad
-        grads = [None, None, done(gx0) if need[2] else None, None, None, None, None]
+        grads = [None, None, done(gx0) if need[2] else None, None, None, None, None] + [None] * len(ctx.wmeta)
         if need[3]:
             g = vx @ (Q + Q.T)
             g[:, H - 1] = vx[:, H - 1] @ (QT + QT.T)
@@ -70,10 +84,21 @@ class _Solve(torch.autograd.Function):
             grads[5] = done(-vx)
         if need[6]:
             grads[6] = done(-vu)
+        if need_theta:
+            # (failed problems are skipped, not filled: the sum over the batch is shared by every parameter)
+            gtheta = eng.weight_grad(Z, X0, out["w"].contiguous(), lam=lam, v=v.contiguous(), skip=failed, flat=True)
+            at = 0
+            for i, (shape, dev, dt) in enumerate(ctx.wmeta):
+                k = 1
+                for d in shape:
+                    k *= int(d)
+                if need[7 + i]:
+                    grads[7 + i] = (-gtheta[at:at + k]).reshape(shape).to(device=dev, dtype=dt)
+                at += k
         return tuple(grads)
 
 
-def solve(eng, X0, *, xref=None, uref=None, cx=None, cu=None, lb=None, ub=None, on_fail="nan", **solve_kw):
+def solve(eng, X0, *, xref=None, uref=None, cx=None, cu=None, lb=None, ub=None, on_fail="nan", weights=None, **solve_kw):
     """Batched solve whose result is differentiable: returns (Z (B,n), status (B,) int32) of `eng.solve(X0, lb=lb, ub=ub,
     **solve_kw)` with the per-problem tracking data xref, cx (B,H,nx), uref, cu (B,H,nu) bound (those given; the others keep
     the shared values of set_objective).  Z carries a gradient with respect to those of X0, xref, uref, cx, cu that require
@@ -84,11 +109,20 @@ def solve(eng, X0, *, xref=None, uref=None, cx=None, cu=None, lb=None, ub=None, 
     The function binds the tracking tensors it is given with `eng.bind_tracking` in forward AND again in backward, and
     leaves that binding on the engine: a later plain `eng.solve` sees it until the caller binds something else or removes
     it with `eng.bind_tracking()`.  Extras / history bindings and the objective weights are the caller's and must be the
-    same at backward as at forward.  Not differentiated: network weights, p / tvp, Q / R / QT, lb / ub (module docstring).
+    same at backward as at forward.  Not differentiated: p / tvp, Q / R / QT, lb / ub (module docstring).
+
+    weights: None, or the network's parameters as a flat list [W_0, b_0, W_1, b_1, ...] of torch tensors (any device and
+    dtype; W_l (in_l,out_l), b_l (out_l,)).  Forward uploads their detached values with `eng.set_weights` -- they stay on the
+    engine -- and Z then carries a gradient with respect to those that require one: one `eng.weight_grad` call on top of the
+    adjoint solve, returned on each tensor's device and dtype.  The weights are shared by the batch: FAILED PROBLEMS ARE ALWAYS
+    SKIPPED in their gradient (a NaN would poison every parameter); `on_fail` decides about the per-problem inputs only.
     solve_kw goes to `eng.solve` (Z_init, max_iter, barrier, ...; return_duals is set here)."""
     if on_fail not in ("nan", "zero"):
         raise ValueError("on_fail must be 'nan' or 'zero'")
     if "return_duals" in solve_kw or "return_iterations" in solve_kw:
         raise ValueError("return_duals / return_iterations are not options of autograd.solve")
     opts = dict(lb=lb, ub=ub, on_fail=on_fail, solve_kw=solve_kw)
-    return _Solve.apply(eng, opts, X0, xref, uref, cx, cu)
+    weights = () if weights is None else tuple(weights)
+    if len(weights) % 2 or any(not isinstance(t, torch.Tensor) for t in weights):
+        raise ValueError("weights must be a flat list [W_0, b_0, W_1, b_1, ...] of torch tensors")
+    return _Solve.apply(eng, opts, X0, xref, uref, cx, cu, *weights)

@@ -298,6 +298,7 @@ void destroy_impl(Handle* h) {
     dev_free(h->d_kkt_bounds);
     dev_free(h->d_sens_ws);
     kktsolve_free(*h);
+    wgrad_free(*h);
     delete h;
 }
 
@@ -967,6 +968,32 @@ int nempc_kkt_solve(nempc_handle hh, int32_t B, const void* Z, const void* X0, c
     if (int rc = point_prepare(hh, who, POINT_TRACKING | POINT_BLOCKS, B, Z, X0, lam, lb, ub, stream, pc)) return rc;
     Handle& h = *reinterpret_cast<Handle*>(hh);
     return launch_kkt_solve(h, B, Z, h.d_tiles_ws, h.d_hess_ws, zl, zu, pc.dlb, pc.dub, nrhs, rz, rg, v, w, gx0, status, pc.s);
+}
+
+int nempc_n_params(nempc_handle hh, int64_t* P) {
+    if (!hh || !P) return fail(NEMPC_EINVAL, "nempc_n_params: null argument");
+    *P = wgrad_n_params(*reinterpret_cast<Handle*>(hh));
+    return NEMPC_OK;
+}
+
+int nempc_weight_grad(nempc_handle hh, int32_t B, const void* Z, const void* X0, const void* lam, const void* v, const void* w,
+                      const int32_t* skip, void* gtheta, void* stream) {
+    const char* const who = "nempc_weight_grad";
+    if (int rc = point_enter(hh, B, who, ": rolling_window > 1 handles are not supported (the sweep is built for the rows of a "
+                                         "plain model)")) return rc;
+    if ((lam == nullptr) != (v == nullptr)) return fail(NEMPC_EINVAL, who, ": lam and v are given both or neither");
+    if (!gtheta) return fail(NEMPC_EINVAL, who, ": gtheta is null");
+    if (B > 0 && (!Z || !X0 || !w)) return fail(NEMPC_EINVAL, who, ": null argument (Z, X0 and w are required)");
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    if (int rc = check_network_inputs(h, B, who)) return rc;
+    DeviceGuard dg(h.cfg.device);
+    if (!dg.ok) return fail(NEMPC_EHIP, who, ": hipSetDevice failed");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (B == 0) {        // the empty sum
+        NEMPC_HIP(hipMemsetAsync(gtheta, 0, (size_t)wgrad_n_params(h) * h.esz, s));
+        return NEMPC_OK;
+    }
+    return launch_weight_grad(h, B, Z, X0, lam, v, w, skip, gtheta, s);
 }
 
 int nempc_rollout(nempc_handle hh, int32_t B, const void* X0, void* Z, void* f, void* stream) {

@@ -226,6 +226,8 @@ struct Handle {
     double* d_sens_ws = nullptr;             // nempc_sensitivity (plain models): gains | value matrices | Sigma | scratch (sens_ws_doubles)
     double* d_kktsolve_ws = nullptr;         // nempc_kkt_solve: per-problem global working sets, when its plan needs them
     size_t kktsolve_ws_doubles = 0;          //   (allocated and grown by the call itself, kernels_kktsolve.hip)
+    void* d_wgrad_ws = nullptr;              // nempc_weight_grad: factor matrices | sweep scratch | slabs | kept-problem list
+    size_t wgrad_ws_bytes = 0;               //   (allocated and grown by the call itself, kernels_wgrad.hip)
     void* d_rk4_stage = nullptr; // RK4 Hessian pipeline (allocated on first use): (Bmax*H, 4, nin + 2*nx*nin) stage records,
     void* d_rk4_nu = nullptr;    //   (Bmax*H, 4, nx) stage multipliers,
     void* d_rk4_ht = nullptr;    //   (Bmax*H, 4, nin, nin) contracted stage Hessians
@@ -367,6 +369,14 @@ int launch_kkt_solve(Handle& h, int B, const void* Z, const void* tiles, const v
                      const double* lb, const double* ub, int nrhs, const void* rz, const void* rg, void* v, void* w, void* gx0,
                      int32_t* status, hipStream_t s);
 void kktsolve_free(Handle& h);
+
+// ---- kernels_wgrad.hip : gradient with respect to the network's weights (nempc_weight_grad)
+long long wgrad_n_params(const Handle& h);
+// lam / v both or neither; skip (B) device or null; gtheta (P) is overwritten.  Grows Handle::d_wgrad_ws (a device
+// synchronisation) when the plan needs more than it holds
+int launch_weight_grad(Handle& h, int B, const void* Z, const void* X0, const void* lam, const void* v, const void* w,
+                       const int32_t* skip, void* gtheta, hipStream_t s);
+void wgrad_free(Handle& h);
 
 // ---- solver.hip : batched Gauss-Newton SQP (host driver; its kernels are in solver_args.h and the solver_*_impl.h headers,
 // which only solver.hip includes)

@@ -755,6 +755,78 @@ class CallbackEngine:
                 res[key] = res[key][:, 0]
         return res
 
+    # ------------------------------------------------------------------ the network's weights as parameters
+    @property
+    def n_params(self):
+        """P = sum_l (in_l + 1) * out_l (nempc_n_params): the length of `weight_grad`'s flat result"""
+        P = ctypes.c_int64()
+        _lib.check(self._wgrad_fn("nempc_n_params")(self._handle, ctypes.byref(P)))
+        return int(P.value)
+
+    def _wgrad_fn(self, name):
+        fn = getattr(self.lib, name, None)
+        if fn is None:
+            raise RuntimeError(f"the loaded libnempc.so has no {name}; rebuild it")
+        return fn
+
+    def set_weights(self, weights, biases):
+        """Replace the network's weights and biases (nempc_set_weights on the live handle: objective, bindings, workspaces
+        stay).  Shapes must be those the engine was built with.  Synchronises the device first: the library frees and
+        re-allocates its weight buffers, and queued work may still read them."""
+        ws = [np.ascontiguousarray(w, dtype=np.float64) for w in weights]
+        bs = [np.ascontiguousarray(b, dtype=np.float64).reshape(-1) for b in biases]
+        if len(ws) != len(self._weights) or len(bs) != len(self._biases):
+            raise ValueError(f"expected {len(self._weights)} weight matrices and as many biases")
+        for l, (w, b) in enumerate(zip(ws, bs)):
+            if w.shape != self._weights[l].shape or b.shape != self._biases[l].shape:
+                raise ValueError(f"layer {l}: expected kernel {self._weights[l].shape} and bias {self._biases[l].shape}, "
+                                 f"got {w.shape} and {b.shape}")
+        nl = len(ws)
+        dp = ctypes.POINTER(ctypes.c_double)
+        Wp = (dp * nl)(*[w.ctypes.data_as(dp) for w in ws])
+        bp = (dp * nl)(*[b.ctypes.data_as(dp) for b in bs])
+        torch.cuda.synchronize(self.device)
+        _lib.check(self.lib.nempc_set_weights(self._handle, Wp, bp))
+        self._weights, self._biases = ws, bs
+
+    def weight_grad(self, Z, X0, w, lam=None, v=None, skip=None, flat=False):
+        """gtheta = d/dtheta sum_b sum_t ( w_{b,t} . Phi_t + lam_{b,t} . (T_t v_{b,[t]}) ), theta = the network's weights and
+        biases (nempc_weight_grad; Z, X0, lam, v, w held fixed).  Z (B,n), X0 (B,nx), w (B,H*nx) in defect order; lam (B,m)
+        and v (B,n) both or neither -- without them the second term drops and the result is the gradient of a defect-weighted
+        loss; with `kkt_solve`'s (v, w) the cotangent of theta behind the solution is -gtheta.  skip (B,) int32 or bool, or
+        None: problems with a non-zero entry contribute exact zeros, whatever (NaN included) their lam / v / w hold.  Returns
+        [(dW_0, db_0), (dW_1, db_1), ...] as views of one new flat device tensor in the layout of the weights, or that tensor
+        (n_params,) with flat=True.  Bitwise reproducible from call to call.  Asynchronous on the current torch stream, except
+        a call that has to allocate or grow the handle's workspace for it (the first one)."""
+        fn = self._wgrad_fn("nempc_weight_grad")
+        B = int(Z.shape[0])
+        self._check_in(Z, (B, self.n), "Z")
+        self._check_in(X0, (B, self.nx), "X0")
+        self._check_in(w, (B, self.H * self.nx), "w")
+        if (lam is None) != (v is None):
+            raise ValueError("lam and v are given both or neither")
+        if lam is not None:
+            self._check_in(lam, (B, self.m), "lam")
+            self._check_in(v, (B, self.n), "v")
+        if skip is not None:
+            if not isinstance(skip, torch.Tensor) or skip.device != self.device or tuple(skip.shape) != (B,):
+                raise ValueError(f"skip must be a ({B},) tensor on {self.device}")
+            skip = skip.to(torch.int32).contiguous()
+        if self.rolling_window == 1:      # (a rolling-window handle is refused by the library, history bound or not)
+            self._check_extra(B)
+        self.reserve(B)
+        g = torch.empty(self.n_params, dtype=self.dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(fn(self._handle, B, _ptr(Z), _ptr(X0), _ptr(lam), _ptr(v), _ptr(w), _ptr(skip), _ptr(g), self._stream()))
+        if flat:
+            return g
+        out, at = [], 0
+        for wl in self._weights:
+            i, o = wl.shape
+            out.append((g[at:at + i * o].view(i, o), g[at + i * o:at + (i + 1) * o]))
+            at += (i + 1) * o
+        return out
+
     def sync(self):
         _lib.check(self.lib.nempc_sync(self._handle, self._stream()))
 
