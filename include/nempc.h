@@ -538,6 +538,12 @@ int nempc_kernel_variant(nempc_handle h);
  * (NEMPC_KERNEL_LAYERED); 0 = none yet */
 int nempc_last_row_kernel(nempc_handle h);
 
+/* which kernel wrote the dense Jacobian of the handle's most recent nempc_eval: 0 no dense matrix asked for, 1 the row launch
+ * itself (the fused fixed-shape launch, rows_coop_kernel writing the dense rows), 2 assemble_dense_kernel (per-problem
+ * grid), 3 post_kernel (the same with the objective blocks), 4 post_flat_kernel (one flat stream of 16-byte vectors, with or
+ * without the objective blocks), 5 post_scatter_kernel (a resident matrix: the structural non-zeros alone) */
+int nempc_last_dense_writer(nempc_handle h);
+
 /* network kernel the handle's most recent nempc_hess (or solver iteration) launched for the Lagrangian blocks: 1 generic
  * (rowhess_valu_kernel), 2 cooperative matrix-core, forward-over-reverse (rowhess_coop_kernel), 3 wave-per-tile
  * matrix-core (rowhess_mfma_kernel), 4 compiled for the problem's shape, layer-wise contraction (rowhess_coopfx_kernel);

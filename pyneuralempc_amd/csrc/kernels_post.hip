@@ -11,6 +11,7 @@
 #include "kernels_obj_impl.h"
 #include "kernels_kkt_impl.h"
 #include "bounds_bind_impl.h"
+#include "post_plan.h"
 
 namespace nempc {
 
@@ -46,8 +47,7 @@ __global__ __launch_bounds__(64) void objective_tracking_kernel(int B, int H, in
 // grid (ceil(m*n / (256 * kAsmVPT * 16/sizeof(T))), B)
 // each lane produces VPT x 16 bytes (2 doubles / 4 floats per store), the VPT stores of a lane 256 lanes apart so
 // that every store instruction of a wave is contiguous; the map / tile loads of all VPT vectors are issued
-// before the first store (memory-level parallelism instead of one dependent L2 round trip per store)
-constexpr int kAsmVPT = 4;
+// before the first store (memory-level parallelism instead of one dependent L2 round trip per store); kAsmVPT: post_plan.h
 template <typename T>
 __device__ __forceinline__ void assemble_dense_body(int b, int mn, int tile_elems, const int32_t* __restrict__ map,
                                                     const T* __restrict__ tiles, T* __restrict__ jac) {
@@ -150,18 +150,9 @@ __global__ __launch_bounds__(256) void post_flat_kernel(int nb_asm, int B, int m
         if (bb[u] < (unsigned)B) *reinterpret_cast<vecT*>(jac + (size_t)bb[u] * mn + ee[u]) = v[u];
 }
 
-// host side: can the flat kernel handle (B, mn)?  magic = ceil(2^32 / mn) is exact for numerators < 2^32 / (magic*mn - 2^32)
+// host side: can the flat kernel handle (B, mn)?  (post_plan.h: the rule, the reciprocal and why it is exact)
 inline bool flat_ok(const Handle& h, int B, const void* jac, unsigned* magic) {
-    const unsigned mn = (unsigned)h.m * (unsigned)h.n;
-    const unsigned NV = 16 / (unsigned)h.esz;
-    if (mn % NV != 0 || (reinterpret_cast<uintptr_t>(jac) & 15) != 0) return false;
-    if ((unsigned long long)B * mn >= (1ull << 32)) return false;
-    const unsigned long long mg = ((1ull << 32) + mn - 1) / mn;
-    const unsigned long long err = mg * mn - (1ull << 32);          // < mn
-    const unsigned long long max_numer = (unsigned long long)mn + 256ull * kAsmVPT * NV;
-    if (mg >= (1ull << 32) || err * max_numer >= (1ull << 32)) return false;
-    *magic = (unsigned)mg;
-    return true;
+    return post_flat_plan((unsigned)h.m * (unsigned)h.n, B, (unsigned)h.esz, jac, magic) == POST_FLAT_OK;
 }
 
 // sparse contract in one launch: band-pattern values for all problems as one flat stream (blocks < nb_asm), objective
@@ -294,10 +285,9 @@ int launch_post_flat(Handle& h, int B, unsigned magic, const void* tiles, void* 
                      hipStream_t s) {
     const int mn = h.m * h.n;
     const int te = h.cfg.H * h.cfg.nx * h.nin;
-    const int NV = 16 / (int)sizeof(T);
-    const long long total = (long long)B * mn;
-    const int nb_asm = (int)((total + 256LL * kAsmVPT * NV - 1) / (256LL * kAsmVPT * NV));
-    const int nb_obj = (f || grad) ? (B + 3) / 4 : 0;
+    const int nb_asm = post_flat_blocks((unsigned)mn, B, (unsigned)sizeof(T));
+    const int nb_obj = (f || grad) ? post_objective_blocks(B) : 0;
+    h.last_dense_writer = DENSE_WRITER_FLAT;
     ObjOffsets o = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     hipLaunchKernelGGL(post_flat_kernel<T>, dim3((unsigned)(nb_asm + nb_obj)), dim3(256), 0, s, nb_asm, B, mn, magic, te,
                        h.d_dense_map, (const T*)tiles, (T*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o, (const T*)h.d_obj,
@@ -311,9 +301,13 @@ template <typename T>
 int launch_post_scatter(Handle& h, int B, const void* tiles, void* jac, const void* Z, void* f, void* grad, hipStream_t s) {
     const int nnz = (int)h.jac_rows.size();
     const int te = h.cfg.H * h.cfg.nx * h.nin;
-    const unsigned long long total = (unsigned long long)B * nnz;
-    const int nb_asm = (int)((total + 255) / 256), nb_obj = (f || grad) ? (B + 3) / 4 : 0;
-    const unsigned long long magic = ~0ull / (unsigned long long)nnz + 1;      // (as launch_post_sparse)
+    const int nb_asm = post_nnz_blocks(nnz, B), nb_obj = (f || grad) ? post_objective_blocks(B) : 0;
+    unsigned long long magic = 0;
+    if (!post_recip64(nnz, &magic)) {
+        set_error("launch_post_scatter: a pattern of fewer than two entries");
+        return NEMPC_EUNSUPPORTED;
+    }
+    h.last_dense_writer = DENSE_WRITER_SCATTER;
     ObjOffsets o = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     hipLaunchKernelGGL(post_scatter_kernel<T>, dim3((unsigned)(nb_asm + nb_obj)), dim3(256), 0, s, nb_asm, B, nnz, magic,
                        h.m * h.n, te, h.d_sparse_map, h.d_sparse_pos, (const T*)tiles, (T*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
@@ -332,8 +326,8 @@ int launch_assemble_dense(Handle& h, int B, const void* tiles, void* jac, hipStr
                                         : launch_post_flat<float>(h, B, magic, tiles, jac, nullptr, nullptr, nullptr, s);
     const int mn = h.m * h.n;
     const int te = h.cfg.H * h.cfg.nx * h.nin;
-    const int per_block = 256 * kAsmVPT * (16 / (int)h.esz);
-    const dim3 block(256), grid((unsigned)((mn + per_block - 1) / per_block), (unsigned)B);
+    const dim3 block(256), grid((unsigned)post_problem_blocks((unsigned)mn, (unsigned)h.esz), (unsigned)B);
+    h.last_dense_writer = DENSE_WRITER_ASSEMBLE;
     if (h.cfg.dtype == NEMPC_F64)
         hipLaunchKernelGGL(assemble_dense_kernel<double>, grid, block, 0, s, mn, te, h.d_dense_map,
                            (const double*)tiles, (double*)jac);
@@ -355,10 +349,10 @@ int launch_post(Handle& h, int B, const void* tiles, void* jac, const void* Z, v
                                         : launch_post_flat<float>(h, B, magic, tiles, jac, Z, f, grad, s);
     const int mn = h.m * h.n;
     const int te = h.cfg.H * h.cfg.nx * h.nin;
-    const int per_block = 256 * kAsmVPT * (16 / (int)h.esz);
-    const int nb = (mn + per_block - 1) / per_block;
+    const int nb = post_problem_blocks((unsigned)mn, (unsigned)h.esz);
     ObjOffsets o = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     const dim3 block(256), grid((unsigned)(nb + 1), (unsigned)B);
+    h.last_dense_writer = DENSE_WRITER_POST;
     if (h.cfg.dtype == NEMPC_F64)
         hipLaunchKernelGGL(post_kernel<double>, grid, block, 0, s, nb, mn, te, h.d_dense_map, (const double*)tiles,
                            (double*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o, (const double*)h.d_obj, (const double*)Z,
@@ -375,10 +369,13 @@ int launch_post_sparse(Handle& h, int B, const void* tiles, void* vals, const vo
                        hipStream_t s) {
     const int nnz = (int)h.jac_rows.size();
     const int te = h.cfg.H * h.cfg.nx * h.nin;
-    const unsigned long long total = (unsigned long long)B * nnz;
-    const int nb_asm = (int)((total + 255) / 256), nb_obj = (B + 3) / 4;
-    // ceil(2^64 / nnz): floor((2^64 - 1) / nnz) + 1 (nnz >= 2 always: every row has its -1 and a control column)
-    const unsigned long long magic = ~0ull / (unsigned long long)nnz + 1;
+    const int nb_asm = post_nnz_blocks(nnz, B), nb_obj = post_objective_blocks(B);
+    // ceil(2^64 / nnz): floor((2^64 - 1) / nnz) + 1 (post_plan.h; nnz >= 2 always: every row has its -1 and a control column)
+    unsigned long long magic = 0;
+    if (!post_recip64(nnz, &magic)) {
+        set_error("launch_post_sparse: a pattern of fewer than two entries");
+        return NEMPC_EUNSUPPORTED;
+    }
     ObjOffsets o = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     if (h.cfg.dtype == NEMPC_F64)
         hipLaunchKernelGGL(post_sparse_kernel<double>, dim3((unsigned)(nb_asm + nb_obj)), dim3(256), 0, s, nb_asm, B, nnz,

@@ -785,6 +785,12 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
     static const int resident_on = env_int("NEMPC_JAC_RESIDENT", 1);
     const bool jres = jac_dense && resident_on && h.jac_resident.resident(jac_dense, B);
     auto then_tracking = [&](int r) { return r == NEMPC_OK && trk ? launch_objective_tracking(h, B, Z, f, grad, nullptr, s) : r; };
+    // which kernel writes the dense matrix (nempc_last_dense_writer): the row launches below, or the assembly launch itself
+    h.last_dense_writer = DENSE_WRITER_NONE;
+    auto rows_wrote_dense = [&](int r) {
+        if (r == NEMPC_OK && jac_dense) h.last_dense_writer = DENSE_WRITER_ROWS;
+        return then_tracking(r);
+    };
     int rc;
     if (need_rows) {
         // defects only (IpoptProblem.constraints on its own): the matrix-core kernel skips its reverse sweeps
@@ -795,7 +801,7 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
         // output (g with f / grad: what a line-search trial needs) the same launch runs its forward passes only
         if (!jac_sparse && (jac_dense || ff || gf) && h.variant == NEMPC_KERNEL_MFMA) {
             rc = launch_eval_fused(h, B, Z, X0, gout, jac_tiles, jac_dense, ff, gf, s, nullptr, jres);
-            if (rc != NEMPC_EUNSUPPORTED) return then_tracking(rc);
+            if (rc != NEMPC_EUNSUPPORTED) return rows_wrote_dense(rc);
         }
         // sparse contract (what a real Ipopt run wants: SURVEY 8f-2; the reference hands cyipopt the dense (m, n),
         // optimizer/ipopt.py:88-96): rows, band values in nempc_jac_structure order and the objective from ONE launch -- of
@@ -813,7 +819,7 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
             // (a resident matrix gets its zeros from this launch all the same: correct, and measured not worth a flag in
             // rows_coop_kernel -- DESIGN 5.2)
             rc = launch_rows_mfma_dense(h, B, Z, X0, gout, jac_tiles, jac_dense, ff, gf, s);
-            if (rc != NEMPC_EUNSUPPORTED) return then_tracking(rc);
+            if (rc != NEMPC_EUNSUPPORTED) return rows_wrote_dense(rc);
         }
         rc = h.variant != NEMPC_KERNEL_VALU ? launch_rows_mfma(h, B, Z, X0, gout, tiles, s)
                                             : launch_rows_valu(h, B, Z, X0, gout, tiles, s);
@@ -1069,6 +1075,11 @@ int nempc_last_hess_kernel(nempc_handle hh) {
 int nempc_last_lq_kernel(nempc_handle hh) {
     if (!hh) return fail(NEMPC_EINVAL, "nempc_last_lq_kernel: null handle");
     return reinterpret_cast<Handle*>(hh)->last_lq_kernel;
+}
+
+int nempc_last_dense_writer(nempc_handle hh) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_last_dense_writer: null handle");
+    return reinterpret_cast<Handle*>(hh)->last_dense_writer;
 }
 
 int nempc_last_row_kernel(nempc_handle hh) {

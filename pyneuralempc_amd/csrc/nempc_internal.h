@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "jac_resident.h"
+#include "post_plan.h"
 #include "nempc.h"
 
 namespace nempc {
@@ -244,7 +245,8 @@ struct Handle {
     void* comm = nullptr;        // comm.hip: RCCL communicator of the u0 all-gather
     mutable int last_row_kernel = 0;  // 1 valu, 2 coop, 3 wave-tile
     mutable int last_hess_kernel = 0; // 1 valu, 2 coop, 3 wave-tile, 4 fixed shape; + 10: inside the RK4 pipeline (nempc_last_hess_kernel)
-    mutable int last_lq_kernel = 0;   // 1 thread per problem from global memory, 2 thread per problem in LDS, 3 wave per problem in LDS, 4 parallel-in-time scan (nempc_last_lq_kernel)
+    mutable int last_dense_writer = 0;  // DenseWriter (post_plan.h) of the most recent nempc_eval (nempc_last_dense_writer)
+    mutable int last_lq_kernel = 0;  // 1 thread per problem from global memory, 2 thread per problem in LDS, 3 wave per problem in LDS, 4 parallel-in-time scan (nempc_last_lq_kernel)
     mutable int last_rollout_kernel = 0; // 1 generic, 2 matrix-core (nempc_last_rollout_kernel)
 };
 

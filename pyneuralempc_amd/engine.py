@@ -184,6 +184,19 @@ class CallbackEngine:
                 5: "rows_coop_kernel+dense", 6: "rows_coopfx_kernel+sparse", 7: "rows_coop_kernel+sparse", 8: "layered_gemm_kernel"}[
             self.lib.nempc_last_row_kernel(self._handle)]
 
+    DENSE_WRITERS = {0: None, 1: "row_launch", 2: "assemble_dense_kernel", 3: "post_kernel", 4: "post_flat_kernel",
+                     5: "post_scatter_kernel"}
+
+    @property
+    def last_dense_writer(self):
+        """Name of the kernel that wrote jac_dense in the most recent evaluation: "row_launch" (the fused fixed-shape launch
+        or rows_coop_kernel+dense), "assemble_dense_kernel", "post_kernel", "post_flat_kernel", "post_scatter_kernel" (the
+        engine's own resident buffer); None when no dense matrix was asked for."""
+        fn = getattr(self.lib, "nempc_last_dense_writer", None)
+        if fn is None:
+            raise RuntimeError("this libnempc.so has no nempc_last_dense_writer")
+        return self.DENSE_WRITERS[fn(self._handle)]
+
     @property
     def last_hess_kernel(self):
         """Name of the network kernel the most recent Lagrangian-Hessian evaluation launched ("rk4:" prefix: inside the RK4
