@@ -182,17 +182,6 @@ __device__ __forceinline__ void coop_zero_rows(T* o_jac, unsigned r0, int nrows,
     }
 }
 
-struct CoopLayout {  // element offsets inside dynamic LDS
-    int w0f;         // layer-0 fragments          ks * MT * 64
-    int tail;        // seed | bias_l | biasL      (off.total - off.seed)
-    int x;           // exchange buffer            2 halves of TPW * MT * 256
-    int xhalf;
-    int part;        // partials                   (1+nx) * TPW * MT * NR * 64
-    int scratch;     // per-tile scratch           TPW * scratch_per_tile
-    int rowinfo;     // (b, t) per tile row as int2  TPW * 16 * 2 ints (stored in T-sized slots)
-    int total;
-};
-
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt(0): in this kernel
 // that would stall the first barrier on the weight-slice loads (first needed a layer later) and every
 // pass's last barrier on the acknowledgement of its global stores.
@@ -200,29 +189,7 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// Cotangents swept together in the reverse pass: two when their accumulators are no bigger than those of a 2-tile
-// fp64 pass (fp64: single-tile passes; fp32: passes of <= 2 tiles).  Two independent MFMA chains per wave and half the
-// exchange barriers -- what the latency-bound cases (single-tile passes, 8-wave workgroups) lack.
-template <typename T>
-__host__ __device__ constexpr int coop_kg(int NT) {
-#ifdef NEMPC_EXP_KG1
-    return 1;
-#endif
-    return NT * (int)sizeof(T) <= 8 ? 2 : 1;   // three at a time for fp32 single-tile passes measured no better (576 vs 568 us at C3)
-}
-// exchange-buffer slots (16-row activation sets) a pass may publish at once
-template <typename T>
-__host__ __device__ constexpr int coop_slots(int TPW) {
-    int m = 0;
-    for (int nt = 1; nt <= TPW; ++nt) m = nt * coop_kg<T>(nt) > m ? nt * coop_kg<T>(nt) : m;
-    return m;
-}
-
-template <typename T>
-__host__ __device__ inline int coop_nr(int nin) {
-    return sizeof(T) == 8 ? (nin + 3) / 4 : 4;
-}
-
+// (coop_kg, coop_slots, coop_nr: mfma_plan.h -- the host sizes the LDS with them)
 template <typename T, int WP, int NH>
 struct CoopWeights {  // this wave's slices, one element per lane per fragment
     static constexpr int MT = WP / 16;
@@ -688,7 +655,7 @@ __device__ __forceinline__ void coop_pass(const CoopCtx<T>& cx, const CoopWeight
     COOP_STAMP(50);
 }
 
-// Everything the kernel needs, prepared on the host (try_launch_coop): the kernel itself does no setup arithmetic.
+// Everything the kernel needs, prepared on the host (launch_coop, kernels_mfma_typed.inc): the kernel itself does no setup arithmetic.
 // The first version derived its constants in the kernel -- three 64-bit scalar divisions, a dozen dependent
 // s_load round trips into a 100-SGPR budget -- and spent 1.7 us between wave start and its first vector load
 // (tools/diag_stamps.py); now the fields the first loads need come first and the rest arrives in their shadow.
@@ -721,7 +688,7 @@ struct CoopArgs {
     unsigned inv32_jrow, inv32_nx;
     double DT;
     RowGather gk;
-    // the objective of the batch from this launch too (dense evaluations of plain models, launch_rows_mfma_dense): f (B) and
+    // the objective of the batch from this launch too (dense evaluations of plain models, ROW_COOP_DENSE): f (B) and
     // grad (B, n), either may be null; P = the handle's objective table; every workgroup takes a slice of the problems
     void* obj_f;
     void* obj_grad;

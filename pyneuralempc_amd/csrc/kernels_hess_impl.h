@@ -259,8 +259,6 @@ __global__ __launch_bounds__(256) void rowhess_mfma_kernel(HessParams hp) {
 }
 
 template <typename T, int ACT>
-int launch_rowhess_mfma_act(const Handle& h, HessParams hp, hipStream_t s);
-template <typename T>
-int launch_rowhess_mfma_typed(const Handle& h, HessParams hp, hipStream_t s);
+int launch_rowhess_mfma_act(const HessParams& hp, const MfmaHessPlan& plan, hipStream_t s);
 
 }  // namespace nempc

@@ -15,15 +15,6 @@
 
 namespace nempc {
 
-struct HessCoopLayout {  // element offsets inside dynamic LDS
-    int w0f;             // layer-0 fragments                               ks * MT * 64
-    int tail;            // p0tab | wLb | seed | bias_l | biasL             off.total - off.p0tab
-    int x, xhalf;        // exchange buffer: 2 halves of TG * MT * 256
-    int part;            // K-split partials of the Hessian columns         TG * MT * NR * 64
-    int scratch;         // xi0[16][nin] | lam[16][nx] | ex[16][ne] | H[16][nin][nin]
-    int total;
-};
-
 template <typename T, int WP, int NH, int TG, int ACT>
 __global__ __launch_bounds__((WP / 16) * 64, 2) void rowhess_coop_kernel(HessParams hp, HessCoopLayout lay) {
     using Ops = MfmaOps<T>;

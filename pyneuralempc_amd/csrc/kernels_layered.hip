@@ -449,7 +449,7 @@ static int layered_hess(Handle& h, int B, const void* Z, const void* X0, const v
     if (!layered_hess_usable(h)) return NEMPC_EUNSUPPORTED;
     if (!stage && h.cfg.integrator == NEMPC_RK4) return launch_rowhess_rk4_layered(h, B, Z, X0, lam, out, s, nullptr, nullptr);
     LG_TRY(layered_prepare(h, true));
-    h.last_hess_kernel = 5;
+    h.last_hess_kernel = HESS_LAYERED;
     return h.cfg.dtype == NEMPC_F64 ? run_layered_hess<double>(h, B, Z, X0, lam, out, s, stage, stride, nrows)
                                     : run_layered_hess<float>(h, B, Z, X0, lam, out, s, stage, stride, nrows);
 }
@@ -464,7 +464,7 @@ int launch_rowhess_layered_direct(Handle& h, long long nrows, const void* stage,
 int launch_rows_layered_stages(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* stage_out, int stage_stride,
                                hipStream_t s) {
     LG_TRY(layered_prepare(h, false));
-    h.last_row_kernel = 8;
+    h.last_row_kernel = ROW_LAYERED;
     return h.cfg.dtype == NEMPC_F64 ? run_layered<double>(h, B, Z, X0, g, tiles, s, stage_out, stage_stride)
                                     : run_layered<float>(h, B, Z, X0, g, tiles, s, stage_out, stage_stride);
 }

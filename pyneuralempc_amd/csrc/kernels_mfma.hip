@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #include "kernels_hess_impl.h"
 
@@ -18,42 +19,17 @@ int padded_width(const Handle& h) {
     return 0;
 }
 
-MfmaOffsets make_offsets(int wp, int nh, int ks, int nx, int nin, int esz) {
-    const int MT = wp / 16;
-    MfmaOffsets o{};
-    int p = 0;
-    o.w0f = p; p += ks * MT * 64;
-    for (int l = 1; l < nh; ++l) { o.wf[l] = p; p += MT * MT * 4 * 64; }
-    o.wLf = p; p += MT * 4 * 64;
-    for (int l = 1; l < nh; ++l) { o.wb[l] = p; p += MT * MT * 4 * 64; }
-    o.w0b = p; p += MT * 4 * 64 * ((nin + 15) / 16);   // one fragment set per 16-row block of the input dimension
-    o.p0tab = p; p += nin * MT * 16;
-    o.wLb = p; p += ((nx + 3) / 4) * MT * 64;
-    o.seed = p; p += nx * MT * 16;
-    for (int l = 0; l < nh; ++l) { o.bias[l] = p; p += MT * 16; }
-    o.biasL = p; p += 16;
-    o.total = p;
-    // cooperative-kernel copies (16-byte aligned: every size above is a multiple of 16 elements)
-    const int vec = 16 / esz;
-    const int nfrag = (nh - 1) * 2 * MT * 4 + 8;
-    o.coop_small = p;
-    o.coop_small_elems = ks * MT * 64 + (o.total - o.seed);
-    p += (o.coop_small_elems + 15) & ~15;
-    o.coop_nload = (nfrag + vec - 1) / vec;
-    o.coop_slices = p;
-    p += MT * o.coop_nload * 64 * vec;
-    o.fx_small = p;
-    o.fx_small_elems = o.coop_small_elems + nin * MT * 16;
-    p += (o.fx_small_elems + 15) & ~15;
-    o.grand_total = p;
-    return o;
-}
-
-int scratch_elems(const Handle& h) {
-    const int nx = h.cfg.nx, nin = h.nin;
-    // xi0 | k | acck | J [| dk | accdk | dkn : RK4 chain only] | x_t slot (cooperative kernel) | extra inputs
-    const int njs = h.cfg.integrator == NEMPC_RK4 ? 4 : 1;
-    return 16 * nin + 2 * 16 * nx + njs * 16 * nx * nin + 16 * nx + 16 * h.ne;
+// what the plans (mfma_plan.h) look at, of a handle and a call's batch size
+MfmaShape mfma_shape(const Handle& h, int B) {
+    MfmaShape s{};
+    s.esz = (int)h.esz; s.wp = h.mfma.wp; s.nh = h.mfma.nh;
+    s.nx = h.cfg.nx; s.nu = h.cfg.nu; s.nin = h.nin; s.ne = h.ne; s.window = h.w;
+    s.integrator = h.cfg.integrator; s.variant = h.variant; s.act = h.mfma_act;
+    s.n = h.n; s.m = h.m; s.B = B; s.H = h.cfg.H; s.num_cus = h.num_cus;
+    s.obj_elems = h.d_obj ? obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu).total : 0;
+    s.hess_scatter = h.d_hess_smap && h.hess_n_orph >= 0;
+    s.layered_hess = h.layered_hess;
+    return s;
 }
 
 }  // namespace
@@ -68,8 +44,9 @@ bool mfma_supported(const Handle& h) {
     // one wave's scratch is the least LDS any row kernel asks for (the streamed wave-per-tile kernel with one wave per
     // workgroup); with the RK4 chain's four Jacobian slots an fp64 16-state / 20-input stage needs 168.5 KiB, more than the
     // CU's 160 KiB, and every launch of it was refused (hipFuncSetAttribute: invalid argument) -- such shapes are not ours
-    const size_t esz = h.cfg.dtype == NEMPC_F64 ? sizeof(double) : sizeof(float);
-    if ((size_t)((scratch_elems(h) + 1) & ~1) * esz > (size_t)160 * 1024) return false;
+    MfmaShape s{};
+    s.esz = h.cfg.dtype == NEMPC_F64 ? 8 : 4; s.nx = h.cfg.nx; s.nin = h.nin; s.ne = h.ne; s.integrator = h.cfg.integrator;
+    if ((size_t)s.rows_scratch() * s.esz > (size_t)160 * 1024) return false;
     return padded_width(h) != 0;
 }
 
@@ -81,7 +58,7 @@ bool mfma_supported(const Handle& h) {
 bool mfma_slower_than_layered(const Handle& h) {
     if (h.mfma_act != NEMPC_ACT_RUNTIME || h.cfg.dtype != NEMPC_F64 || !layered_supported(h)) return false;
     const int nh = h.nl - 1, MT = padded_width(h) / 16;
-    return ((nh - 1) * 2 * MT * 4 + 8) * 2 > 144;          // coop_fits_registers<double, WP, NH>() of kernels_mfma_typed.inc
+    return !coop_fits_registers(8, 16 * MT, nh);
 }
 
 // Shapes whose ROWS are fastest on the register-resident kernels but whose Lagrangian blocks are not (fp64, padded width 128,
@@ -195,9 +172,9 @@ int mfma_pack_weights(Handle& h, const double* const* W, const double* const* b)
 }
 
 // one translation unit per (dtype, hidden activation) defines these (kernels_mfma_typed.inc)
-#define NEMPC_DECL_ACT(T, A)                                                                       \
-    template <> int launch_rows_mfma_act<T, A>(const Handle& h, MfmaParams p, hipStream_t s);     \
-    template <> int launch_rowhess_mfma_act<T, A>(const Handle& h, HessParams hp, hipStream_t s);
+#define NEMPC_DECL_ACT(T, A)                                                                                  \
+    template <> int launch_rows_mfma_act<T, A>(const MfmaParams& p, const MfmaRowsPlan& plan, hipStream_t s);    \
+    template <> int launch_rowhess_mfma_act<T, A>(const HessParams& hp, const MfmaHessPlan& plan, hipStream_t s);
 #define NEMPC_DECL_ACTS(T)                                                                         \
     NEMPC_DECL_ACT(T, NEMPC_ACT_TANH) NEMPC_DECL_ACT(T, NEMPC_ACT_RELU) NEMPC_DECL_ACT(T, NEMPC_ACT_SIGMOID) \
     NEMPC_DECL_ACT(T, NEMPC_ACT_SOFTPLUS) NEMPC_DECL_ACT(T, NEMPC_ACT_ELU) NEMPC_DECL_ACT(T, NEMPC_ACT_RUNTIME)
@@ -206,39 +183,29 @@ NEMPC_DECL_ACTS(float)
 #undef NEMPC_DECL_ACTS
 #undef NEMPC_DECL_ACT
 
-template <typename T>
-int launch_rows_mfma_typed(const Handle& h, MfmaParams p, hipStream_t s) {
+namespace {
+
+// the typed unit of the handle's dtype and activation (NEMPC_ACT_RUNTIME: per-layer codes in MfmaParams::acts)
+template <typename T, typename P, typename Plan>
+int launch_typed(const Handle& h, const P& p, const Plan& plan, hipStream_t s) {
+    auto go = [&](auto act) {
+        if constexpr (std::is_same_v<P, MfmaParams>) return launch_rows_mfma_act<T, decltype(act)::value>(p, plan, s);
+        else return launch_rowhess_mfma_act<T, decltype(act)::value>(p, plan, s);
+    };
     switch (h.mfma_act) {
-        case NEMPC_ACT_TANH: return launch_rows_mfma_act<T, NEMPC_ACT_TANH>(h, p, s);
-        case NEMPC_ACT_RELU: return launch_rows_mfma_act<T, NEMPC_ACT_RELU>(h, p, s);
-        case NEMPC_ACT_SIGMOID: return launch_rows_mfma_act<T, NEMPC_ACT_SIGMOID>(h, p, s);
-        case NEMPC_ACT_SOFTPLUS: return launch_rows_mfma_act<T, NEMPC_ACT_SOFTPLUS>(h, p, s);
-        case NEMPC_ACT_ELU: return launch_rows_mfma_act<T, NEMPC_ACT_ELU>(h, p, s);
-        case NEMPC_ACT_RUNTIME: return launch_rows_mfma_act<T, NEMPC_ACT_RUNTIME>(h, p, s);      // per-layer codes in p.acts
+        case NEMPC_ACT_TANH: return go(std::integral_constant<int, NEMPC_ACT_TANH>{});
+        case NEMPC_ACT_RELU: return go(std::integral_constant<int, NEMPC_ACT_RELU>{});
+        case NEMPC_ACT_SIGMOID: return go(std::integral_constant<int, NEMPC_ACT_SIGMOID>{});
+        case NEMPC_ACT_SOFTPLUS: return go(std::integral_constant<int, NEMPC_ACT_SOFTPLUS>{});
+        case NEMPC_ACT_ELU: return go(std::integral_constant<int, NEMPC_ACT_ELU>{});
+        case NEMPC_ACT_RUNTIME: return go(std::integral_constant<int, NEMPC_ACT_RUNTIME>{});
     }
-    set_error("launch_rows_mfma: the matrix-core kernels do not take this network's activations");
-    return NEMPC_EUNSUPPORTED;
+    set_error("matrix-core launch: the kernels do not take this network's activations");
+    return NEMPC_EINVAL;
 }
 
-template <typename T>
-int launch_rowhess_mfma_typed(const Handle& h, HessParams hp, hipStream_t s) {
-    switch (h.mfma_act) {
-        case NEMPC_ACT_TANH: return launch_rowhess_mfma_act<T, NEMPC_ACT_TANH>(h, hp, s);
-        case NEMPC_ACT_RELU: return launch_rowhess_mfma_act<T, NEMPC_ACT_RELU>(h, hp, s);
-        case NEMPC_ACT_SIGMOID: return launch_rowhess_mfma_act<T, NEMPC_ACT_SIGMOID>(h, hp, s);
-        case NEMPC_ACT_SOFTPLUS: return launch_rowhess_mfma_act<T, NEMPC_ACT_SOFTPLUS>(h, hp, s);
-        case NEMPC_ACT_ELU: return launch_rowhess_mfma_act<T, NEMPC_ACT_ELU>(h, hp, s);
-        case NEMPC_ACT_RUNTIME: return launch_rowhess_mfma_act<T, NEMPC_ACT_RUNTIME>(h, hp, s);
-    }
-    set_error("launch_rowhess_mfma: the matrix-core kernels do not take this network's activations");
-    return NEMPC_EUNSUPPORTED;
-}
-
-int launch_rows_mfma(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, hipStream_t s) {
-    return launch_rows_mfma_stages(h, B, Z, X0, g, tiles, nullptr, 0, s);
-}
-
-static MfmaParams base_params(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles) {
+// the parameters every matrix-core kernel reads: network, dims, inputs, gather
+MfmaParams base_params(const Handle& h, int B, const void* Z, const void* X0, int ntiles, int scratch_per_wave) {
     MfmaParams p{};
     p.blob = h.mfma.blob;
     p.nx = h.cfg.nx; p.nu = h.cfg.nu; p.nin = h.nin; p.ks = (h.nin + h.ne + 3) / 4; p.mb = (h.nin + 15) / 16;
@@ -250,183 +217,113 @@ static MfmaParams base_params(Handle& h, int B, const void* Z, const void* X0, v
     }
     p.kind = h.cfg.integrator; p.DT = h.cfg.DT;
     p.B = B; p.H = h.cfg.H; p.m = h.m; p.box = h.box ? 1 : 0; p.num_cus = h.num_cus;
-    p.Z = Z; p.X0 = X0; p.g = g; p.tiles = tiles;
+    p.Z = Z; p.X0 = X0;
     p.gk = h.gather();
-    p.ntiles = (int)(((size_t)B * h.cfg.H + 15) / 16);
-    p.scratch_per_wave = (scratch_elems(h) + 1) & ~1;
-    p.dbg = h.d_dbg;
+    p.ntiles = ntiles;
+    p.scratch_per_wave = scratch_per_wave;
     return p;
 }
 
-// Whole hessian-free evaluation (g, dense jac, f, grad [, tiles]) in ONE launch where a fixed-shape kernel covers the
-// problem; NEMPC_EUNSUPPORTED (no error message, nothing launched) tells nempc_eval to take the two-launch path.
-int launch_eval_fused(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* jac, void* f,
-                      void* grad, hipStream_t s, void* sparse, bool jac_resident) {
-    if (!h.mfma.blob || !h.d_obj || (!jac && !f && !grad && !sparse)) return NEMPC_EUNSUPPORTED;
-    if (sparse && (h.w != 1 || jac)) return NEMPC_EUNSUPPORTED;
-    MfmaParams p = base_params(h, B, Z, X0, g, tiles);
-    p.fuse_obj = true;
-    p.fuse_jac = jac; p.fuse_f = f; p.fuse_grad = grad;
-    p.jac_resident = jac && jac_resident;
-    p.fuse_sparse = sparse; p.sp_nnz = (int)h.jac_rows.size();
-    p.obj = h.d_obj;
-    p.oo = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
-    const int rc = h.cfg.dtype == NEMPC_F64 ? launch_rows_mfma_typed<double>(h, p, s) : launch_rows_mfma_typed<float>(h, p, s);
-    if (rc == NEMPC_OK && sparse) h.last_row_kernel = 6;     // the fixed-shape kernel, band values included
-    return rc;
+unsigned lo4(const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15); }
+
+}  // namespace
+
+const MfmaKnobs& mfma_knobs() {
+    static const MfmaKnobs k = [] {
+        MfmaKnobs k;
+        k.fx = env_int("NEMPC_FX", 1); k.hfx = env_int("NEMPC_HFX", 1); k.hfx_eval = env_int("NEMPC_HFX_EVAL", 1);
+        k.gn_fused = env_int("NEMPC_GN_FUSED", 1); k.coop_dense = env_int("NEMPC_COOP_DENSE", 1);
+        k.coop_sparse = env_int("NEMPC_COOP_SPARSE", 1); k.coop_dims = env_int("NEMPC_COOP_DIMS", 1);
+        k.coop_tpw = env_int("NEMPC_COOP_TPW", MfmaKnobs::kUnset); k.fx_tpw = env_int("NEMPC_FX_TPW", 3);
+        k.tile_waves = env_int("NEMPC_TILE_WAVES", 4);
+        return k;
+    }();
+    return k;
 }
 
-// Rows, compact tiles (optional), the band-pattern Jacobian values and the objective from one launch of the cooperative
-// kernel (any shape it takes, plain models): the sparse contract without the tile round trip and the assembly launch.
-// NEMPC_EUNSUPPORTED (nothing launched, no error message) sends nempc_eval to the row + assembly launches.
-int launch_rows_mfma_sparse(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* sparse, void* f,
-                            void* grad, hipStream_t s) {
-    static const int on = env_int("NEMPC_COOP_SPARSE", 1);
-    if (!on || !h.mfma.blob || !sparse || h.w != 1 || ((f || grad) && !h.d_obj)) return NEMPC_EUNSUPPORTED;
-    MfmaParams p = base_params(h, B, Z, X0, g, tiles);
-    p.fuse_sparse = sparse; p.sp_nnz = (int)h.jac_rows.size();
-    if (f || grad) {
-        p.fuse_f = f; p.fuse_grad = grad; p.obj = h.d_obj;
-        p.oo = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
-    }
-    const int rc = h.cfg.dtype == NEMPC_F64 ? launch_rows_mfma_typed<double>(h, p, s) : launch_rows_mfma_typed<float>(h, p, s);
-    if (rc == NEMPC_OK) h.last_row_kernel = 7;        // the cooperative kernel, band values included
-    return rc;
+MfmaRowsPlan mfma_plan_rows(const Handle& h, int B, const RowsOut& o) {
+    RowsWant w;
+    w.bits = (o.tiles || o.need_tiles ? WANT_TILES : 0u) | (o.jac ? WANT_DENSE : 0u) | (o.sparse ? WANT_SPARSE : 0u) |
+             (o.f ? WANT_F : 0u) | (o.grad ? WANT_GRAD : 0u) | (o.stage_out ? WANT_STAGES : 0u) | (o.gn_hvals ? WANT_GN : 0u);
+    w.dense_lo4 = lo4(o.jac); w.sparse_lo4 = lo4(o.sparse);
+    return plan_rows(mfma_shape(h, B), w, mfma_knobs());
 }
 
-// Gauss-Newton Hessian callback (tril values) in ONE launch of the fixed-shape kernel: the blocks sum_i w_i T_i^T T_i are
-// formed and assembled in the row kernel's epilogue.  NEMPC_EUNSUPPORTED (nothing launched) for every other shape, for
-// rolling windows, and when the Hessian map has no scatter form.
-int launch_hess_gn_fused(Handle& h, int B, const void* Z, const void* X0, const void* w, const void* sigma, void* hvals,
-                         hipStream_t s) {
-    static const int on = env_int("NEMPC_GN_FUSED", 1);
-    if (!on || !h.mfma.blob || !hvals || h.w != 1 || !h.d_hess_smap || h.hess_n_orph < 0 || h.cfg.dtype != NEMPC_F64)
-        return NEMPC_EUNSUPPORTED;
-    MfmaParams p = base_params(h, B, Z, X0, h.d_g_ws, nullptr);
-    p.gn_hvals = hvals; p.gn_sigma = sigma; p.gn_w = w; p.gn_smap = h.d_hess_smap;
-    p.gn_objc = (const char*)h.d_obj + (size_t)obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu).total * h.esz;
-    p.gn_nnz = (int)h.hess_rows.size(); p.gn_n_orph = h.hess_n_orph;
-    return launch_rows_mfma_typed<double>(h, p, s);
+MfmaHessPlan mfma_plan_hess(const Handle& h, int B, const HessOut& o) {
+    HessWant w;
+    w.bits = (o.hvals ? HWANT_HVALS : HWANT_BLOCKS) | (o.ev_g ? HWANT_EVAL : 0u) | (o.xi_direct ? HWANT_DIRECT : 0u);
+    w.vdiv = o.vdiv;
+    return plan_hess(mfma_shape(h, B), w, mfma_knobs());
 }
 
-// Rows, compact tiles (optional) and the DENSE Jacobian from one launch of the cooperative kernel (any shape it takes,
-// plain models): background zeros streamed at the start of each pass, non-zeros written with the pass's outputs.
-// NEMPC_EUNSUPPORTED (nothing launched, no error message) sends nempc_eval to the row + assembly launches.
-int launch_rows_mfma_dense(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* jac, void* f,
-                           void* grad, hipStream_t s) {
-    static const int on = env_int("NEMPC_COOP_DENSE", 1);
-    if (!on || !h.mfma.blob || !jac || ((f || grad) && !h.d_obj)) return NEMPC_EUNSUPPORTED;
-    MfmaParams p = base_params(h, B, Z, X0, g, tiles);
-    p.fuse_jac = jac;
-    if (f || grad) {        // the objective from the same launch (its workgroups take slices of the batch after their passes)
-        p.fuse_f = f; p.fuse_grad = grad; p.obj = h.d_obj;
-        p.oo = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
-    }
-    const int rc = h.cfg.dtype == NEMPC_F64 ? launch_rows_mfma_typed<double>(h, p, s) : launch_rows_mfma_typed<float>(h, p, s);
-    if (rc == NEMPC_OK) h.last_row_kernel = 5;        // the cooperative kernel, dense rows included
-    return rc;
-}
-
-int launch_rows_mfma_stages(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* stage_out,
-                            int stage_stride, hipStream_t s) {
+// Rows (defects, compact tiles) and whatever else of the evaluation the planned launch writes itself: the whole
+// hessian-free evaluation or the Gauss-Newton callback on a compiled shape, the dense rows or the band values (and the
+// objective with them) from the cooperative kernel.
+int launch_rows_mfma(Handle& h, int B, const void* Z, const void* X0, const RowsOut& o, hipStream_t s, unsigned* covers) {
     if (!h.mfma.blob) {
         set_error("launch_rows_mfma: weights not packed");
         return NEMPC_ESTATE;
     }
-    MfmaParams p{};
-    p.blob = h.mfma.blob;
-    p.nx = h.cfg.nx; p.nu = h.cfg.nu; p.nin = h.nin; p.ks = (h.nin + h.ne + 3) / 4; p.mb = (h.nin + 15) / 16;
-    p.ne = h.ne; p.extra = h.d_extra;
-    p.off = make_offsets(h.mfma.wp, h.mfma.nh, p.ks, p.nx, p.nin, (int)h.esz);
-    for (int l = 0; l < NEMPC_MFMA_MAX_HIDDEN; ++l) {
-        p.acts.code[l] = l < h.nl - 1 ? h.act[l] : NEMPC_ACT_LINEAR;
-        p.acts.par[l] = l < h.nl - 1 ? h.actp[l] : 0.0;
-    }
-    p.kind = h.cfg.integrator; p.DT = h.cfg.DT;
-    p.B = B; p.H = h.cfg.H; p.m = h.m; p.box = h.box ? 1 : 0; p.num_cus = h.num_cus;
-    p.Z = Z; p.X0 = X0; p.g = g; p.tiles = tiles;
-    p.gk = h.gather();
-    p.stage_out = stage_out; p.stage_stride = stage_stride;
-    p.ntiles = (int)(((size_t)B * h.cfg.H + 15) / 16);
-    p.scratch_per_wave = (scratch_elems(h) + 1) & ~1;
+    const MfmaRowsPlan plan = mfma_plan_rows(h, B, o);
+    if (covers) *covers = plan.covers;
+    MfmaParams p = base_params(h, B, Z, X0, (int)(((size_t)B * h.cfg.H + 15) / 16), mfma_shape(h, B).rows_scratch());
+    p.g = o.g;
+    // (a launch that writes the dense rows / band values itself has no assembly launch behind it: the caller's tiles only)
+    p.tiles = o.tiles ? o.tiles : (o.need_tiles && !(plan.covers & (COVERS_DENSE | COVERS_SPARSE)) ? h.d_tiles_ws : nullptr);
+    p.stage_out = o.stage_out; p.stage_stride = o.stage_stride;
     p.dbg = h.d_dbg;
-    const int rc = h.cfg.dtype == NEMPC_F64 ? launch_rows_mfma_typed<double>(h, p, s) : launch_rows_mfma_typed<float>(h, p, s);
-    if (rc != NEMPC_INTERNAL_USE_VALU) return rc;
-    // an instantiation of the wave-per-tile kernel that is not used (launch_shape): the generic kernel computes the rows.
-    // It has no stage records: the RK4 Hessian pipeline's callers take their generic path on NEMPC_EUNSUPPORTED
-    if (stage_out) return NEMPC_EUNSUPPORTED;
-    if (!tiles && h.variant == NEMPC_KERNEL_MFMA) {
-        // a defect-only launch (they take the wave-per-tile kernel): the cooperative kernel with its tiles into the workspace
-        // is still far ahead of the generic kernel where it serves the shape
-        p.tiles = h.d_tiles_ws;
-        const int rc2 = h.cfg.dtype == NEMPC_F64 ? launch_rows_mfma_typed<double>(h, p, s) : launch_rows_mfma_typed<float>(h, p, s);
-        if (rc2 != NEMPC_INTERNAL_USE_VALU) return rc2;
+    p.fuse_obj = plan.fuse;
+    if (plan.covers & COVERS_DENSE) { p.fuse_jac = o.jac; p.jac_resident = plan.fuse && o.jac_resident; }
+    if (plan.covers & COVERS_SPARSE) { p.fuse_sparse = o.sparse; p.sp_nnz = (int)h.jac_rows.size(); }
+    if (plan.fuse || (plan.covers & COVERS_OBJ)) {      // (the fused evaluation reads the table's size whatever it writes)
+        p.fuse_f = o.f; p.fuse_grad = o.grad; p.obj = h.d_obj;
+        p.oo = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     }
-    return launch_rows_valu(h, B, Z, X0, g, tiles ? tiles : h.d_tiles_ws, s);
-}
-
-int launch_rowhess_mfma(Handle& h, int B, const void* Z, const void* X0, const void* lambda, void* blocks,
-                        hipStream_t s) {
-    if (h.layered_hess) {       // (mfma_hess_on_layered: this shape's blocks are faster on the layer-at-a-time sweeps)
-        const int rc = launch_rowhess_layered(h, B, Z, X0, lambda, blocks, s);
-        if (rc != NEMPC_EUNSUPPORTED) return rc;
+    if (plan.covers & COVERS_GN) {
+        p.g = h.d_g_ws; p.tiles = nullptr;
+        p.gn_hvals = o.gn_hvals; p.gn_sigma = o.gn_sigma; p.gn_w = o.gn_w; p.gn_smap = h.d_hess_smap;
+        p.gn_objc = (const char*)h.d_obj + (size_t)obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu).total * h.esz;
+        p.gn_nnz = (int)h.hess_rows.size(); p.gn_n_orph = h.hess_n_orph;
     }
-    return launch_rowhess_mfma_direct(h, B, Z, X0, lambda, blocks, nullptr, 0, nullptr, 1, s);
+    const int rc = h.cfg.dtype == NEMPC_F64 ? launch_typed<double>(h, p, plan, s) : launch_typed<float>(h, p, plan, s);
+    if (rc == NEMPC_OK) h.last_row_kernel = plan.kernel;
+    return rc;
 }
 
-// blocks and assembly in one launch: the tril values of the Lagrangian Hessian written by the cooperative Hessian kernel
-// itself.  NEMPC_EUNSUPPORTED (nothing launched) when the shape runs on the wave-per-tile kernel or the model has a
-// rolling window (an entry then sums block elements of several rows).
-int launch_rowhess_mfma_hvals(Handle& h, int B, const void* Z, const void* X0, const void* lambda, const void* sigma,
-                              void* hvals, hipStream_t s) {
-    if (h.w != 1 || !h.d_hess_smap || h.hess_n_orph < 0 || h.layered_hess) return NEMPC_EUNSUPPORTED;
-    return launch_rowhess_mfma_direct(h, B, Z, X0, lambda, nullptr, nullptr, 0, nullptr, 1, s, hvals, sigma);
-}
-
-// Lagrangian blocks and the first-order evaluation (defects, compact tiles) of the same rows in ONE launch of the
-// fixed-shape Hessian kernel -- the batched solver's trial point.  NEMPC_EUNSUPPORTED (nothing launched) for other shapes.
-int launch_rowhess_eval_mfma(Handle& h, int B, const void* Z, const void* X0, const void* lambda, void* blocks, void* g,
-                             void* tiles, hipStream_t s) {
-    static const int on = env_int("NEMPC_HFX_EVAL", 1);
-    if (!on || !h.mfma.blob || h.w != 1 || h.ne != 0 || !blocks || !g || !tiles) return NEMPC_EUNSUPPORTED;
-    return launch_rowhess_mfma_direct(h, B, Z, X0, lambda, blocks, nullptr, 0, nullptr, 1, s, nullptr, nullptr, g, tiles);
-}
-
-int launch_rowhess_mfma_direct(Handle& h, int B, const void* Z, const void* X0, const void* lambda, void* blocks,
-                               const void* xi_direct, int xi_stride, const void* lam_direct, int vdiv, hipStream_t s,
-                               void* fuse_hvals, const void* fuse_sigma, void* ev_g, void* ev_tiles) {
+// Lagrangian blocks; on a plan that covers them, the tril values from the kernel itself (out.hvals) or the first-order
+// evaluation of the same rows (out.ev_g / ev_tiles: the batched solver's trial point).  NEMPC_EUNSUPPORTED: out.ev_g on a
+// shape without such a launch.  A handle whose blocks are faster on the layer-at-a-time sweeps (mfma_hess_on_layered) gets
+// them there.
+int launch_rowhess_mfma(Handle& h, int B, const void* Z, const void* X0, const void* lambda, const HessOut& o, hipStream_t s,
+                        unsigned* covers) {
+    if (covers) *covers = 0;
+    if (h.layered_hess && !o.ev_g && !o.xi_direct) {
+        const int rc = launch_rowhess_layered(h, B, Z, X0, lambda, o.blocks, s);
+        if (rc != NEMPC_EUNSUPPORTED) return rc;        // (the layered path's own switch, NEMPC_LAYERED_HESS=0)
+    }
     if (!h.mfma.blob) {
         set_error("launch_rowhess_mfma: weights not packed");
         return NEMPC_ESTATE;
     }
+    const MfmaHessPlan plan = mfma_plan_hess(h, B, o);
+    if (plan.kernel == HESS_NONE) return NEMPC_EUNSUPPORTED;
+    if (covers) *covers = plan.covers;
     HessParams hp{};
-    MfmaParams& p = hp.base;
-    p.blob = h.mfma.blob;
-    p.nx = h.cfg.nx; p.nu = h.cfg.nu; p.nin = h.nin; p.ks = (h.nin + h.ne + 3) / 4; p.mb = (h.nin + 15) / 16;
-    p.ne = h.ne; p.extra = h.d_extra;
-    p.off = make_offsets(h.mfma.wp, h.mfma.nh, p.ks, p.nx, p.nin, (int)h.esz);
-    for (int l = 0; l < NEMPC_MFMA_MAX_HIDDEN; ++l) {
-        p.acts.code[l] = l < h.nl - 1 ? h.act[l] : NEMPC_ACT_LINEAR;
-        p.acts.par[l] = l < h.nl - 1 ? h.actp[l] : 0.0;
-    }
-    p.kind = h.cfg.integrator; p.DT = h.cfg.DT;
-    p.B = B; p.H = h.cfg.H; p.m = h.m; p.box = h.box ? 1 : 0; p.num_cus = h.num_cus;
-    p.Z = Z; p.X0 = X0; p.g = nullptr; p.tiles = nullptr;
-    p.gk = h.gather();
-    p.ntiles = (int)(((size_t)B * h.cfg.H * (xi_direct ? vdiv : 1) + 15) / 16);
-    hp.xi_direct = xi_direct; hp.xi_stride = xi_stride; hp.lam_direct = lam_direct; hp.vdiv = vdiv;
-    p.scratch_per_wave = (16 * h.nin + 16 * h.cfg.nx + 16 * h.nin * h.nin + 16 * h.ne + 1) & ~1;
-    p.dbg = nullptr;
-    hp.lambda = lambda; hp.blocks = blocks;
-    hp.ev_g = ev_g; hp.ev_tiles = ev_tiles;
-    if (fuse_hvals) {       // the kernel assembles the tril values itself (launch_rowhess_mfma_hvals)
-        hp.hvals = fuse_hvals; hp.sigma = fuse_sigma; hp.smap = h.d_hess_smap;
+    hp.base = base_params(h, B, Z, X0, (int)(((size_t)B * h.cfg.H * (o.xi_direct ? o.vdiv : 1) + 15) / 16),
+                          mfma_shape(h, B).hess_scratch());
+    const MfmaParams& p = hp.base;
+    hp.xi_direct = o.xi_direct; hp.xi_stride = o.xi_stride; hp.lam_direct = o.lam_direct; hp.vdiv = o.vdiv;
+    hp.lambda = lambda; hp.blocks = (plan.covers & COVERS_HVALS) ? nullptr : o.blocks;
+    hp.ev_g = o.ev_g; hp.ev_tiles = o.ev_tiles;
+    if (plan.covers & COVERS_HVALS) {       // the kernel assembles the tril values itself
+        hp.hvals = o.hvals; hp.sigma = o.sigma; hp.smap = h.d_hess_smap;
         hp.objc = (const char*)h.d_obj + (size_t)obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu).total * h.esz;
         hp.nnz = (int)h.hess_rows.size(); hp.n_orph = h.hess_n_orph;
     }
     hp.p0tab = p.off.p0tab; hp.wLb = p.off.wLb; hp.ksx = (h.cfg.nx + 3) / 4;
-    return h.cfg.dtype == NEMPC_F64 ? launch_rowhess_mfma_typed<double>(h, hp, s)
-                                    : launch_rowhess_mfma_typed<float>(h, hp, s);
+    const int rc = h.cfg.dtype == NEMPC_F64 ? launch_typed<double>(h, hp, plan, s) : launch_typed<float>(h, hp, plan, s);
+    if (rc == NEMPC_OK) h.last_hess_kernel = plan.kernel;
+    return rc;
 }
 
 }  // namespace nempc

@@ -25,23 +25,7 @@
 
 namespace nempc {
 
-constexpr int kMaxKs = 8;   // first-layer k-steps: network inputs (window + extras) up to 32
-
-struct MfmaOffsets {  // element offsets into the packed blob
-    int w0f, wLf, w0b, seed, biasL;
-    int p0tab, wLb;  // Hessian kernel tables: first-layer rows W_0[p,:], output-layer fragments for W_L lambda
-    int wf[NEMPC_MFMA_MAX_HIDDEN], wb[NEMPC_MFMA_MAX_HIDDEN], bias[NEMPC_MFMA_MAX_HIDDEN];
-    int total;
-    // cooperative row kernel: the same numbers once more, laid out for its prologue (kernels_coop_impl.h) --
-    //   coop_small   [w0f | seed | bias_l | biasL] contiguous (one flat copy to LDS),
-    //   coop_slices  per wave: its register-resident fragments (wf, wb per hidden layer, wL, w0b) as 16-byte
-    //                lane vectors, load k of lane = element ((wave * coop_nload + k) * 64 + lane) * VEC
-    int coop_small, coop_small_elems, coop_slices, coop_nload;
-    //   fx_small     [w0f | seed | bias_l | biasL | p0tab]: the fixed-shape kernel's tables (p0tab = first-layer rows per
-    //                lane, for its vector-unit skinny layers)
-    int fx_small, fx_small_elems;
-    int grand_total;
-};
+static_assert(kActRuntime == NEMPC_ACT_RUNTIME && kMfmaMaxHidden == NEMPC_MFMA_MAX_HIDDEN, "mfma_plan.h restates them");
 
 struct MfmaParams {
     const void* blob;
@@ -66,7 +50,7 @@ struct MfmaParams {
     int stage_stride;      // elements per record = nin + 2*nx*nin
     long long* dbg;        // diagnostic builds only (-DNEMPC_STAMPS): per-wave phase stamps of workgroup 0
     // fused evaluation (fixed-shape kernel only): dense Jacobian and objective from the same launch
-    bool fuse_obj;         // one-launch evaluation asked for (launch_eval_fused); fuse_jac may be null (no dense matrix)
+    bool fuse_obj;         // one-launch evaluation (MfmaRowsPlan::fuse); fuse_jac may be null (no dense matrix)
     bool jac_resident;     // fuse_jac's structural zeros are in place (nempc_jac_dense_resident): the launch writes the non-zeros
                            // only.  (Host-side; it sits in fuse_obj's padding -- the kernels that take this struct keep their layout.)
     void* fuse_jac;
@@ -76,7 +60,7 @@ struct MfmaParams {
     void* fuse_grad;
     const void* obj;
     ObjOffsets oo;
-    // Gauss-Newton Hessian callback from the row launch (fixed-shape kernel only, launch_hess_gn_fused)
+    // Gauss-Newton Hessian callback from the row launch (fixed-shape kernel only, COVERS_GN)
     void* gn_hvals;
     const void* gn_sigma;
     const void* gn_w;
@@ -483,11 +467,9 @@ int launch_one(const MfmaParams& p, int waves, int grid, size_t lds_bytes, hipSt
     return NEMPC_OK;
 }
 
-// picks the instantiation for (WP, NH, weights-in-LDS): one translation unit per (dtype, hidden activation)
-// (kernels_mfma_typed.inc); launch_rows_mfma_typed dispatches on the handle's activation (kernels_mfma.hip)
+// launches the instantiation a plan (mfma_plan.h) names: one translation unit per (dtype, hidden activation)
+// (kernels_mfma_typed.inc); kernels_mfma.hip dispatches on the handle's dtype and activation
 template <typename T, int ACT>
-int launch_rows_mfma_act(const Handle& h, MfmaParams p, hipStream_t s);
-template <typename T>
-int launch_rows_mfma_typed(const Handle& h, MfmaParams p, hipStream_t s);
+int launch_rows_mfma_act(const MfmaParams& p, const MfmaRowsPlan& plan, hipStream_t s);
 
 }  // namespace nempc

@@ -147,6 +147,8 @@ int run_small_kernels(Handle& h, size_t R, const void* lambda, void* blocks, int
 
 }  // namespace
 
+bool rk4hess_supported(const Handle& h) { return congruence_waves(h) >= 1; }
+
 void rk4hess_free(Handle& h) {
     for (void** p : {&h.d_rk4_stage, &h.d_rk4_nu, &h.d_rk4_ht}) {
         if (*p) (void)hipFree(*p);
@@ -160,24 +162,26 @@ int launch_rowhess_rk4_mfma(Handle& h, int B, const void* Z, const void* X0, con
     const int stride = nin + 2 * nx * nin;
     const size_t Rcap = (size_t)h.cfg.max_batch * h.cfg.H, R = (size_t)B * h.cfg.H;
     int rc;
-    if (congruence_waves(h) < 1) return NEMPC_EUNSUPPORTED;
+    if (!rk4hess_supported(h)) return NEMPC_EUNSUPPORTED;       // (the callers ask first: not reached)
     if ((rc = dev_alloc_rk4(&h.d_rk4_stage, Rcap * 4 * stride * h.esz))) return rc;
     if ((rc = dev_alloc_rk4(&h.d_rk4_nu, Rcap * 4 * nx * h.esz))) return rc;
     if ((rc = dev_alloc_rk4(&h.d_rk4_ht, Rcap * 4 * nin * nin * h.esz))) return rc;
     // 1. stage records; the launch's defects and tiles go to the caller (the batched solver wants them anyway) or to
     //    the handle's scratch outputs
-    if ((rc = launch_rows_mfma_stages(h, B, Z, X0, g_out ? g_out : h.d_g_ws, tiles_out ? tiles_out : h.d_tiles_ws,
-                                      h.d_rk4_stage, stride, s)))
-        return rc;
+    RowsOut ro;
+    ro.g = g_out ? g_out : h.d_g_ws; ro.tiles = tiles_out ? tiles_out : h.d_tiles_ws;
+    ro.stage_out = h.d_rk4_stage; ro.stage_stride = stride;
+    if ((rc = launch_rows_mfma(h, B, Z, X0, ro, s))) return rc;
     const bool f64 = h.cfg.dtype == NEMPC_F64;
     // 2. stage multipliers
     if ((rc = f64 ? run_small_kernels<double>(h, R, lambda, blocks, stride, false, s)
                   : run_small_kernels<float>(h, R, lambda, blocks, stride, false, s)))
         return rc;
     // 3. contracted network Hessians at the four stage inputs
-    if ((rc = launch_rowhess_mfma_direct(h, B, Z, X0, lambda, h.d_rk4_ht, h.d_rk4_stage, stride, h.d_rk4_nu, 4, s)))
-        return rc;
-    h.last_hess_kernel += 10;      // (the network kernel of step 3, inside the pipeline)
+    HessOut ho;
+    ho.blocks = h.d_rk4_ht; ho.xi_direct = h.d_rk4_stage; ho.xi_stride = stride; ho.lam_direct = h.d_rk4_nu; ho.vdiv = 4;
+    if ((rc = launch_rowhess_mfma(h, B, Z, X0, lambda, ho, s))) return rc;
+    h.last_hess_kernel += HESS_IN_RK4;      // (the network kernel of step 3, inside the pipeline)
     // 4. congruence sum
     return f64 ? run_small_kernels<double>(h, R, lambda, blocks, stride, true, s)
                : run_small_kernels<float>(h, R, lambda, blocks, stride, true, s);
@@ -203,7 +207,7 @@ int launch_rowhess_rk4_layered(Handle& h, int B, const void* Z, const void* X0, 
                   : run_small_kernels<float>(h, R, lambda, blocks, stride, false, s)))
         return rc;
     if ((rc = launch_rowhess_layered_direct(h, (long long)R * 4, h.d_rk4_stage, stride, h.d_rk4_nu, h.d_rk4_ht, s))) return rc;
-    h.last_hess_kernel += 10;
+    h.last_hess_kernel += HESS_IN_RK4;
     return f64 ? run_small_kernels<double>(h, R, lambda, blocks, stride, true, s)
                : run_small_kernels<float>(h, R, lambda, blocks, stride, true, s);
 }

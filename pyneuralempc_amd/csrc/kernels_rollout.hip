@@ -471,7 +471,7 @@ int launch_rollout(Handle& h, int B, const void* X0, void* Z, int which, hipStre
     int rc;
     if (mfma) rc = h.cfg.dtype == NEMPC_F64 ? launch_mfma_typed<double>(h, net, B, X0, Z, s) : launch_mfma_typed<float>(h, net, B, X0, Z, s);
     else rc = h.cfg.dtype == NEMPC_F64 ? launch_wave_typed<double>(h, net, B, X0, Z, s) : launch_wave_typed<float>(h, net, B, X0, Z, s);
-    if (rc == NEMPC_OK) h.last_rollout_kernel = mfma ? 2 : 1;
+    if (rc == NEMPC_OK) h.last_rollout_kernel = mfma ? ROLLOUT_MFMA : ROLLOUT_WAVE;
     return rc;
 }
 

@@ -516,7 +516,7 @@ int ensure_valu_ws(Handle& h) {
 int launch_rows_valu(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, hipStream_t s) {
     // networks outside the register-resident kernels' shapes: the rows come from the layer-at-a-time GEMM pipeline
     if (h.layered) return launch_rows_layered(h, B, Z, X0, g, tiles, s);
-    h.last_row_kernel = 1;
+    h.last_row_kernel = ROW_VALU;
     const size_t rows = (size_t)B * h.cfg.H;
     const size_t Rcap = (size_t)h.cfg.max_batch * h.cfg.H;
     const dim3 block(256), grid((unsigned)((rows + 255) / 256));
@@ -546,7 +546,7 @@ int launch_rowhess_valu(Handle& h, int B, const void* Z, const void* X0, const v
     const dim3 block(256), grid((unsigned)((rows + 255) / 256));
     NetDev nd = make_netdev(h);
     WsOff o = ws_offsets(h);
-    h.last_hess_kernel = 1;
+    h.last_hess_kernel = HESS_VALU;
     if (h.cfg.dtype == NEMPC_F64)
         hipLaunchKernelGGL(rowhess_valu_kernel<double>, grid, block, 0, s, nd, o, h.cfg.integrator, h.cfg.DT, B, h.cfg.H,
                            Rcap, (const double*)Z, (const double*)X0, (const double*)lambda, h.m, (double*)blocks,

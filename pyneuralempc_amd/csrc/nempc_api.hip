@@ -773,7 +773,7 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
     if (need_rows)
         if (int rc = check_network_inputs(h, B, "nempc_eval")) return rc;
     // per-problem tracking data (nempc_bind_tracking): the launches that fuse the shared objective get no f / grad (ff, gf)
-    // and the binding's own kernel follows them
+    // and the binding's own kernel follows them (launch_objective below)
     const bool trk = (f || grad) && h.track.on();
     if (trk && B > h.track.B) return fail(NEMPC_EINVAL, "nempc_eval: B exceeds the batch the bound tracking data cover");
     void* const ff = trk ? nullptr : f;
@@ -784,51 +784,42 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
     // a resident dense Jacobian (nempc_jac_dense_resident) has its structural zeros in place: the writers below leave them
     static const int resident_on = env_int("NEMPC_JAC_RESIDENT", 1);
     const bool jres = jac_dense && resident_on && h.jac_resident.resident(jac_dense, B);
-    auto then_tracking = [&](int r) { return r == NEMPC_OK && trk ? launch_objective_tracking(h, B, Z, f, grad, nullptr, s) : r; };
-    // which kernel writes the dense matrix (nempc_last_dense_writer): the row launches below, or the assembly launch itself
+    // which kernel writes the dense matrix (nempc_last_dense_writer): the row launch below, or the assembly launch itself
     h.last_dense_writer = DENSE_WRITER_NONE;
-    auto rows_wrote_dense = [&](int r) {
-        if (r == NEMPC_OK && jac_dense) h.last_dense_writer = DENSE_WRITER_ROWS;
-        return then_tracking(r);
-    };
     int rc;
-    if (need_rows) {
-        // defects only (IpoptProblem.constraints on its own): the matrix-core kernel skips its reverse sweeps
-        const bool need_tiles = jac_dense || jac_tiles || jac_sparse || h.variant == NEMPC_KERNEL_VALU;
-        void* tiles = jac_tiles ? jac_tiles : (need_tiles ? h.d_tiles_ws : nullptr);
-        void* gout = g ? g : h.d_g_ws;
-        // compiled shape: rows, objective and (dense contract) the dense assembly in ONE launch; without a derivative
-        // output (g with f / grad: what a line-search trial needs) the same launch runs its forward passes only
-        if (!jac_sparse && (jac_dense || ff || gf) && h.variant == NEMPC_KERNEL_MFMA) {
-            rc = launch_eval_fused(h, B, Z, X0, gout, jac_tiles, jac_dense, ff, gf, s, nullptr, jres);
-            if (rc != NEMPC_EUNSUPPORTED) return rows_wrote_dense(rc);
-        }
-        // sparse contract (what a real Ipopt run wants: SURVEY 8f-2; the reference hands cyipopt the dense (m, n),
-        // optimizer/ipopt.py:88-96): rows, band values in nempc_jac_structure order and the objective from ONE launch -- of
-        // the fixed-shape kernel on a compiled shape, of the cooperative kernel on every other plain-model shape it takes.
-        // No tile round trip through memory, no assembly launch.
-        if (jac_sparse && !jac_dense && h.variant == NEMPC_KERNEL_MFMA) {
-            rc = launch_eval_fused(h, B, Z, X0, gout, jac_tiles, nullptr, ff, gf, s, jac_sparse);
-            if (rc != NEMPC_EUNSUPPORTED) return then_tracking(rc);
-            rc = launch_rows_mfma_sparse(h, B, Z, X0, gout, jac_tiles, jac_sparse, ff, gf, s);
-            if (rc != NEMPC_EUNSUPPORTED) return then_tracking(rc);
-        }
-        // dense contract on any shape the cooperative kernel takes (plain models): the dense rows AND the objective leave
-        // from the row launch itself -- no assembly launch, no tile round trip through memory, no objective launch
-        if (jac_dense && !jac_sparse && h.variant == NEMPC_KERNEL_MFMA) {
-            // (a resident matrix gets its zeros from this launch all the same: correct, and measured not worth a flag in
-            // rows_coop_kernel -- DESIGN 5.2)
-            rc = launch_rows_mfma_dense(h, B, Z, X0, gout, jac_tiles, jac_dense, ff, gf, s);
-            if (rc != NEMPC_EUNSUPPORTED) return rows_wrote_dense(rc);
-        }
-        rc = h.variant != NEMPC_KERNEL_VALU ? launch_rows_mfma(h, B, Z, X0, gout, tiles, s)
-                                            : launch_rows_valu(h, B, Z, X0, gout, tiles, s);
-        if (rc) return rc;
+    if (need_rows && h.variant == NEMPC_KERNEL_VALU) {
+        void* tiles = jac_tiles ? jac_tiles : h.d_tiles_ws;
+        if ((rc = launch_rows_valu(h, B, Z, X0, g ? g : h.d_g_ws, tiles, s))) return rc;
         // sparse contract with the objective and without the dense matrix: one fused launch
         if (jac_sparse && !jac_dense && (ff || gf)) return launch_post_sparse(h, B, tiles, jac_sparse, Z, ff, gf, s);
         if (jac_sparse && (rc = launch_assemble_sparse(h, B, tiles, jac_sparse, s))) return rc;
         if (jac_dense && (ff || gf)) return launch_post(h, B, tiles, jac_dense, Z, ff, gf, s, jres);
         if (jac_dense && (rc = launch_assemble_dense(h, B, tiles, jac_dense, s, jres))) return rc;
+    } else if (need_rows) {
+        // One plan (mfma_plan.h) says what the row launch writes itself.  Compiled shape: rows, objective and the dense rows
+        // or the band values in ONE launch; without a derivative output (g with f / grad: what a line-search trial needs)
+        // the same launch runs its forward passes only.  Any plain-model shape the cooperative kernel takes: the dense rows
+        // or the band values in nempc_jac_structure order (what a real Ipopt run wants: SURVEY 8f-2; the reference hands
+        // cyipopt the dense (m, n), optimizer/ipopt.py:88-96) AND the objective leave from the row launch -- no assembly
+        // launch, no tile round trip through memory, no objective launch.  (A resident matrix gets its zeros from the
+        // cooperative kernel all the same: correct, and measured not worth a flag in rows_coop_kernel -- DESIGN 5.2.)
+        // Defects only (IpoptProblem.constraints on its own): the matrix-core kernel skips its reverse sweeps.
+        RowsOut ro;
+        ro.g = g ? g : h.d_g_ws; ro.tiles = jac_tiles; ro.need_tiles = jac_dense || jac_sparse;
+        ro.jac = jac_dense; ro.sparse = jac_sparse; ro.f = ff; ro.grad = gf; ro.jac_resident = jres;
+        unsigned covers = 0;
+        if ((rc = launch_rows_mfma(h, B, Z, X0, ro, s, &covers))) return rc;
+        if (covers & COVERS_DENSE) h.last_dense_writer = DENSE_WRITER_ROWS;
+        // what the launch left over: assembly, post, objective
+        const void* tiles = jac_tiles ? jac_tiles : h.d_tiles_ws;
+        const bool obj_left = (ff || gf) && !(covers & COVERS_OBJ);
+        const bool dense_left = jac_dense && !(covers & COVERS_DENSE), sparse_left = jac_sparse && !(covers & COVERS_SPARSE);
+        // sparse contract with the objective and without the dense matrix: one fused launch
+        if (sparse_left && !dense_left && obj_left) return launch_post_sparse(h, B, tiles, jac_sparse, Z, ff, gf, s);
+        if (sparse_left && (rc = launch_assemble_sparse(h, B, tiles, jac_sparse, s))) return rc;
+        if (dense_left && obj_left) return launch_post(h, B, tiles, jac_dense, Z, ff, gf, s, jres);
+        if (dense_left && (rc = launch_assemble_dense(h, B, tiles, jac_dense, s, jres))) return rc;
+        if (covers & COVERS_OBJ) return NEMPC_OK;
     }
     if ((f || grad) && (rc = launch_objective(h, B, Z, f, grad, s))) return rc;
     return NEMPC_OK;
@@ -846,20 +837,21 @@ int nempc_hess(nempc_handle hh, int32_t B, const void* Z, const void* X0, const 
     if (!dg.ok) return fail(NEMPC_EHIP, "nempc_hess: hipSetDevice failed");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int rc;
-    // tril values only, on a cooperative-kernel shape: the Hessian kernel assembles them itself (one launch)
-    if (hvals && !hdense && !hblocks && h.variant != NEMPC_KERNEL_VALU && h.cfg.integrator != NEMPC_RK4) {
-        rc = launch_rowhess_mfma_hvals(h, B, Z, X0, lambda, sigma, hvals, s);
-        if (rc != NEMPC_EUNSUPPORTED) return rc;
-    }
     void* blocks = hblocks ? hblocks : h.d_hess_ws;
+    unsigned covers = 0;
     if (h.variant == NEMPC_KERNEL_VALU) rc = launch_rowhess_valu(h, B, Z, X0, lambda, blocks, s);
     else if (h.cfg.integrator == NEMPC_RK4) {
-        rc = launch_rowhess_rk4_mfma(h, B, Z, X0, lambda, blocks, s);
-        // (a shape whose stage records would come from a wave-per-tile instantiation that is not used: generic kernel)
-        if (rc == NEMPC_EUNSUPPORTED) rc = launch_rowhess_valu(h, B, Z, X0, lambda, blocks, s);
-    } else rc = launch_rowhess_mfma(h, B, Z, X0, lambda, blocks, s);
+        // (a wave's slice of the congruence step does not fit the device's LDS: generic kernel)
+        rc = rk4hess_supported(h) ? launch_rowhess_rk4_mfma(h, B, Z, X0, lambda, blocks, s) : launch_rowhess_valu(h, B, Z, X0, lambda, blocks, s);
+    } else {
+        // tril values only: the compiled-shape and cooperative Hessian kernels assemble them themselves (one launch)
+        HessOut ho;
+        ho.blocks = blocks; ho.sigma = sigma;
+        if (hvals && !hdense && !hblocks) ho.hvals = hvals;
+        rc = launch_rowhess_mfma(h, B, Z, X0, lambda, ho, s, &covers);
+    }
     if (rc) return rc;
-    if (!hvals && !hdense) return NEMPC_OK;
+    if ((!hvals && !hdense) || (covers & COVERS_HVALS)) return NEMPC_OK;
     return launch_assemble_hess(h, B, blocks, sigma, hvals, hdense, s);
 }
 
@@ -874,14 +866,17 @@ int nempc_hess_gn(nempc_handle hh, int32_t B, const void* Z, const void* X0, con
     DeviceGuard dg(h.cfg.device);
     if (!dg.ok) return fail(NEMPC_EHIP, "nempc_hess_gn: hipSetDevice failed");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    // compiled shape, tril values only: blocks and assembly in the row launch's epilogue (one launch)
-    if (hvals && !hdense && !hblocks && h.variant == NEMPC_KERNEL_MFMA) {
-        const int rc1 = launch_hess_gn_fused(h, B, Z, X0, w, sigma, hvals, s);
-        if (rc1 != NEMPC_EUNSUPPORTED) return rc1;
-    }
-    // first-order model only: the row kernel's tiles (no second-order sweep), then the same assembly as nempc_hess
-    int rc = h.variant != NEMPC_KERNEL_VALU ? launch_rows_mfma(h, B, Z, X0, h.d_g_ws, h.d_tiles_ws, s)
-                                            : launch_rows_valu(h, B, Z, X0, h.d_g_ws, h.d_tiles_ws, s);
+    // first-order model only: the row kernel's tiles (no second-order sweep), then the same assembly as nempc_hess.  Compiled
+    // shape, tril values only: blocks and assembly in the row launch's epilogue (one launch)
+    int rc;
+    if (h.variant != NEMPC_KERNEL_VALU) {
+        RowsOut ro;
+        ro.g = h.d_g_ws; ro.tiles = h.d_tiles_ws;
+        if (hvals && !hdense && !hblocks) { ro.gn_hvals = hvals; ro.gn_w = w; ro.gn_sigma = sigma; }
+        unsigned covers = 0;
+        rc = launch_rows_mfma(h, B, Z, X0, ro, s, &covers);
+        if (rc == NEMPC_OK && (covers & COVERS_GN)) return rc;
+    } else rc = launch_rows_valu(h, B, Z, X0, h.d_g_ws, h.d_tiles_ws, s);
     if (rc) return rc;
     // the caller does not ask for the per-row blocks: the assembly forms their elements where it uses them
     if (!hblocks) return (hvals || hdense) ? launch_assemble_hess_gn(h, B, h.d_tiles_ws, w, sigma, hvals, hdense, s) : NEMPC_OK;

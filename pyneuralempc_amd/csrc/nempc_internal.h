@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "jac_resident.h"
+#include "mfma_plan.h"
 #include "post_plan.h"
 #include "nempc.h"
 
@@ -114,10 +115,6 @@ struct MfmaNet {
     size_t blob_elems = 0;
 };
 
-// internal return code of the matrix-core row launchers: "this launch belongs on the generic kernel" (translated by
-// launch_rows_mfma_stages; never leaves the library)
-constexpr int NEMPC_INTERNAL_USE_VALU = -9001;
-
 struct ObjHost {   // host copy of the objective parameters (doubles), re-uploaded whenever one of them changes
     std::vector<double> Q, R, xref, uref, cx, cu;
 };
@@ -139,20 +136,6 @@ struct BoundBind {
     int B = 0;
     bool on() const { return xlb || xub || ulb || uub; }
 };
-
-// Launch geometry of the cooperative kernels: `per_cu` co-resident workgroups on each of the device's `num_cus`
-// compute units (fewer when there are fewer tiles), each owning a contiguous run of tiles_per_wg (+1 for the first
-// tiles_rem workgroups) 16-row tiles.  num_cus comes from hipDeviceProp_t::multiProcessorCount of the handle's device
-// (256 on an MI355X in SPX mode; a partitioned mode or another gfx950 part reports its own count).
-struct GridPlan {
-    int grid, tiles_per_wg, tiles_rem;
-};
-inline GridPlan plan_grid(int ntiles, int num_cus, int per_cu) {
-    long long g = (long long)(num_cus < 1 ? 1 : num_cus) * (per_cu < 1 ? 1 : per_cu);
-    if (g > ntiles) g = ntiles;
-    if (g < 1) g = 1;
-    return GridPlan{(int)g, ntiles / (int)g, ntiles % (int)g};
-}
 
 struct Handle {
     nempc_config cfg{};
@@ -243,11 +226,11 @@ struct Handle {
     bool layered_pairs_valid = false;
     void* solver_ws = nullptr;   // solver.hip
     void* comm = nullptr;        // comm.hip: RCCL communicator of the u0 all-gather
-    mutable int last_row_kernel = 0;  // 1 valu, 2 coop, 3 wave-tile
-    mutable int last_hess_kernel = 0; // 1 valu, 2 coop, 3 wave-tile, 4 fixed shape; + 10: inside the RK4 pipeline (nempc_last_hess_kernel)
+    mutable int last_row_kernel = ROW_NONE;    // RowKernel (mfma_plan.h) of the most recent row launch (nempc_last_row_kernel)
+    mutable int last_hess_kernel = HESS_NONE;  // HessKernel [+ HESS_IN_RK4] of the most recent Lagrangian blocks (nempc_last_hess_kernel)
     mutable int last_dense_writer = 0;  // DenseWriter (post_plan.h) of the most recent nempc_eval (nempc_last_dense_writer)
-    mutable int last_lq_kernel = 0;  // 1 thread per problem from global memory, 2 thread per problem in LDS, 3 wave per problem in LDS, 4 parallel-in-time scan (nempc_last_lq_kernel)
-    mutable int last_rollout_kernel = 0; // 1 generic, 2 matrix-core (nempc_last_rollout_kernel)
+    mutable int last_lq_kernel = LQ_NONE;            // LqKernel of the most recent solve's plan (nempc_last_lq_kernel)
+    mutable int last_rollout_kernel = ROLLOUT_NONE;  // RolloutKernel of the most recent roll-out (nempc_last_rollout_kernel)
 };
 
 struct ObjOffsets {  // element offsets into Handle::d_obj
@@ -305,31 +288,38 @@ bool mfma_supported(const Handle& h);
 bool mfma_slower_than_layered(const Handle& h);    // AUTO prefers the layered path (kernels_mfma.hip)
 bool mfma_hess_on_layered(const Handle& h);        // AUTO: rows on the register-resident kernels, Lagrangian blocks on the layered sweeps
 int mfma_pack_weights(Handle& h, const double* const* W, const double* const* b);
-int launch_rows_mfma(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, hipStream_t s);
-int launch_eval_fused(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* jac, void* f,
-                      void* grad, hipStream_t s, void* sparse = nullptr, bool jac_resident = false);
-int launch_rows_mfma_sparse(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* sparse, void* f,
-                            void* grad, hipStream_t s);
-int launch_rows_mfma_dense(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* jac, void* f,
-                           void* grad, hipStream_t s);
-int launch_hess_gn_fused(Handle& h, int B, const void* Z, const void* X0, const void* w, const void* sigma, void* hvals,
-                         hipStream_t s);
+// What a matrix-core launch writes, null = not asked for.  The entry points plan (mfma_plan.h), fill the kernel parameters and
+// launch what the plan names; `covers` (may be null) receives the plan's COVERS_* mask: what is left over (assembly, post,
+// objective) is the caller's.  NEMPC_EUNSUPPORTED (nothing launched, no error message) means "the plan says not ours", nothing else.
+struct RowsOut {
+    void *g = nullptr, *tiles = nullptr;    // defects; compact tiles (null with need_tiles: the handle's workspace)
+    bool need_tiles = false;                // an assembly launch behind this one reads the tiles
+    void *jac = nullptr, *sparse = nullptr, *f = nullptr, *grad = nullptr;
+    bool jac_resident = false;              // jac's structural zeros are in place (nempc_jac_dense_resident)
+    void* stage_out = nullptr;              // RK4 Hessian pipeline: stage records, stage_stride elements each
+    int stage_stride = 0;
+    void* gn_hvals = nullptr;               // Gauss-Newton tril values with weights gn_w (null = ones) and gn_sigma
+    const void *gn_w = nullptr, *gn_sigma = nullptr;
+};
+struct HessOut {
+    void* blocks = nullptr;                           // (B, H, nin, nin), or the contracted stage Hessians in direct mode
+    void* hvals = nullptr;                            // tril values with sigma, and nothing else asked for
+    const void* sigma = nullptr;
+    void *ev_g = nullptr, *ev_tiles = nullptr;        // blocks + first-order evaluation of the same rows (batched solver)
+    const void *xi_direct = nullptr, *lam_direct = nullptr;   // direct mode (RK4 pipeline): vdiv records of xi_stride elements per row
+    int xi_stride = 0, vdiv = 1;
+};
+const MfmaKnobs& mfma_knobs();
+MfmaRowsPlan mfma_plan_rows(const Handle& h, int B, const RowsOut& out);
+MfmaHessPlan mfma_plan_hess(const Handle& h, int B, const HessOut& out);
+int launch_rows_mfma(Handle& h, int B, const void* Z, const void* X0, const RowsOut& out, hipStream_t s, unsigned* covers = nullptr);
+int launch_rowhess_mfma(Handle& h, int B, const void* Z, const void* X0, const void* lambda, const HessOut& out, hipStream_t s,
+                        unsigned* covers = nullptr);
 void mfma_free(Handle& h);
-int launch_rowhess_mfma(Handle& h, int B, const void* Z, const void* X0, const void* lambda, void* blocks,
-                        hipStream_t s);
-int launch_rowhess_mfma_hvals(Handle& h, int B, const void* Z, const void* X0, const void* lambda, const void* sigma,
-                              void* hvals, hipStream_t s);
-int launch_rows_mfma_stages(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, void* stage_out,
-                            int stage_stride, hipStream_t s);
-int launch_rowhess_mfma_direct(Handle& h, int B, const void* Z, const void* X0, const void* lambda, void* blocks,
-                               const void* xi_direct, int xi_stride, const void* lam_direct, int vdiv, hipStream_t s,
-                               void* fuse_hvals = nullptr, const void* fuse_sigma = nullptr, void* ev_g = nullptr,
-                               void* ev_tiles = nullptr);
-int launch_rowhess_eval_mfma(Handle& h, int B, const void* Z, const void* X0, const void* lambda, void* blocks, void* g,
-                             void* tiles, hipStream_t s);
 
 // ---- kernels_rk4hess.hip : RK4 Lagrangian blocks on the matrix cores (stage records -> stage multipliers ->
 //      contracted network Hessians of the four stage inputs -> congruence sum)
+bool rk4hess_supported(const Handle& h);     // a wave's slice of the congruence step fits the device's LDS (else: generic kernel)
 int launch_rowhess_rk4_mfma(Handle& h, int B, const void* Z, const void* X0, const void* lambda, void* blocks,
                             hipStream_t s, void* g_out = nullptr, void* tiles_out = nullptr);
 void rk4hess_free(Handle& h);

@@ -464,7 +464,7 @@ struct Solve {
         if constexpr (sizeof(T) == 8)
             if (lq_scan && a.use_lds && !lq_wave) lqk = solver_lq_kernel<T, 2, 1, true, true>;
         // what ran, for nempc_last_lq_kernel: a forced wave (or scan) kernel whose working set does not fit is plan 1
-        h.last_lq_kernel = !a.use_lds ? 1 : (lq_wave ? 3 : (sizeof(T) == 8 && lq_scan ? 4 : 2));
+        h.last_lq_kernel = !a.use_lds ? LQ_THREAD_GLOBAL : (lq_wave ? LQ_WAVE_LDS : (sizeof(T) == 8 && lq_scan ? LQ_SCAN : LQ_THREAD_LDS));
         const size_t lds_max = a.use_lds ? lds_bytes(std::min(std::max(max_ppw(), 1), 16)) : 0;
         NEMPC_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lqk), lds_max));
         return NEMPC_OK;
@@ -556,12 +556,23 @@ struct Solve {
     // ---- callbacks.  Plain models: the handle's launches on the solver's buffers.  Rolling: gather the caller's
     //      variables, launch on them, spread the results into the window-state form (RollTables)
     int launch_rows(int nb, const void* Zs, const void* X0s, void* g, void* tiles, void* tiles_scratch) {
-        if (h.variant != NEMPC_KERNEL_VALU) return launch_rows_mfma(h, nb, Zs, X0s, g, tiles, s);
+        if (h.variant != NEMPC_KERNEL_VALU) return launch_rows_mfma(h, nb, Zs, X0s, fused_eval_out(g, tiles, nullptr, nullptr), s);
         return launch_rows_valu(h, nb, Zs, X0s, g, tiles ? tiles : tiles_scratch, s);
     }
     int launch_blocks(int nb, const void* Zs, const void* X0s, const void* lam, void* blocks) {
-        if (h.variant != NEMPC_KERNEL_VALU) return launch_rowhess_mfma(h, nb, Zs, X0s, lam, blocks, s);
+        if (h.variant != NEMPC_KERNEL_VALU) return launch_rowhess_mfma(h, nb, Zs, X0s, lam, blocks_eval_out(blocks, nullptr, nullptr), s);
         return launch_rowhess_valu(h, nb, Zs, X0s, lam, blocks, s);
+    }
+    // The launches a compiled shape has, asked of the plan (mfma_plan.h) at the call's batch size (several gates depend on it):
+    // blocks + defects + tiles from one launch of the Hessian kernel ...
+    HessOut blocks_eval_out(void* blocks, void* g, void* tiles) const { HessOut ho; ho.blocks = blocks; ho.ev_g = g; ho.ev_tiles = tiles; return ho; }
+    bool has_blocks_eval(int nb, const HessOut& ho) const {
+        return h.variant != NEMPC_KERNEL_VALU && h.mfma.blob && (mfma_plan_hess(h, nb, ho).covers & COVERS_EVAL);
+    }
+    // ... and defects, tiles (or neither: forward passes only), f and grad from one launch of the row kernel
+    RowsOut fused_eval_out(void* g, void* tiles, void* f, void* grad) const { RowsOut ro; ro.g = g; ro.tiles = tiles; ro.f = f; ro.grad = grad; return ro; }
+    bool has_fused_eval(int nb, const RowsOut& ro) const {
+        return h.variant != NEMPC_KERNEL_VALU && h.mfma.blob && (mfma_plan_rows(h, nb, ro).covers & COVERS_OBJ);
     }
     // everything at an iterate: defects, tiles, f, gradient, Lagrangian blocks (into the iterate's buffers); a trial point
     // (lam_aug = null): defects only, into gt (the acceptance kernel evaluates the objective from the augmented table itself)
@@ -602,22 +613,22 @@ struct Solve {
             fused_eval = true;
             rc = have_blocks ? NEMPC_OK : launch_blocks(Bact, Zc, X0c, lam, ws.hblk);
         } else if (rk4_pipeline) {
-            rc = launch_rowhess_rk4_mfma(h, Bact, Zc, X0c, lam, ws.hblk, s, ws.g, ws.tiles);
-            if (rc == NEMPC_EUNSUPPORTED) {
-                // (a shape whose stage records would come from a wave-per-tile instantiation that is not used: rows through
-                //  the matrix-core entry point -- it falls back by itself -- and the blocks from the generic kernel)
-                if ((rc = launch_rows_mfma(h, Bact, Zc, X0c, ws.g, ws.tiles, s))) return rc;
+            if (rk4hess_supported(h)) rc = launch_rowhess_rk4_mfma(h, Bact, Zc, X0c, lam, ws.hblk, s, ws.g, ws.tiles);
+            else {
+                // (a wave's slice of the congruence step does not fit the device's LDS: rows through the matrix-core entry
+                //  point and the blocks from the generic kernel)
+                if ((rc = launch_rows(Bact, Zc, X0c, ws.g, ws.tiles, nullptr))) return rc;
                 rc = launch_rowhess_valu(h, Bact, Zc, X0c, lam, ws.hblk, s);
             }
-        } else if (carry && hess_trial &&
-                   (rc = launch_rowhess_eval_mfma(h, Bact, Zc, X0c, lam, ws.hblk, ws.g, ws.tiles, s)) != NEMPC_EUNSUPPORTED) {
+        } else if (const HessOut ho = blocks_eval_out(ws.hblk, ws.g, ws.tiles); carry && hess_trial && has_blocks_eval(Bact, ho)) {
             // first iterate (and the one after a compaction) through the kernel the trial points go through -- the same
             // arithmetic whichever way an iterate's evaluation was obtained: blocks, defects, tiles; f and grad below
+            rc = launch_rowhess_mfma(h, Bact, Zc, X0c, lam, ho, s);
         } else {
             // compiled shapes: defects, tiles, f and grad from one launch
-            fused_eval = h.variant == NEMPC_KERNEL_MFMA && !tracking &&
-                         (rc = launch_eval_fused(h, Bact, Zc, X0c, ws.g, ws.tiles, nullptr, ws.f, ws.grad, s)) != NEMPC_EUNSUPPORTED;
-            if (!fused_eval) rc = launch_rows(Bact, Zc, X0c, ws.g, ws.tiles, nullptr);
+            const RowsOut ro = fused_eval_out(ws.g, ws.tiles, ws.f, ws.grad);
+            fused_eval = h.variant == NEMPC_KERNEL_MFMA && !tracking && has_fused_eval(Bact, ro);
+            rc = fused_eval ? launch_rows_mfma(h, Bact, Zc, X0c, ro, s) : launch_rows(Bact, Zc, X0c, ws.g, ws.tiles, nullptr);
             if (rc) return rc;
             rc = launch_blocks(Bact, Zc, X0c, lam, ws.hblk);
         }
@@ -729,26 +740,30 @@ struct Solve {
             a.carry = 0; a.hblk_t = nullptr;
             if (carry && hess_trial) {
                 // blocks, defects and tiles of the trial point from one launch (the acceptance kernel evaluates the objective)
-                rc = launch_rowhess_eval_mfma(h, nb, ws.Zt, X0t, ws.lam_t, ws.hblk_t, ws.gt, ws.tiles_t, s);
-                if (rc == NEMPC_EUNSUPPORTED) hess_trial = false;
-                else { trial_done = true; a.carry = 1; a.hblk_t = ws.hblk_t; }
+                const HessOut ho = blocks_eval_out(ws.hblk_t, ws.gt, ws.tiles_t);
+                if (!has_blocks_eval(nb, ho)) hess_trial = false;
+                else {
+                    rc = launch_rowhess_mfma(h, nb, ws.Zt, X0t, ws.lam_t, ho, s);
+                    trial_done = true; a.carry = 1; a.hblk_t = ws.hblk_t;
+                }
             }
             if (carry && !trial_done && tracking) carry = false;      // (that launch fuses the shared objective)
             if (carry && !trial_done) {
                 // full evaluation of the trial point (tiles and gradient too): it is the next iterate's if accepted
-                fused_trial = (rc = launch_eval_fused(h, nb, ws.Zt, X0t, ws.gt, ws.tiles_t, nullptr, ws.ft, ws.grad_t, s)) !=
-                              NEMPC_EUNSUPPORTED;
+                const RowsOut ro = fused_eval_out(ws.gt, ws.tiles_t, ws.ft, ws.grad_t);
+                fused_trial = has_fused_eval(nb, ro);
                 if (!fused_trial) carry = false;      // not a compiled shape
-                else a.carry = 1;
+                else { rc = launch_rows_mfma(h, nb, ws.Zt, X0t, ro, s); a.carry = 1; }
             }
             if (trial_done) {
             } else if (rolling) {
                 rc = roll_eval(ws.Zt, nullptr);
             } else {
-                if (!fused_trial)
-                    fused_trial = h.variant == NEMPC_KERNEL_MFMA && !tracking &&
-                        (rc = launch_eval_fused(h, nb, ws.Zt, X0t, ws.gt, nullptr, nullptr, ws.ft, nullptr, s)) != NEMPC_EUNSUPPORTED;
-                if (!fused_trial) rc = launch_rows(nb, ws.Zt, X0t, ws.gt, nullptr, h.d_tiles_ws);
+                if (!fused_trial) {
+                    const RowsOut ro = fused_eval_out(ws.gt, nullptr, ws.ft, nullptr);
+                    fused_trial = h.variant == NEMPC_KERNEL_MFMA && !tracking && has_fused_eval(nb, ro);
+                    rc = fused_trial ? launch_rows_mfma(h, nb, ws.Zt, X0t, ro, s) : launch_rows(nb, ws.Zt, X0t, ws.gt, nullptr, h.d_tiles_ws);
+                }
             }
             h.d_extra = extra_all;
             if (rc) return rc;

@@ -46,7 +46,7 @@ struct SolverArgs {
     int* n_done;          // acceptance launches of the inner loop: blocks finished (the last one publishes)
     int carry;            // the trial evaluation is a full one and becomes the next iterate's on acceptance (tiles_t, grad_t)
     const void *tiles_t, *grad_t;
-    // ... with the Lagrangian blocks of the trial point too (one launch: blocks + evaluation, launch_rowhess_eval_mfma): the
+    // ... with the Lagrangian blocks of the trial point too (one launch: blocks + evaluation, HessOut::ev_g): the
     // step kernel writes the multipliers the trial point would have, lam + alpha (lamn - lam); hblk_t is carried over on
     // acceptance like the tiles
     void* lam_t; const void* hblk_t;

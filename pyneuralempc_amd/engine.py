@@ -180,10 +180,16 @@ class CallbackEngine:
     @property
     def last_row_kernel(self):
         """Name of the row kernel the most recent evaluation launched."""
-        return {0: None, 1: "rows_valu_kernel", 2: "rows_coop_kernel", 3: "rows_mfma_kernel", 4: "rows_coopfx_kernel",
-                5: "rows_coop_kernel+dense", 6: "rows_coopfx_kernel+sparse", 7: "rows_coop_kernel+sparse", 8: "layered_gemm_kernel"}[
-            self.lib.nempc_last_row_kernel(self._handle)]
+        return self.ROW_KERNELS[self.lib.nempc_last_row_kernel(self._handle)]
 
+    # what the nempc_last_* codes name (the enums of csrc/mfma_plan.h and DenseWriter of csrc/post_plan.h)
+    ROW_KERNELS = {0: None, 1: "rows_valu_kernel", 2: "rows_coop_kernel", 3: "rows_mfma_kernel", 4: "rows_coopfx_kernel",
+                   5: "rows_coop_kernel+dense", 6: "rows_coopfx_kernel+sparse", 7: "rows_coop_kernel+sparse", 8: "layered_gemm_kernel"}
+    HESS_KERNELS = {0: None, 1: "rowhess_valu_kernel", 2: "rowhess_coop_kernel", 3: "rowhess_mfma_kernel", 4: "rowhess_coopfx_kernel",
+                    5: "layered_gemm_kernel"}
+    HESS_IN_RK4 = 10          # added to a HESS_KERNELS code: the kernel ran inside the RK4 pipeline
+    LQ_KERNELS = {0: None, 1: "thread_global", 2: "thread_lds", 3: "wave_lds", 4: "scan"}
+    ROLLOUT_KERNELS = {0: None, 1: "rollout_wave_kernel", 2: "rollout_mfma_kernel"}
     DENSE_WRITERS = {0: None, 1: "row_launch", 2: "assemble_dense_kernel", 3: "post_kernel", 4: "post_flat_kernel",
                      5: "post_scatter_kernel"}
 
@@ -202,15 +208,14 @@ class CallbackEngine:
         """Name of the network kernel the most recent Lagrangian-Hessian evaluation launched ("rk4:" prefix: inside the RK4
         pipeline)."""
         v = self.lib.nempc_last_hess_kernel(self._handle)
-        name = {0: None, 1: "rowhess_valu_kernel", 2: "rowhess_coop_kernel", 3: "rowhess_mfma_kernel", 4: "rowhess_coopfx_kernel",
-                5: "layered_gemm_kernel"}[v % 10]
-        return ("rk4:" + name) if v >= 10 and name else name
+        name = self.HESS_KERNELS[v % self.HESS_IN_RK4]
+        return ("rk4:" + name) if v >= self.HESS_IN_RK4 and name else name
 
     @property
     def last_lq_kernel(self):
         """LQ plan of the most recent solve: "thread_global" (thread per problem, working set in global memory),
         "thread_lds", "wave_lds", "scan"; None before the first solve."""
-        return {0: None, 1: "thread_global", 2: "thread_lds", 3: "wave_lds", 4: "scan"}[self.lib.nempc_last_lq_kernel(self._handle)]
+        return self.LQ_KERNELS[self.lib.nempc_last_lq_kernel(self._handle)]
 
     # ------------------------------------------------------------------ parameters
     def set_objective(self, Q=None, R=None, xref=None, uref=None, cx=None, cu=None, QT=None):
@@ -546,7 +551,7 @@ class CallbackEngine:
     @property
     def last_rollout_kernel(self):
         """Name of the kernel the most recent roll-out launched."""
-        return {0: None, 1: "rollout_wave_kernel", 2: "rollout_mfma_kernel"}[self.lib.nempc_last_rollout_kernel(self._handle)]
+        return self.ROLLOUT_KERNELS[self.lib.nempc_last_rollout_kernel(self._handle)]
 
     def rollout(self, X0, U=None, Z=None, want_f=False):
         """Forward simulation of the model on the device (nempc_rollout): x_t = Phi(x_{t-1}, u_t), x_{-1} = X0, one launch

@@ -266,7 +266,7 @@ def test_launch_geometry_follows_the_device_cu_count(num_cus, monkeypatch):
 
 @pytest.mark.parametrize("dtype,hidden", [(torch.float64, [30, 30]), (torch.float32, [30, 30]), (torch.float32, [64, 64])])
 def test_compiled_shape_table_beyond_the_baseline_shape(dtype, hidden):
-    """The table of compiled fixed shapes (csrc/kernels_mfma_typed.inc, FxTable): the reference's own example network
+    """The table of compiled fixed shapes (csrc/mfma_plan.h, kCompiledShapes): the reference's own example network
     3 -> 30 -> 30 -> 2 (examples/lotka_volterra/run.py:64-98, nn_model.h5) in both precisions and 2/1 2 x 64 in fp32 take
     rows_coopfx_kernel / rowhess_coopfx_kernel -- every output subset of the one-launch evaluation (dense, sparse, tiles,
     forward only), box rows, ragged batches, the Hessian callbacks and the batched solver -- against the oracle."""
