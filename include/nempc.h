@@ -473,6 +473,37 @@ int nempc_n_params(nempc_handle h, int64_t* P);
 int nempc_weight_grad(nempc_handle h, int32_t B, const void* Z, const void* X0, const void* lam, const void* v,
                       const void* w, const int32_t* skip, void* gtheta, void* stream);
 
+/* Gradient with respect to the extra network inputs p / tvp (reference counterpart: none -- the reference passes p and tvp
+ * through its model, Model(p_dim, tvp_dim), NMPC.next(x0, p=, tvp=), and never differentiates with respect to them).  In the
+ * notation of nempc_weight_grad, with e_{b,t} row (b,t) of the tensor bound by nempc_bind_extra ([tvp_t ; p]) and
+ * xi_{b,t} = [x_{t-1} | u_t | e_{b,t}]:
+ *     S_b(E)    = sum_t ( w_{b,t} . Phi_t(xi_{b,t}) + lam_{b,t} . ( T_t(xi_{b,t}) v_{b,[t]} ) )
+ *     gE[b,t,:] = dS_b / d e_{b,t}          (Z, X0, lam, v, w, theta held fixed)
+ * per row: no sum over t, no sum over b.  A constant parameter p occupies the same slots of every row and its gradient is the
+ * caller's sum over t.  g = Phi - x depends on E, the objective and the bound terms do not: with (v, w) from nempc_kkt_solve
+ * the cotangent of E behind the solution map is -gE.  With lam = v = NULL the second term drops and gE = w' dPhi/de is the
+ * gradient of a defect-weighted loss (one-step-prediction fitting of p).  Under RK4 the extras are held over the four stages,
+ * like u, and row (b,t) collects the contributions of all four.
+ *   Z (B,n), X0 (B,nx) device, required; w (B,H*nx) device, defect order, required;
+ *   lam (B,m), v (B,n) device, both or neither (one without the other: NEMPC_EINVAL); box-row entries of lam are not read;
+ *   gE (B,H,n_extra) device, dtype of the handle, OVERWRITTEN.
+ * n_extra == 0: NEMPC_EINVAL; rolling_window > 1: NEMPC_EUNSUPPORTED; a missing extras binding or one that covers fewer than
+ * B problems: the codes of nempc_eval (NEMPC_ESTATE, NEMPC_EINVAL).  Every refusal names the function in nempc_last_error and
+ * leaves the handle usable.  Problems are independent: the rows of a problem do not depend on B nor on what the other
+ * problems hold (NaN included), to the bit, and a call is bitwise reproducible (no atomics, one summation order per row).
+ * Any network the generic row kernel takes (widths up to 1024, up to 8 layers, any activation on any layer), Discret / Unity
+ * / RK4, both dtypes, whatever the handle's row-kernel variant.  One launch: the dual-number sweep of nempc_weight_grad with a
+ * row split over 1, 16 or 64 lanes (from the widest layer), s'(z) and s''(z) z. of the backward pass in LDS while they fit and
+ * otherwise in a per-workgroup region of a workspace the handle owns.  Asynchronous on `stream`; only the first call of a
+ * handle whose plan needs that workspace (and one after max_batch grew) allocates it and SYNCHRONISES THE DEVICE.  A handle
+ * that never calls this function allocates nothing for it.  The ABI version stays 8: nothing existing changed. */
+int nempc_extra_grad(nempc_handle h, int32_t B, const void* Z, const void* X0, const void* lam, const void* v, const void* w,
+                     void* gE, void* stream);
+
+/* launch form of the handle's most recent nempc_extra_grad: lanes per row 1 -> 1, 16 -> 2, 64 -> 3, plus 4 when the saved
+ * activation derivatives went to the workspace instead of LDS (5, 6, 7); 0 = none yet */
+int nempc_last_extra_grad_kernel(nempc_handle h);
+
 /* Forward simulation of the handle's model (no reference counterpart: the reference never integrates its model over the
  * horizon on its own -- its cold start tiles x0, optimizer/ipopt.py:149, and its examples step the plant outside the library).
  *   Z (B,n) device, in/out: the controls are read from Z[:, H*nx:] and are not written; the states Z[:, :H*nx] are

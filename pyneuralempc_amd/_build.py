@@ -30,7 +30,7 @@ _MFMA_ACTS = ["relu", "sigmoid", "softplus", "elu"]          # (+ "rt": per-laye
 SOURCES = (["kernels_mfma_f64_rt.hip", "kernels_mfma_f64.hip", "kernels_mfma_f32_rt.hip", "kernels_mfma_f32.hip", "solver.hip"] +
            [f"kernels_mfma_{t}_{a}.hip" for t in ("f64", "f32") for a in _MFMA_ACTS] +
            ["nempc_api.hip", "kernels_valu.hip", "kernels_layered.hip", "kernels_post.hip", "kernels_mfma.hip", "kernels_rk4hess.hip",
-            "kernels_rollout.hip", "kernels_sens.hip", "kernels_kktsolve.hip", "kernels_wgrad.hip", "comm.hip"])
+            "kernels_rollout.hip", "kernels_sens.hip", "kernels_kktsolve.hip", "kernels_wgrad.hip", "kernels_egrad.hip", "comm.hip"])
 ARCH = "gfx950"
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-I", os.path.join(REPO, "include"), "-I", CSRC]

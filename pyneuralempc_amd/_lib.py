@@ -46,7 +46,7 @@ EXPORTS = ["nempc_create", "nempc_destroy", "nempc_reserve", "nempc_set_weights"
            "nempc_bind_tracking", "nempc_bind_bounds",
            "nempc_jac_dense_resident",
            "nempc_dims", "nempc_constraint_bounds", "nempc_jac_structure", "nempc_hess_structure", "nempc_eval",
-           "nempc_hess", "nempc_hess_gn", "nempc_solve", "nempc_solve_duals", "nempc_kkt_residual", "nempc_sensitivity", "nempc_kkt_solve", "nempc_n_params", "nempc_weight_grad", "nempc_rollout", "nempc_last_rollout_kernel", "nempc_sync", "nempc_kernel_variant", "nempc_last_row_kernel", "nempc_last_dense_writer", "nempc_last_hess_kernel", "nempc_last_lq_kernel", "nempc_last_error", "nempc_abi_version",
+           "nempc_hess", "nempc_hess_gn", "nempc_solve", "nempc_solve_duals", "nempc_kkt_residual", "nempc_sensitivity", "nempc_kkt_solve", "nempc_n_params", "nempc_weight_grad", "nempc_extra_grad", "nempc_last_extra_grad_kernel", "nempc_rollout", "nempc_last_rollout_kernel", "nempc_sync", "nempc_kernel_variant", "nempc_last_row_kernel", "nempc_last_dense_writer", "nempc_last_hess_kernel", "nempc_last_lq_kernel", "nempc_last_error", "nempc_abi_version",
            "nempc_plan_grid", "nempc_num_cus",
            "nempc_comm_unique_id", "nempc_comm_init", "nempc_allgather_u0", "nempc_comm_size", "nempc_comm_destroy"]
 
@@ -122,6 +122,11 @@ def load():
     if have_wgrad:
         lib.nempc_n_params.argtypes = [vp, ctypes.POINTER(ctypes.c_int64)]
         lib.nempc_weight_grad.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    # (and for the gradient of the extras: CallbackEngine.extra_grad says so when the loaded library has no such symbol)
+    have_egrad = hasattr(lib, "nempc_extra_grad")
+    if have_egrad:
+        lib.nempc_extra_grad.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        lib.nempc_last_extra_grad_kernel.argtypes = [vp]
     lib.nempc_rollout.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.nempc_last_rollout_kernel.argtypes = [vp]
     lib.nempc_sync.argtypes = [vp, vp]
@@ -145,6 +150,7 @@ def load():
     for name in EXPORTS:
         if name != "nempc_last_error" and (name != "nempc_jac_dense_resident" or have_resident) and \
                 (name not in ("nempc_n_params", "nempc_weight_grad") or have_wgrad) and \
+                (name not in ("nempc_extra_grad", "nempc_last_extra_grad_kernel") or have_egrad) and \
                 (name != "nempc_last_dense_writer" or have_writer):
             getattr(lib, name).restype = ctypes.c_int
     if lib.nempc_abi_version() != ABI_VERSION:

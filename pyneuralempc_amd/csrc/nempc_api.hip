@@ -299,6 +299,7 @@ void destroy_impl(Handle* h) {
     dev_free(h->d_sens_ws);
     kktsolve_free(*h);
     wgrad_free(*h);
+    egrad_free(*h);
     delete h;
 }
 
@@ -995,6 +996,28 @@ int nempc_weight_grad(nempc_handle hh, int32_t B, const void* Z, const void* X0,
         return NEMPC_OK;
     }
     return launch_weight_grad(h, B, Z, X0, lam, v, w, skip, gtheta, s);
+}
+
+int nempc_extra_grad(nempc_handle hh, int32_t B, const void* Z, const void* X0, const void* lam, const void* v, const void* w,
+                     void* gE, void* stream) {
+    const char* const who = "nempc_extra_grad";
+    if (int rc = point_enter(hh, B, who, ": rolling_window > 1 handles are not supported (the sweep is built for the rows of a "
+                                         "plain model)")) return rc;
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    if (h.ne == 0) return fail(NEMPC_EINVAL, who, ": the handle was created with n_extra = 0");
+    if ((lam == nullptr) != (v == nullptr)) return fail(NEMPC_EINVAL, who, ": lam and v are given both or neither");
+    if (!gE) return fail(NEMPC_EINVAL, who, ": gE is null");
+    if (B > 0 && (!Z || !X0 || !w)) return fail(NEMPC_EINVAL, who, ": null argument (Z, X0 and w are required)");
+    if (int rc = check_network_inputs(h, B, who)) return rc;
+    if (B == 0) return NEMPC_OK;
+    DeviceGuard dg(h.cfg.device);
+    if (!dg.ok) return fail(NEMPC_EHIP, who, ": hipSetDevice failed");
+    return launch_extra_grad(h, B, Z, X0, lam, v, w, gE, reinterpret_cast<hipStream_t>(stream));
+}
+
+int nempc_last_extra_grad_kernel(nempc_handle hh) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_last_extra_grad_kernel: null handle");
+    return reinterpret_cast<Handle*>(hh)->last_egrad_kernel;
 }
 
 int nempc_rollout(nempc_handle hh, int32_t B, const void* X0, void* Z, void* f, void* stream) {

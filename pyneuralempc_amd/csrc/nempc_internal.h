@@ -212,6 +212,8 @@ struct Handle {
     size_t kktsolve_ws_doubles = 0;          //   (allocated and grown by the call itself, kernels_kktsolve.hip)
     void* d_wgrad_ws = nullptr;              // nempc_weight_grad: factor matrices | sweep scratch | slabs | kept-problem list
     size_t wgrad_ws_bytes = 0;               //   (allocated and grown by the call itself, kernels_wgrad.hip)
+    void* d_egrad_ws = nullptr;              // nempc_extra_grad: s', s'' z. of the resident workgroups, when its plan keeps them
+    size_t egrad_ws_bytes = 0;               //   outside LDS (allocated by the call itself, kernels_egrad.hip)
     void* d_rk4_stage = nullptr; // RK4 Hessian pipeline (allocated on first use): (Bmax*H, 4, nin + 2*nx*nin) stage records,
     void* d_rk4_nu = nullptr;    //   (Bmax*H, 4, nx) stage multipliers,
     void* d_rk4_ht = nullptr;    //   (Bmax*H, 4, nin, nin) contracted stage Hessians
@@ -231,6 +233,7 @@ struct Handle {
     mutable int last_dense_writer = 0;  // DenseWriter (post_plan.h) of the most recent nempc_eval (nempc_last_dense_writer)
     mutable int last_lq_kernel = LQ_NONE;            // LqKernel of the most recent solve's plan (nempc_last_lq_kernel)
     mutable int last_rollout_kernel = ROLLOUT_NONE;  // RolloutKernel of the most recent roll-out (nempc_last_rollout_kernel)
+    int last_egrad_kernel = 0;                       // EgradKernel (egrad_plan.h) of the most recent nempc_extra_grad
 };
 
 struct ObjOffsets {  // element offsets into Handle::d_obj
@@ -369,6 +372,13 @@ long long wgrad_n_params(const Handle& h);
 int launch_weight_grad(Handle& h, int B, const void* Z, const void* X0, const void* lam, const void* v, const void* w,
                        const int32_t* skip, void* gtheta, hipStream_t s);
 void wgrad_free(Handle& h);
+
+// ---- kernels_egrad.hip : gradient with respect to the extra network inputs (nempc_extra_grad)
+// lam / v both or neither; gE (B,H,ne) is overwritten.  Allocates Handle::d_egrad_ws (a device synchronisation) when the plan
+// keeps the saved activation derivatives outside LDS
+int launch_extra_grad(Handle& h, int B, const void* Z, const void* X0, const void* lam, const void* v, const void* w, void* gE,
+                      hipStream_t s);
+void egrad_free(Handle& h);
 
 // ---- solver.hip : batched Gauss-Newton SQP (host driver; its kernels are in solver_args.h and the solver_*_impl.h headers,
 // which only solver.hip includes)

@@ -239,6 +239,15 @@ class CallbackEngine:
         self._objective = dict(Q=Q, R=R, xref=xref, uref=uref, cx=cx, cu=cu, QT=QT)
         self._refresh_dims()
 
+    def set_objective_weights(self, Q=None, R=None, QT=None):
+        """Re-upload the objective with the given weights replaced: xref / uref / cx / cu and the weights not given stay as
+        last set (`set_objective`'s arguments, or the library's defaults where it was given nothing)."""
+        ob = dict(self._objective or {})
+        for key, val in (("Q", Q), ("R", R), ("QT", QT)):
+            if val is not None:
+                ob[key] = val
+        self.set_objective(**ob)
+
     def objective_weights(self):
         """(Q (nx,nx), R (nu,nu), QT (nx,nx)) of the handle's objective as float64 arrays: what set_objective was given,
         the library's defaults (I, 0.1 I) where it was given nothing, QT = Q without a terminal weight."""
@@ -247,6 +256,25 @@ class CallbackEngine:
         R = 0.1 * np.eye(self.nu) if ob.get("R") is None else np.array(np.broadcast_to(np.asarray(ob["R"], dtype=np.float64), (self.nu, self.nu)))
         QT = Q.copy() if ob.get("QT") is None else np.asarray(ob["QT"], dtype=np.float64).reshape(self.nx, self.nx).copy()
         return Q, R, QT
+
+    def objective_refs(self):
+        """(xref (H,nx), uref (H,nu)) of the handle's shared objective as float64 arrays (zeros where set_objective was given
+        nothing): what a problem tracks where no per-problem row is bound."""
+        ob = self._objective or {}
+        return tuple(np.zeros(shape) if ob.get(k) is None else np.array(np.broadcast_to(np.asarray(ob[k], dtype=np.float64), shape))
+                     for k, shape in (("xref", (self.H, self.nx)), ("uref", (self.H, self.nu))))
+
+    @property
+    def has_terminal_weight(self):
+        """True when the last step is weighed by a QT of its own (set_objective's QT), False when Q weighs every step."""
+        return (self._objective or {}).get("QT") is not None
+
+    def tracking_refs(self):
+        """{name: (B,H,d) view} of the tensors bound with bind_tracking, the horizon's rows; {} without a binding."""
+        if getattr(self, "_tracking", None) is None:
+            return {}
+        given, offset = self._tracking
+        return {k: t[:, offset:offset + self.H] for k, t in given.items()}
 
     def bind_extra(self, E):
         """Bind the extra network inputs (B,H,n_extra) = [tvp_t ; p] per step for the following evaluations
@@ -844,6 +872,43 @@ class CallbackEngine:
             out.append((g[at:at + i * o].view(i, o), g[at + i * o:at + (i + 1) * o]))
             at += (i + 1) * o
         return out
+
+    # ------------------------------------------------------------------ the extra inputs p / tvp as parameters
+    EXTRA_GRAD_KERNELS = {0: None, 1: "egrad_rows_kernel<1 lane, lds>", 2: "egrad_rows_kernel<16 lanes, lds>",
+                          3: "egrad_rows_kernel<64 lanes, lds>", 5: "egrad_rows_kernel<1 lane, workspace>",
+                          6: "egrad_rows_kernel<16 lanes, workspace>", 7: "egrad_rows_kernel<64 lanes, workspace>"}
+
+    def extra_grad(self, Z, X0, w, lam=None, v=None):
+        """gE[b,t,:] = d/d e_{b,t} ( w_{b,t} . Phi_t + lam_{b,t} . (T_t v_{b,[t]}) ), e_{b,t} row (b,t) of the tensor bound with
+        `bind_extra` (nempc_extra_grad; Z, X0, lam, v, w and the weights held fixed) -- per row, no sum over t or b: the
+        gradient of a constant parameter p is the caller's sum over t of its slots.  Z (B,n), X0 (B,nx), w (B,H*nx) in defect
+        order; lam (B,m) and v (B,n) both or neither -- without them the result is w' dPhi/de, the gradient of a
+        defect-weighted loss; with `kkt_solve`'s (v, w) the cotangent of the extras behind the solution is -gE.  Returns a new
+        (B,H,n_extra) device tensor.  Problems are independent and the call is bitwise reproducible.  Asynchronous on the
+        current torch stream, except a first call that has to allocate the handle's workspace for it."""
+        fn = self._wgrad_fn("nempc_extra_grad")
+        B = int(Z.shape[0])
+        self._check_in(Z, (B, self.n), "Z")
+        self._check_in(X0, (B, self.nx), "X0")
+        self._check_in(w, (B, self.H * self.nx), "w")
+        if (lam is None) != (v is None):
+            raise ValueError("lam and v are given both or neither")
+        if lam is not None:
+            self._check_in(lam, (B, self.m), "lam")
+            self._check_in(v, (B, self.n), "v")
+        if self.rolling_window == 1 and self.n_extra:      # (a rolling-window or n_extra = 0 handle is refused by the library)
+            self._check_extra(B)
+        self.reserve(B)
+        g = torch.empty((B, self.H, self.n_extra), dtype=self.dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(fn(self._handle, B, _ptr(Z), _ptr(X0), _ptr(lam), _ptr(v), _ptr(w), _ptr(g), self._stream()))
+        return g
+
+    @property
+    def last_extra_grad_kernel(self):
+        """Launch form of the most recent `extra_grad` (nempc_last_extra_grad_kernel): lanes per row, and where the saved
+        activation derivatives lived; None before the first call."""
+        return self.EXTRA_GRAD_KERNELS[self._wgrad_fn("nempc_last_extra_grad_kernel")(self._handle)]
 
     def sync(self):
         _lib.check(self.lib.nempc_sync(self._handle, self._stream()))
