@@ -222,6 +222,28 @@ int nempc_bind_tracking(nempc_handle h, const void* xref, const void* uref, cons
 int nempc_bind_bounds(nempc_handle h, const void* xlb, const void* xub, const void* ulb, const void* uub,
                       int32_t B, int64_t ld_x, int64_t ld_u);
 
+/* input-rate penalty and rate limits for subsequent nempc_solve calls.  With du_t = u_t - u_{t-1} and u_{-1} = u_prev_b (the
+ * control applied before problem b's first step, data), the solve becomes
+ *    min f(z) + sum_{t=0..H-1} du_t' S du_t    s.t. defects = 0,  lb <= z <= ub (as without the binding),  dlo_t <= du_t <= dhi_t
+ *   S         (nu,nu) host doubles, used as given like R (the gradient uses S + S'); NULL = no penalty;
+ *   dlo, dhi  host doubles, (nu) when per_stage == 0 (every step), (H,nu) when per_stage == 1; NULL or -+INFINITY = no limit.
+ *             dlo >= dhi on any entry, or a NaN, is NEMPC_EINVAL (the barrier needs an interior: the rule of lb == ub);
+ *   u_prev    (B,nu) device pointer of the handle's dtype, stored not copied, read in stream order by the solves that
+ *             follow; required whenever S, dlo or dhi is given.  B = problems it covers: a solve over more is NEMPC_EINVAL.
+ * S, dlo, dhi are copied.  All of S, dlo, dhi, u_prev NULL removes the binding.
+ * The solver runs the problem stage-wise in the state [x_t ; u_t] with du_t as the stage control; the returned
+ * u are the u slots of that state, and u_t - u_{t-1} = du_t holds to tol_constraint at convergence.  The Levenberg term of
+ * nempc_solver_opts.reg sits on du.
+ * nempc_eval, nempc_hess / nempc_hess_gn and nempc_rollout do not read the binding: they evaluate the plain problem.
+ * While a binding is on: nempc_solve_duals with a non-NULL lam, zl or zu, nempc_kkt_residual, nempc_sensitivity and
+ * nempc_kkt_solve are NEMPC_EUNSUPPORTED (they would certify or differentiate a different problem; mapping the multipliers of
+ * the augmented problem back to the caller's rows is left to a later change); nempc_solve with a tracking binding
+ * (nempc_bind_tracking) or per-problem bounds (nempc_bind_bounds) is NEMPC_EUNSUPPORTED (the objective table and the bounds of
+ * the augmented state are built on the host, as for rolling windows).  On a rolling_window > 1 handle the call itself is
+ * NEMPC_EUNSUPPORTED. */
+int nempc_bind_rate(nempc_handle h, const double* S, const double* dlo, const double* dhi, int32_t per_stage,
+                    const void* u_prev, int32_t B);
+
 /* extra constraint rows g_box = states.ravel() (a Constraint in the sense of constraints.py:36-63
  * with constant selector Jacobian); lo/hi (nx) host doubles are only reported back through
  * nempc_constraint_bounds. enabled=0 removes the rows. */

@@ -61,9 +61,15 @@ class NMPC:
             factory.set_use_hessian(bool(self.use_hessian))
         return factory.getProblemInterface()
 
-    def next(self, x0: np.array, p=None, tvp=None, init_x=None, init_u=None):
-        """Solve one MPC problem; returns (states (H,nx), u (H,nu)) or (None, None) on solver failure."""
+    def next(self, x0: np.array, p=None, tvp=None, init_x=None, init_u=None, u_prev=None):
+        """Solve one MPC problem; returns (states (H,nx), u (H,nu)) or (None, None) on solver failure.  u_prev (nu,): the
+        control applied before this step, for an optimizer with an input-rate penalty or rate limits (DeviceSqp(du_weight=,
+        du_lb=, du_ub=)); left out, such an optimizer takes the first control of its last result (zeros on the first call)."""
         pb = self.get_pb(x0, p=p, tvp=tvp, init_x=init_x, init_u=init_u)
+        if u_prev is not None:
+            if not hasattr(self.optimizer, "set_u_prev"):
+                raise ValueError("next: u_prev is for an optimizer with rate terms (DeviceSqp(du_weight=, du_lb=, du_ub=))")
+            self.optimizer.set_u_prev(u_prev, self.integrator.model.u_dim)
         status = self.optimizer.solve(pb, self.domain_constraint)
         if status != Optimizer.SUCCESS:
             return None, None
@@ -154,6 +160,43 @@ class NMPC:
             given[name] = v
         return given
 
+    def _rate_check(self, X0, who, u_prev, du_weight, du_lb, du_ub):
+        """Shapes of the rate arguments, checked before anything touches a device.  -> None when none is given, else
+        dict(u_prev (B,nu) float64 array or a tensor, S, du_lb, du_ub)."""
+        if u_prev is None and du_weight is None and du_lb is None and du_ub is None:
+            return None
+        model = self.integrator.model
+        nu, H = int(model.u_dim), int(self.integrator.H)
+        B = 1 if len(np.shape(X0)) < 2 else int(np.shape(X0)[0])
+        if u_prev is None:
+            raise ValueError(f"{who}: u_prev (the control applied before the first step) is required with du_weight, du_lb or du_ub")
+        shape = tuple(int(k) for k in np.shape(u_prev))
+        if shape not in ((B, nu), (nu,)):
+            raise ValueError(f"{who}: u_prev must have shape {(B, nu)} (one per problem) or {(nu,)} (shared), got {shape}")
+        if du_weight is not None and tuple(np.shape(du_weight)) != (nu, nu):
+            raise ValueError(f"{who}: du_weight must have shape {(nu, nu)}, got {tuple(np.shape(du_weight))}")
+        for name, v in (("du_lb", du_lb), ("du_ub", du_ub)):
+            if v is not None and tuple(np.shape(v)) not in ((nu,), (H, nu)):
+                raise ValueError(f"{who}: {name} must have shape {(nu,)} (every step) or {(H, nu)} (per step), got {tuple(np.shape(v))}")
+        if du_lb is not None and du_ub is not None and \
+                (np.broadcast_to(np.asarray(du_lb, dtype=np.float64), (H, nu)) >= np.broadcast_to(np.asarray(du_ub, dtype=np.float64), (H, nu))).any():
+            raise ValueError(f"{who}: du_lb >= du_ub on some entry (the solver's barrier needs an interior)")
+        if int(getattr(model, "rolling_window", 1)) > 1:
+            raise ValueError(f"{who}: rate terms are not supported with rolling-window models")
+        return dict(u_prev=u_prev, S=du_weight, du_lb=du_lb, du_ub=du_ub)
+
+    @staticmethod
+    def _rate_bind(eng, B, rate):
+        """The rate terms bound on the engine (CallbackEngine.bind_rate); returns the (B,nu) device tensor of u_prev, which
+        the engine reads in stream order at every solve."""
+        import torch
+        v = rate["u_prev"]
+        t = v.to(device=eng.device, dtype=eng.dtype) if isinstance(v, torch.Tensor) else \
+            torch.as_tensor(np.asarray(v, dtype=np.float64), dtype=eng.dtype, device=eng.device)
+        t = (t if t.dim() == 2 else t[None].expand(B, -1)).contiguous().clone()
+        eng.bind_rate(u_prev=t, S=rate["S"], du_lb=rate["du_lb"], du_ub=rate["du_ub"])
+        return t
+
     @staticmethod
     def _tracking_bind(eng, B, given, offset=0, bind=None):
         """Device tensors (B,L,d) of the engine's dtype for the given arrays, bound at `offset` (by eng.bind_tracking, or by
@@ -168,7 +211,8 @@ class NMPC:
         return dev
 
     def next_batch(self, X0, init_z=None, p=None, tvp=None, prev_x=None, prev_u=None, prev_tvp=None, xref=None, uref=None,
-                   cx=None, cu=None, xlb=None, xub=None, ulb=None, uub=None, return_duals=False, return_gain=False, **solver_opts):
+                   cx=None, cu=None, xlb=None, xub=None, ulb=None, uub=None, return_duals=False, return_gain=False,
+                   u_prev=None, du_weight=None, du_lb=None, du_ub=None, **solver_opts):
         """Solve B MPC problems at once on the device (no reference counterpart).  X0 (B,nx) NumPy
         array or device tensor.  Needs the fused device path (device integrator + QuadraticObjective; the only
         extra rows accepted are BoxStateConstraint, which become bounds on the state variables).  Models with
@@ -191,9 +235,13 @@ class NMPC:
         appends (after the duals when both are asked for) the feedback gain K0 = du_0*/dx0 (B,nu,nx) as a NumPy array, for
         u = u0* + K0 (x_measured - x0) between solves (CallbackEngine.sensitivity at the returned point, from the duals of
         the same solve and the controller's own bounds); entries are NaN where the sensitivity status, kept in
-        ``self.last_gain_status`` (B,), is non-zero."""
+        ``self.last_gain_status`` (B,), is non-zero.  u_prev (B,nu) or (nu,), du_weight (nu,nu), du_lb / du_ub (nu,) or (H,nu)
+        add an input-rate penalty sum_t du_t' du_weight du_t and rate limits du_lb <= du_t <= du_ub on du_t = u_t - u_{t-1},
+        u_{-1} = u_prev (CallbackEngine.bind_rate, for this call only); not together with per-problem references or bounds,
+        return_duals or return_gain (the device solver refuses those combinations)."""
         import torch
         H = self.integrator.H
+        rate = self._rate_check(X0, "next_batch", u_prev, du_weight, du_lb, du_ub)
         given = self._tracking_check(X0, H, "next_batch", xref=xref, uref=uref, cx=cx, cu=cu)
         bounds = self._tracking_check(X0, H, "next_batch", xlb=xlb, xub=xub, ulb=ulb, uub=uub)
         eng, X0t, lb, ub = self._batch_engine(X0, p, tvp, prev_x, prev_u, prev_tvp, "next_batch")
@@ -203,6 +251,8 @@ class NMPC:
                 self._tracking_bind(eng, int(X0t.shape[0]), given)
             if bounds:
                 self._tracking_bind(eng, int(X0t.shape[0]), bounds, bind=eng.bind_bounds)
+            if rate:
+                self._rate_bind(eng, int(X0t.shape[0]), rate)
             duals = gain = None
             if return_duals or return_gain:
                 Z, status, iters, duals = eng.solve(X0t, Zi, lb, ub, return_duals=True, **solver_opts)
@@ -217,6 +267,8 @@ class NMPC:
                 eng.bind_tracking()
             if bounds:
                 eng.bind_bounds()
+            if rate:
+                eng.bind_rate()
         self.last_batch_iterations = iters
         z = Z.to("cpu", torch.float64).numpy()
         B, nx, nu = z.shape[0], eng.nx, eng.nu
@@ -224,7 +276,8 @@ class NMPC:
         return res + ((duals,) if return_duals else ()) + ((gain,) if return_gain else ())
 
     def closed_loop_batch(self, X0, steps, p=None, prev_x=None, prev_u=None, disturbance=None, xref=None, uref=None, cx=None,
-                          cu=None, xlb=None, xub=None, ulb=None, uub=None, **solver_opts):
+                          cu=None, xlb=None, xub=None, ulb=None, uub=None, u_prev=None, du_weight=None, du_lb=None, du_ub=None,
+                          **solver_opts):
         """B closed loops of `steps` MPC steps on the device, the plant being the model itself (no reference counterpart:
         the reference's examples step their plant on the host between NMPC.next calls).  Preconditions as next_batch.  Per
         step, on device tensors only: (1) solve -- step 0 from solver_opts' init ("tile" by default), later steps from the
@@ -239,7 +292,10 @@ class NMPC:
         (H,d) values serve every step.  xlb / xub (B, steps+H-1, nx) and ulb / uub (B, steps+H-1, nu) (or one (steps+H-1, d)
         schedule) are per-problem, time-varying bounds over the whole run in the same way: step k solves inside rows
         k .. k+H-1 (row 0 of a u schedule bounds the control applied at step 0, row 0 of an x schedule the state it leads to),
-        intersected with the DomainConstraint and the box rows.  Returns (X (B,steps+1,nx), U (B,steps,nu), status (steps,B)) as NumPy arrays."""
+        intersected with the DomainConstraint and the box rows.  u_prev (B,nu) or (nu,) (the control applied before step 0),
+        du_weight (nu,nu), du_lb / du_ub (nu,) or (H,nu) add an input-rate penalty and rate limits to every solve
+        (next_batch): after each step the applied u_0 becomes u_prev of the next solve, on the device; the shifted warm start
+        is unchanged.  Returns (X (B,steps+1,nx), U (B,steps,nu), status (steps,B)) as NumPy arrays."""
         import torch
         model = self.integrator.model
         steps = int(steps)
@@ -247,6 +303,7 @@ class NMPC:
             raise ValueError("steps must be >= 1")
         given = self._tracking_check(X0, steps + int(self.integrator.H) - 1, "closed_loop_batch", xref=xref, uref=uref, cx=cx, cu=cu)
         bounds = self._tracking_check(X0, steps + int(self.integrator.H) - 1, "closed_loop_batch", xlb=xlb, xub=xub, ulb=ulb, uub=uub)
+        rate = self._rate_check(X0, "closed_loop_batch", u_prev, du_weight, du_lb, du_ub)
         if int(getattr(model, "tvp_dim", 0)) > 0:
             raise NotImplementedError("closed_loop_batch: models with time-varying parameters (tvp_dim > 0) are not supported -- "
                                       "a closed loop of `steps` steps needs a tvp schedule of H + steps - 1 rows, longer than the "
@@ -266,6 +323,7 @@ class NMPC:
         try:
             track = self._tracking_bind(eng, B, given) if given else None
             bnd = self._tracking_bind(eng, B, bounds, bind=eng.bind_bounds) if bounds else None
+            up = self._rate_bind(eng, B, rate) if rate else None
             for k in range(steps):
                 if track and k > 0:                               # the horizon's window of the schedules: rows k .. k+H-1
                     eng.bind_tracking(**track, offset=k)
@@ -286,12 +344,16 @@ class NMPC:
                 Zi = eng.rollout(X, U=torch.cat([U[:, 1:], U[:, -1:]], dim=1))
                 Xs.append(X)
                 Us.append(U[:, 0])
+                if up is not None:                                # the applied control is the next solve's u_prev (bound tensor, in place)
+                    up.copy_(U[:, 0])
                 Ss.append(status)
         finally:
             if given:       # the engine is NMPC.next's too: back to the shared objective
                 eng.bind_tracking()
             if bounds:
                 eng.bind_bounds()
+            if rate:
+                eng.bind_rate()
         self.last_closed_loop_iterations = iters      # outer iterations of every step's solve (a list; next_batch's int is last_batch_iterations)
         return (torch.stack(Xs, dim=1).to("cpu", torch.float64).numpy(), torch.stack(Us, dim=1).to("cpu", torch.float64).numpy(),
                 torch.stack(Ss, dim=0).cpu().numpy())

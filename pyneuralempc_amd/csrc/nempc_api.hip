@@ -394,6 +394,14 @@ int point_enter(nempc_handle hh, int32_t B, const char* who, const char* rolling
     return NEMPC_OK;
 }
 
+// nempc_kkt_residual, nempc_sensitivity, nempc_kkt_solve under a rate binding: they would certify or differentiate the problem
+// WITHOUT the penalty and the limits
+int refuse_rate(nempc_handle hh, const char* who) {
+    if (!reinterpret_cast<Handle*>(hh)->rate.on()) return NEMPC_OK;
+    return fail(NEMPC_EUNSUPPORTED, who, ": a rate binding (nempc_bind_rate) is on: the multipliers of the augmented problem are not "
+                                         "mapped back to the caller's rows; unbind it to evaluate the plain problem");
+}
+
 enum : unsigned {
     POINT_TRACKING = 1,   // check the tracking binding's coverage here (without it only an evaluation with grad does)
     POINT_GRAD = 2,       // the objective gradient into d_kkt_grad
@@ -685,6 +693,41 @@ int nempc_bind_bounds(nempc_handle hh, const void* xlb, const void* xub, const v
     return NEMPC_OK;
 }
 
+int nempc_bind_rate(nempc_handle hh, const double* S, const double* dlo, const double* dhi, int32_t per_stage,
+                    const void* u_prev, int32_t B) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_bind_rate: null handle");
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    if (!S && !dlo && !dhi && !u_prev) { h.rate = RateBind{}; return NEMPC_OK; }
+    if (h.w > 1)
+        return fail(NEMPC_EUNSUPPORTED, "nempc_bind_rate: rolling_window > 1 handles are not supported (the window state and the "
+                                        "rate state are two augmentations of the stage; their combination is not built)");
+    if (!u_prev) return fail(NEMPC_EINVAL, "nempc_bind_rate: u_prev is required whenever S, dlo or dhi is given");
+    if (B < 1) return fail(NEMPC_EINVAL, "nempc_bind_rate: B (problems u_prev covers) must be >= 1");
+    if (per_stage != 0 && per_stage != 1) return fail(NEMPC_EINVAL, "nempc_bind_rate: per_stage must be 0 or 1");
+    const int H = h.cfg.H, nu = h.cfg.nu;
+    RateBind rb;
+    rb.u_prev = u_prev; rb.B = B;
+    rb.S.assign((size_t)nu * nu, 0.0);
+    if (S)
+        for (int i = 0; i < nu * nu; ++i) {
+            if (!std::isfinite(S[i])) return fail(NEMPC_EINVAL, "nempc_bind_rate: S has a non-finite entry");
+            rb.S[i] = S[i];
+        }
+    rb.dlo.assign((size_t)H * nu, -INFINITY);
+    rb.dhi.assign((size_t)H * nu, INFINITY);
+    for (int t = 0; t < H; ++t)
+        for (int j = 0; j < nu; ++j) {
+            const int e = per_stage ? t * nu + j : j;
+            const double lo = dlo ? dlo[e] : -INFINITY, hi = dhi ? dhi[e] : INFINITY;
+            if (std::isnan(lo) || std::isnan(hi)) return fail(NEMPC_EINVAL, "nempc_bind_rate: a limit is NaN");
+            if (lo >= hi)
+                return fail(NEMPC_EINVAL, "nempc_bind_rate: dlo >= dhi (a fixed or empty move has no interior for the barrier)");
+            rb.dlo[(size_t)t * nu + j] = lo; rb.dhi[(size_t)t * nu + j] = hi;
+        }
+    h.rate = std::move(rb);
+    return NEMPC_OK;
+}
+
 int nempc_set_box_rows(nempc_handle hh, int enabled, const double* lo, const double* hi) {
     if (!hh) return fail(NEMPC_EINVAL, "nempc_set_box_rows: null handle");
     Handle& h = *reinterpret_cast<Handle*>(hh);
@@ -913,6 +956,21 @@ int nempc_solve_duals(nempc_handle hh, int32_t B, const void* X0, void* Z, const
     if (h.bbind.on() && h.w > 1)
         return fail(NEMPC_EUNSUPPORTED, "nempc_solve: per-problem bounds (nempc_bind_bounds) on a rolling_window > 1 handle: "
                                         "the bounds of the window state are built on the host");
+    if (h.rate.on()) {
+        if (B > h.rate.B) return fail(NEMPC_EINVAL, "nempc_solve: B exceeds the batch the bound u_prev (nempc_bind_rate) covers");
+        if (lam || zl || zu)
+            return fail(NEMPC_EUNSUPPORTED, "nempc_solve_duals: multipliers under a rate binding (nempc_bind_rate) are not supported (the "
+                                            "costates of the augmented state are not mapped back to the caller's rows); pass NULL for "
+                                            "lam, zl and zu");
+        if (h.w > 1)
+            return fail(NEMPC_EUNSUPPORTED, "nempc_solve: a rate binding (nempc_bind_rate) on a rolling_window > 1 handle is not supported");
+        if (h.track.on())
+            return fail(NEMPC_EUNSUPPORTED, "nempc_solve: per-problem tracking data (nempc_bind_tracking) with a rate binding "
+                                            "(nempc_bind_rate): the objective table over the augmented state is built on the host");
+        if (h.bbind.on())
+            return fail(NEMPC_EUNSUPPORTED, "nempc_solve: per-problem bounds (nempc_bind_bounds) with a rate binding (nempc_bind_rate): "
+                                            "the bounds of the augmented state are built on the host");
+    }
     if (opts->max_iter < 1 || opts->max_linesearch < 1 || !(opts->mu_factor > 0.0 && opts->mu_factor < 1.0) ||
         !(opts->mu_init > 0.0) || !(opts->mu_min > 0.0) || opts->lq_kernel < 0 || opts->lq_kernel > 3)
         return fail(NEMPC_EINVAL, "nempc_solve: bad options");
@@ -928,6 +986,7 @@ int nempc_kkt_residual(nempc_handle hh, int32_t B, const void* Z, const void* X0
     const char* const who = "nempc_kkt_residual";
     if (int rc = point_enter(hh, B, who, ": rolling_window > 1 handles are not supported (the band product is built for the "
                                          "tiles of a plain model)")) return rc;
+    if (int rc = refuse_rate(hh, who)) return rc;
     if (B == 0) return NEMPC_OK;
     if (!Z || !X0 || !lam || !r) return fail(NEMPC_EINVAL, "nempc_kkt_residual: null argument (Z, X0, lam and r are required)");
     // (no tracking check of its own: its evaluation asks for grad, and nempc_eval checks the binding then)
@@ -943,6 +1002,7 @@ int nempc_sensitivity(nempc_handle hh, int32_t B, const void* Z, const void* X0,
     const char* const who = "nempc_sensitivity";
     if (int rc = point_enter(hh, B, who, ": rolling_window > 1 handles are not supported (the sweep is built for the stages "
                                          "of a plain model)")) return rc;
+    if (int rc = refuse_rate(hh, who)) return rc;
     if (!dU0 && !dZ && !dlam && !gains) return fail(NEMPC_EINVAL, "nempc_sensitivity: no output asked for (dU0, dZ, dlam, gains all null)");
     if (B == 0) return NEMPC_OK;
     if (!Z || !X0 || !lam || !status)
@@ -960,6 +1020,7 @@ int nempc_kkt_solve(nempc_handle hh, int32_t B, const void* Z, const void* X0, c
     const char* const who = "nempc_kkt_solve";
     if (int rc = point_enter(hh, B, who, ": rolling_window > 1 handles are not supported (the sweep is built for the stages "
                                          "of a plain model)")) return rc;
+    if (int rc = refuse_rate(hh, who)) return rc;
     if (nrhs < 1 || nrhs > 64) return fail(NEMPC_EINVAL, "nempc_kkt_solve: nrhs outside [1, 64]");
     if (!v && !w && !gx0) return fail(NEMPC_EINVAL, "nempc_kkt_solve: no output asked for (v, w, gx0 all null)");
     if (B == 0) return NEMPC_OK;

@@ -137,6 +137,16 @@ struct BoundBind {
     bool on() const { return xlb || xub || ulb || uub; }
 };
 
+// Input-rate penalty and rate limits bound by nempc_bind_rate: host copies of the weight and of the limits (expanded to
+// (H,nu), +-inf = no limit) and the device pointer of the controls applied before each problem's first step.  B = problems
+// u_prev covers, 0 = nothing bound.
+struct RateBind {
+    const void* u_prev = nullptr;
+    int B = 0;
+    std::vector<double> S, dlo, dhi;      // (nu,nu) (zeros when no penalty was given), (H,nu), (H,nu)
+    bool on() const { return u_prev != nullptr; }
+};
+
 struct Handle {
     nempc_config cfg{};
     int num_cus = 256;           // compute units of cfg.device (nempc_create)
@@ -152,6 +162,7 @@ struct Handle {
     const void* d_hist_u = nullptr;
     TrackBind track;             // bound by nempc_bind_tracking
     BoundBind bbind;             // bound by nempc_bind_bounds
+    RateBind rate;               // bound by nempc_bind_rate
     RowGather gather() const {
         RowGather gk;
         gk.H = cfg.H; gk.nx = cfg.nx; gk.nu = cfg.nu; gk.n = n; gk.w = w; gk.rev = rev;

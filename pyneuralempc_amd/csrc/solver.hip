@@ -45,6 +45,7 @@
 //     solver_lqw_impl.h      LQ solve, wave per problem
 //     solver_compact_impl.h  partition / gather of the unconverged problems, scatter of the results
 //     solver_roll_impl.h     rolling-window models: RollTables and the roll_* kernels
+//     solver_rate_impl.h     input-rate penalty and limits (nempc_bind_rate): the rate_* kernels (index arithmetic: rate_index.h)
 // The merit and bound headers come first because the LQ kernels call their bodies.
 #include <chrono>
 #include <cmath>
@@ -67,13 +68,19 @@
 #include "solver_lqw_impl.h"
 #include "solver_compact_impl.h"
 #include "solver_roll_impl.h"
+#include "solver_rate_impl.h"
 
 namespace nempc {
 
 namespace {
 
+// The stage the solver runs on: the handle's own, or an augmentation of it -- the window of a rolling-window model
+// (solver_roll_impl.h) or [x ; u] with the control move as the stage control (nempc_bind_rate, solver_rate_impl.h)
+enum Augmentation { AUG_NONE = 0, AUG_WINDOW = 1, AUG_RATE = 2 };
+
 struct SolverWs {
-    // rolling-window models: tables, the caller-side evaluation buffers and the augmented objective table
+    int aug = AUG_NONE;                       // the augmentation the buffers were sized for
+    // augmented problems: the window's tables, the caller-side evaluation buffers and the augmented objective table
     RollTables rt;
     void *rZ = nullptr, *rg = nullptr, *rtiles = nullptr, *rhblk = nullptr, *rgrad = nullptr, *rlam = nullptr,
          *rZin = nullptr, *rS0 = nullptr, *rZout = nullptr, *robj = nullptr;
@@ -188,9 +195,11 @@ template <typename T>
 struct Solve {
     Handle& h; SolverWs& ws; const nempc_solver_opts& o; const int B; const void* const X0; const hipStream_t s;
     const SolverDuals duals;      // where the multipliers of the returned iterates go (nempc_solve_duals; all null: nowhere)
-    // rolling-window models run as a plain problem in the augmented (window) state, see RollTables: nx, nin, n, m are
-    // the SOLVER's stage dimensions; *_r the handle's (the caller's variables, the callbacks' shapes)
-    const bool rolling; const int H, nx_r, nu, nin_r, n_r, m_r, back, nx, nin, n, m;
+    // rolling-window models and rate bindings run as a plain problem in an augmented state, see RollTables / rate_index.h:
+    // nx, nin, n, m are the SOLVER's stage dimensions; *_r the handle's (the caller's variables, the callbacks' shapes)
+    const int aug; const bool augmented, rolling, rate;      // rolling: AUG_WINDOW, rate: AUG_RATE
+    const int H, nx_r, nu, nin_r, n_r, m_r, back, nx, nin, n, m;
+    const RateDims rd;
     const size_t ex_per; const unsigned gBn, gRn;      // grids of the element-wise kernels over the solver's / the caller's variables
     const SolverKnobs kn = read_knobs();
     ExtraBindingGuard extra_guard; SolverArgs a{}; bool has_bounds = false;
@@ -216,9 +225,12 @@ struct Solve {
     static SolverKnobs read_knobs() { static const ProcessKnobs once; return SolverKnobs{once}; }
     static SolverWs& workspace(Handle& h) { return *static_cast<SolverWs*>(h.solver_ws ? h.solver_ws : (h.solver_ws = new SolverWs())); }
     Solve(Handle& hh, int BB, const void* X0_, const nempc_solver_opts& oo, const SolverDuals& dd, hipStream_t ss)
-        : h(hh), ws(workspace(hh)), o(oo), B(BB), X0(X0_), s(ss), duals(dd), rolling(h.w > 1), H(h.cfg.H), nx_r(h.cfg.nx), nu(h.cfg.nu),
-          nin_r(h.nin), n_r(h.n), m_r(h.m), back(h.w - 1), nx(rolling ? h.w * nx_r + back * nu : nx_r),
-          nin(rolling ? nx + nu : nin_r), n(rolling ? H * (nx + nu) : n_r), m(rolling ? H * nx : m_r), ex_per((size_t)H * h.ne),
+        : h(hh), ws(workspace(hh)), o(oo), B(BB), X0(X0_), s(ss), duals(dd),
+          aug(h.w > 1 ? AUG_WINDOW : (h.rate.on() ? AUG_RATE : AUG_NONE)), augmented(aug != AUG_NONE), rolling(aug == AUG_WINDOW),
+          rate(aug == AUG_RATE), H(h.cfg.H), nx_r(h.cfg.nx), nu(h.cfg.nu),
+          nin_r(h.nin), n_r(h.n), m_r(h.m), back(h.w - 1), nx(rolling ? h.w * nx_r + back * nu : (rate ? nx_r + nu : nx_r)),
+          nin(augmented ? nx + nu : nin_r), n(augmented ? H * (nx + nu) : n_r), m(augmented ? H * nx : m_r),
+          rd(rate_dims(h.cfg.H, h.cfg.nx, h.cfg.nu)), ex_per((size_t)H * h.ne),
           gBn((unsigned)(((size_t)BB * std::max(n, std::max(m, nx)) + 255) / 256)),
           gRn((unsigned)(((size_t)BB * n_r + 255) / 256)), extra_guard(hh), Bact(BB), last_nact(BB) {}
     int run(void* Z, const double* lb, const double* ub, int32_t* status_dev, int32_t* iters_host) {
@@ -286,7 +298,7 @@ struct Solve {
     }
     // a workspace that holds B problems of these dimensions: kept when the handle has one, rebuilt otherwise
     int ensure_workspace() {
-        if (ws.cap >= B && ws.ex_per == ex_per && ws.m == m && ws.n == n) return NEMPC_OK;
+        if (ws.cap >= B && ws.ex_per == ex_per && ws.m == m && ws.n == n && ws.aug == aug) return NEMPC_OK;
         ws.release(); ws = SolverWs();
         SolverWs& w = ws;
         const size_t e = sizeof(T), Bn = (size_t)B;
@@ -313,19 +325,20 @@ struct Solve {
                              {(void**)&w.pend[1], Bn * sizeof(int)},
                              {(void**)&w.n_active, 8 * sizeof(int)},   // [unconverged, still backtracking, blocks done, -, unconverged (odd iterations)]
                              {(void**)&w.perm, Bn * sizeof(int)}, {(void**)&w.count, sizeof(int)}});
-        if (rolling)
+        if (augmented)
             al.insert(al.end(), {
                 {&w.rZ, Bn * n_r * e}, {&w.rg, Bn * m_r * e}, {&w.rtiles, Bn * H * nx_r * nin_r * e},
-                {&w.rhblk, Bn * H * nin_r * nin_r * e}, {&w.rgrad, Bn * n_r * e}, {&w.rlam, Bn * m_r * e},
+                {&w.rhblk, Bn * H * nin_r * nin_r * e}, {&w.rlam, Bn * m_r * e},
                 {&w.rZin, Bn * n * e}, {&w.rS0, Bn * nx * e}, {&w.rZout, Bn * n * e},
                 {&w.robj, (size_t)obj_offsets(H, nx, nu).total * e}});
+        if (rolling) al.push_back({&w.rgrad, Bn * n_r * e});     // (rate: the gradient comes from the augmented table)
         for (const Req& x : al) if (int rc = w.alloc(x.p, x.bytes)) return rc;
         NEMPC_HIP(hipMemset(w.n_active, 0, 8 * sizeof(int)));
         if (int rc = w.alloc((void**)&w.hpoll, 4 * sizeof(int), hipHostMallocDefault)) return rc;
         if (int rc = w.alloc((void**)&w.hpub, 8 * sizeof(int), hipHostMallocMapped)) return rc;
         NEMPC_HIP(hipHostGetDevicePointer((void**)&w.hpub_dev, w.hpub, 0));
+        if (augmented) NEMPC_HIP(hipMemsetAsync(w.rlam, 0, Bn * m_r * e, s));     // (box rows of the handle keep zero multipliers)
         if (rolling) {
-            NEMPC_HIP(hipMemsetAsync(w.rlam, 0, Bn * m_r * e, s));     // (box rows of the handle keep zero multipliers)
             const RollTablesHost t = build_roll_tables();
             struct { int** p; const std::vector<int>* v; } tb[] = {{&w.rt.src, &t.src}, {&w.rt.src0, &t.src0}, {&w.rt.prim, &t.prim},
                                                                    {&w.rt.isprim, &t.isprim}, {&w.rt.dcol, &t.dcol}, {&w.rt.shift, &t.shift}};
@@ -335,7 +348,7 @@ struct Solve {
             }
             w.prim_host = t.prim;
         }
-        w.cap = B; w.m = m; w.n = n; w.ex_per = ex_per;
+        w.cap = B; w.m = m; w.n = n; w.ex_per = ex_per; w.aug = aug;
         return NEMPC_OK;
     }
     // bounds -> device (dtype T); +-inf become +-max so that comparisons stay exact.  Box ROWS on the states
@@ -343,16 +356,26 @@ struct Solve {
     // state variables for this solver: intersected here, what controller.py:101-105 of this package does on the host.
     int upload_bounds(const double* lb, const double* ub) {
         const T big = std::numeric_limits<T>::max();
-        std::vector<T> hl(n, -big), hu(n, big);      // (rolling: the copies inside the window state carry no bounds of their own)
+        std::vector<T> hl(n, -big), hu(n, big);      // (rolling: the copies inside the window state carry no bounds of their own;
+                                                     //  rate: the caller's bounds sit on the s slots, the limits on v)
         std::vector<double> blo, bhi;
         if (int rc = intersect_bounds(h, lb, ub, true, "nempc_solve", blo, bhi)) return rc;
         for (int i = 0; i < n_r; ++i) {
             const double lo = blo[i], hi = bhi[i];
-            const int k = rolling ? ws.prim_host[i] : i;
+            const int k = rolling ? ws.prim_host[i] : (rate ? rate_bound_slot(rd, i) : i);
             hl[k] = std::isfinite(lo) ? (T)lo : -big;
             hu[k] = std::isfinite(hi) ? (T)hi : big;
             has_bounds = has_bounds || std::isfinite(lo) || std::isfinite(hi);
         }
+        if (rate)
+            for (int t = 0; t < H; ++t)
+                for (int j = 0; j < nu; ++j) {
+                    const double lo = h.rate.dlo[(size_t)t * nu + j], hi = h.rate.dhi[(size_t)t * nu + j];
+                    const int k = rate_limit_slot(rd, t, j);
+                    hl[k] = std::isfinite(lo) ? (T)lo : -big;
+                    hu[k] = std::isfinite(hi) ? (T)hi : big;
+                    has_bounds = has_bounds || std::isfinite(lo) || std::isfinite(hi);
+                }
         // per-problem bounds live on the device: whether a problem has a finite bound is decided there, per problem
         // (solver_init_bound_kernel: mu = 0 for one that has none); the host plans for the barrier
         bound_rows = h.bbind.on();
@@ -399,6 +422,45 @@ struct Solve {
                 tab[ao.cu + t * nu + i] = (T)oh.cu[t * nu + i];
             }
         }
+        return upload_aug_table(tab);
+    }
+    // rate: Q_aug = blkdiag(Q, R), QT_aug = blkdiag(QT, R) and [xref ; uref], [cx ; cu] on s = [x ; u]; R_aug = S and zero
+    // reference / linear cost on the control move v
+    int upload_rate_objective() {
+        const ObjOffsets ao = obj_offsets(H, nx, nu);
+        const ObjHost& oh = h.obj_host;
+        const std::vector<double>& QT = h.obj_QT.empty() ? oh.Q : h.obj_QT;
+        const std::vector<double>& S = h.rate.S;
+        std::vector<T> tab((size_t)ao.total, T(0));
+        for (int i = 0; i < nx_r; ++i)
+            for (int j = 0; j < nx_r; ++j) {
+                tab[ao.Q + i * nx + j] = (T)oh.Q[i * nx_r + j];
+                tab[ao.Qs + i * nx + j] = (T)(oh.Q[i * nx_r + j] + oh.Q[j * nx_r + i]);
+                tab[ao.QT + i * nx + j] = (T)QT[i * nx_r + j];
+                tab[ao.QTs + i * nx + j] = (T)(QT[i * nx_r + j] + QT[j * nx_r + i]);
+            }
+        for (int i = 0; i < nu; ++i)
+            for (int j = 0; j < nu; ++j) {
+                const int e = (nx_r + i) * nx + nx_r + j;
+                tab[ao.Q + e] = tab[ao.QT + e] = (T)oh.R[i * nu + j];
+                tab[ao.Qs + e] = tab[ao.QTs + e] = (T)(oh.R[i * nu + j] + oh.R[j * nu + i]);
+                tab[ao.R + i * nu + j] = (T)S[i * nu + j];
+                tab[ao.Rs + i * nu + j] = (T)(S[i * nu + j] + S[j * nu + i]);
+            }
+        for (int t = 0; t < H; ++t) {
+            for (int i = 0; i < nx_r; ++i) {
+                tab[ao.xref + t * nx + i] = (T)oh.xref[t * nx_r + i];
+                tab[ao.cx + t * nx + i] = (T)oh.cx[t * nx_r + i];
+            }
+            for (int i = 0; i < nu; ++i) {
+                tab[ao.xref + t * nx + nx_r + i] = (T)oh.uref[t * nu + i];
+                tab[ao.cx + t * nx + nx_r + i] = (T)oh.cu[t * nu + i];
+            }
+        }
+        return upload_aug_table(tab);
+    }
+    // (uploaded when it changes, like the bounds)
+    int upload_aug_table(const std::vector<T>& tab) {
         const size_t tb = tab.size() * sizeof(T);
         if (ws.robj_host.size() != tb || memcmp(ws.robj_host.data(), tab.data(), tb) != 0) {
             NEMPC_HIP(hipMemcpyAsync(ws.robj, tab.data(), tb, hipMemcpyHostToDevice, s));
@@ -494,6 +556,15 @@ struct Solve {
             if ((rc = upload_roll_objective())) return rc;
             obj_dev = ws.robj;
         }
+        if (rate) {
+            // the same for the rate state: augmented guess, s_{-1} = [x0 ; u_prev], the table with S on the control move
+            hipLaunchKernelGGL(rate_build_kernel<T>, dim3(gBn), dim3(256), 0, s, B, rd, (const T*)Z, (const T*)X0,
+                               (const T*)h.rate.u_prev, (const T*)ws.lb, (const T*)ws.ub, (T)o.mu_init, has_bounds ? 1 : 0,
+                               (T*)ws.rZin, (T*)ws.rS0);
+            Zstart = ws.rZin; X0start = ws.rS0;
+            if ((rc = upload_rate_objective())) return rc;
+            obj_dev = ws.robj;
+        }
         if (bound_rows && !ws.lbw) {     // (a rebuilt workspace starts without them; sized like its other buffers)
             const size_t nb = (size_t)ws.cap * n * sizeof(T);
             if ((rc = ws.alloc(&ws.lbw, nb)) || (rc = ws.alloc(&ws.ubw, nb))) return rc;
@@ -536,7 +607,7 @@ struct Solve {
         a.reg_raise = kn.reg_raise > 1.0 && kn.reg_raise <= 100.0 ? kn.reg_raise : 3.1622776601683795;
         const int lsm_carry = o.linesearch == 0 ? (wave_wanted ? 1 : 2) : o.linesearch;
         carry = lsm_carry == 2 && !kn.no_carry && a.use_lds && h.variant == NEMPC_KERNEL_MFMA && h.cfg.integrator != NEMPC_RK4 &&
-                !rolling;
+                !augmented;
         // the trial point's Lagrangian blocks from the launch that evaluates it (compiled shape): an iteration is then the LQ
         // solve, ONE callback launch and the acceptance test
         hess_trial = carry && a.fuse_step && kn.hess_trial != 0;
@@ -548,9 +619,9 @@ struct Solve {
         published_polls = !wave_wanted;  // small stages (chains of latency-bound launches): no blocking polls, the host
                                             // reads the counter the device publishes
         trace = kn.trace_slot >= 0 && kn.trace_slot < B;
-        // rolling: the callbacks read the caller's x0 / history by problem index, so the batch keeps its order (a finished
+        // augmented: the callbacks read the caller's x0 / history by problem index, so the batch keeps its order (a finished
         // problem is skipped by every solver kernel; its callback rows are evaluated and ignored)
-        compact = o.compact != 0 && !trace && !rolling;
+        compact = o.compact != 0 && !trace && !augmented;
         return NEMPC_OK;
     }
     // ---- callbacks.  Plain models: the handle's launches on the solver's buffers.  Rolling: gather the caller's
@@ -591,6 +662,22 @@ struct Solve {
                            full ? (T*)ws.grad : (T*)nullptr);
         return NEMPC_OK;
     }
+    // the same for a rate binding (solver_rate_impl.h): the network at x_t, u_{t-1} + v_t; f and the gradient from the
+    // augmented table inside the spread kernel (no objective launch on the caller's variables)
+    int rate_eval(const void* Zaug, const void* lam_aug) {
+        const bool full = lam_aug != nullptr;
+        hipLaunchKernelGGL(rate_gather_kernel<T>, dim3(gRn), dim3(256), 0, s, B, rd, m_r, 0, (const T*)Zaug, (const T*)ws.rS0,
+                           (T*)ws.rZ, (const T*)lam_aug, full ? (T*)ws.rlam : (T*)nullptr);
+        int r = launch_rows(B, ws.rZ, X0, ws.rg, full ? ws.rtiles : nullptr, h.d_tiles_ws);
+        if (r) return r;
+        if (full && (r = launch_blocks(B, ws.rZ, X0, ws.rlam, ws.rhblk))) return r;
+        hipLaunchKernelGGL(rate_spread_kernel<T>, dim3(B * H), dim3(256), 0, s, rd, m_r, (const T*)Zaug, (const T*)ws.rS0,
+                           (const T*)ws.rg, full ? (const T*)ws.rtiles : (const T*)nullptr,
+                           full ? (const T*)ws.rhblk : (const T*)nullptr, (const T*)ws.robj, obj_offsets(H, nx, nu),
+                           full ? (T*)ws.g : (T*)ws.gt, full ? (T*)ws.tiles : (T*)nullptr, full ? (T*)ws.hblk : (T*)nullptr,
+                           full ? (T*)ws.grad : (T*)nullptr, full ? (T*)ws.f : (T*)nullptr);
+        return NEMPC_OK;
+    }
     // (A block-wise mirrored convexification of the stage Hessians, for the problems whose sweep needed damping, was built and
     // measured in round 4 -- profiles/r04_solver_convexify_c3.txt: +3 - 5 % problems converged at 1.5 ms per iteration; removed
     // in round 5: indefiniteness is not what holds the configs[2] solves back, DESIGN "Batched solver".)
@@ -603,9 +690,9 @@ struct Solve {
         const bool rk4_pipeline = h.variant != NEMPC_KERNEL_VALU && h.cfg.integrator == NEMPC_RK4;
         bool fused_eval = false;
         int rc;
-        if (rolling) {
+        if (augmented) {
             fused_eval = true;                  // (f and grad come with it)
-            rc = roll_eval(Zc, lam);
+            rc = rolling ? roll_eval(Zc, lam) : rate_eval(Zc, lam);
         } else if (have_eval) {
             // deferred backtracking on a compiled shape: the trial evaluation of the last iteration was a full one and the
             // acceptance kernel kept, per problem, the evaluation of the point it stands on -- only the blocks are new, and
@@ -714,10 +801,10 @@ struct Solve {
     int line_search() {
         void* Zc = ws.Zc[cur];
         const void* X0c = ws.X0c[cur];
-        const int lsm = rolling ? 2 : (o.linesearch == 0 ? (wave_wanted ? 1 : 2) : o.linesearch);
+        const int lsm = augmented ? 2 : (o.linesearch == 0 ? (wave_wanted ? 1 : 2) : o.linesearch);
         // second-order correction of rejected full steps: inner-loop backtracking only (the deferred form accepts inside the
         // next LQ kernel); NEMPC_SOLVER_SOC=0 switches it off (A/B, tests)
-        const bool soc_on = lsm != 2 && !rolling && kn.soc;
+        const bool soc_on = lsm != 2 && !augmented && kn.soc;
         int pending = 0, rc = NEMPC_OK;
         int pflip = 0;          // which of the two lists of searching problems is read next (the correction stage swaps them)
         const void* const extra_all = h.d_extra;      // (h.d_extra points at a dense list's extras around its launches only)
@@ -756,8 +843,8 @@ struct Solve {
                 else { rc = launch_rows_mfma(h, nb, ws.Zt, X0t, ro, s); a.carry = 1; }
             }
             if (trial_done) {
-            } else if (rolling) {
-                rc = roll_eval(ws.Zt, nullptr);
+            } else if (augmented) {
+                rc = rolling ? roll_eval(ws.Zt, nullptr) : rate_eval(ws.Zt, nullptr);
             } else {
                 if (!fused_trial) {
                     const RowsOut ro = fused_eval_out(ws.gt, nullptr, ws.ft, nullptr);
@@ -927,9 +1014,12 @@ struct Solve {
         if (accept_pending) accept_now();           // (the loop was left with a trial point evaluated and not yet tested)
         hipLaunchKernelGGL(solver_scatter_kernel<T>, dim3(B), dim3(256), 0, s, B, n, (const T*)ws.Zc[cur],
                            (const int*)ws.stc[cur], (const int*)ws.orig[cur], (const int*)ws.itc[cur],
-                           rolling ? (T*)ws.rZout : (T*)Z, status_dev, (int*)o.iters_out);
+                           augmented ? (T*)ws.rZout : (T*)Z, status_dev, (int*)o.iters_out);
         if (rolling)      // the caller's variables are the primary copies
             hipLaunchKernelGGL(roll_in_kernel<T>, dim3(gRn), dim3(256), 0, s, B, n, n_r, H, nx_r, nx, m_r, ws.rt, (const T*)ws.rZout,
+                               (T*)Z, (const T*)nullptr, (T*)nullptr);
+        if (rate)         // ... or, under a rate binding, the x and u slots of the state
+            hipLaunchKernelGGL(rate_gather_kernel<T>, dim3(gRn), dim3(256), 0, s, B, rd, m_r, 1, (const T*)ws.rZout, (const T*)ws.rS0,
                                (T*)Z, (const T*)nullptr, (T*)nullptr);
         if (duals.any())  // (plain models only, solver_run: n, m are the caller's)
             hipLaunchKernelGGL(solver_scatter_duals_kernel<T>, dim3(B), dim3(256), 0, s, B, n, m, H * nx, (const T*)ws.Zc[cur],
@@ -989,6 +1079,11 @@ int solver_run(Handle& h, int B, const void* X0, void* Z, const double* lb, cons
     if (duals.any() && h.w > 1) {
         set_error("nempc_solve_duals: multipliers of a rolling_window > 1 handle are not supported (the costates of the window "
                   "state are not mapped back to the caller's rows); pass NULL for lam, zl and zu");
+        return NEMPC_EUNSUPPORTED;
+    }
+    if (duals.any() && h.rate.on()) {
+        set_error("nempc_solve_duals: multipliers under a rate binding (nempc_bind_rate) are not supported (the costates of the "
+                  "augmented state are not mapped back to the caller's rows); pass NULL for lam, zl and zu");
         return NEMPC_EUNSUPPORTED;
     }
     return h.cfg.dtype == NEMPC_F64 ? solve_typed<double>(h, B, X0, Z, lb, ub, o, status_dev, iters_host, duals, s)

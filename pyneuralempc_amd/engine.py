@@ -38,6 +38,44 @@ def _as_c_double(a):
     return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
+def check_rate_args(H, nu, dtype, device, u_prev, S, du_lb, du_ub):
+    """Arguments of CallbackEngine.bind_rate, checked before the C call (no device is touched): u_prev a `dtype` tensor
+    (B,nu) on `device`, B >= 1, required; S (nu,nu) finite; du_lb / du_ub (nu,) or (H,nu) -- both the same form when both
+    are given --, no NaN, du_lb < du_ub on every entry.  -> (S, du_lb, du_ub as float64 arrays or None, per_stage 0 | 1)."""
+    H, nu = int(H), int(nu)
+    if u_prev is None:
+        raise ValueError("bind_rate: u_prev is required whenever S, du_lb or du_ub is given")
+    if (not isinstance(u_prev, torch.Tensor) or u_prev.dtype != dtype or u_prev.device != torch.device(device) or u_prev.dim() != 2
+            or u_prev.shape[1] != nu or u_prev.shape[0] < 1):
+        got = (tuple(u_prev.shape), u_prev.dtype, str(u_prev.device)) if isinstance(u_prev, torch.Tensor) else type(u_prev).__name__
+        raise ValueError(f"bind_rate: u_prev must be a {dtype} tensor (B,{nu}) on {device}, got {got}")
+    Sa = None
+    if S is not None:
+        Sa = np.asarray(S, dtype=np.float64)
+        if Sa.shape != (nu, nu) or not np.isfinite(Sa).all():
+            raise ValueError(f"bind_rate: S must be a finite {(nu, nu)} matrix, got shape {Sa.shape}")
+    lims, forms = {}, set()
+    for name, v in (("du_lb", du_lb), ("du_ub", du_ub)):
+        if v is None:
+            continue
+        a = np.asarray(v, dtype=np.float64)
+        if a.shape not in ((nu,), (H, nu)):
+            raise ValueError(f"bind_rate: {name} must have shape {(nu,)} (every step) or {(H, nu)} (per step), got {a.shape}")
+        if np.isnan(a).any():
+            raise ValueError(f"bind_rate: {name} has a NaN")
+        lims[name] = a
+        forms.add(a.ndim)
+    if len(forms) > 1:        # one form in the C interface
+        lims = {k: np.broadcast_to(a, (H, nu)) for k, a in lims.items()}
+    if len(lims) == 2 and (lims["du_lb"] >= lims["du_ub"]).any():
+        raise ValueError("bind_rate: du_lb >= du_ub on some entry (the barrier needs an interior)")
+    if "du_lb" in lims and np.isposinf(lims["du_lb"]).any() or "du_ub" in lims and np.isneginf(lims["du_ub"]).any():
+        raise ValueError("bind_rate: du_lb >= du_ub on some entry (the barrier needs an interior)")
+    per_stage = 1 if any(a.ndim == 2 for a in lims.values()) else 0
+    cont = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    return cont(Sa), cont(lims.get("du_lb")), cont(lims.get("du_ub")), per_stage
+
+
 def _ptr(t):
     """device pointer of a tensor for the C ABI; None stays None (an optional argument)"""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
@@ -72,6 +110,7 @@ class CallbackEngine:
         self._extra = None
         self._tracking = None
         self._bounds = None
+        self._rate = None
         self.integrator = integrator if isinstance(integrator, int) else _lib.INTEGRATOR_IDS[integrator]
         self.DT = float(DT)
         self.kernel = kernel
@@ -140,6 +179,8 @@ class CallbackEngine:
             self.bind_tracking(**self._tracking[0], offset=self._tracking[1])
         if self._bounds is not None:
             self.bind_bounds(**self._bounds[0], offset=self._bounds[1])
+        if self._rate is not None:
+            self.bind_rate(**self._rate)
         self._refresh_dims()
         self._buffers = {}
 
@@ -324,6 +365,30 @@ class CallbackEngine:
         removes the binding.  eval / hess / rollout do not read it."""
         self._bounds = self._bind_rows(self.lib.nempc_bind_bounds, "bounds", ("xlb", "xub", "ulb", "uub"), (("xlb", xlb), ("xub", xub)),
                                        (("ulb", ulb), ("uub", uub)), offset)
+
+    def bind_rate(self, u_prev=None, S=None, du_lb=None, du_ub=None):
+        """Bind an input-rate penalty and rate limits for the following solve calls (nempc_bind_rate): with
+        du_t = u_t - u_{t-1} and u_{-1} = u_prev[b], problem b minimises f(z) + sum_t du_t' S du_t inside du_lb <= du_t <= du_ub
+        (and the bounds of the call as before).  u_prev: device tensor (B,nu) of the engine's dtype, kept alive here, not copied
+        (write into it between solves to move on); S (nu,nu), used as given like R, None = no penalty; du_lb / du_ub (nu,) for
+        every step or (H,nu) per step, None or +-inf = no limit, du_lb < du_ub on every entry.  bind_rate() with nothing
+        removes the binding.  eval / hess / rollout do not read it; kkt_residual, sensitivity, kkt_solve and
+        solve(return_duals=True) refuse while it is on, and so does a solve with bind_tracking / bind_bounds rows."""
+        fn = getattr(self.lib, "nempc_bind_rate", None)
+        if fn is None:
+            raise RuntimeError("this libnempc.so has no nempc_bind_rate")
+        if u_prev is None and S is None and du_lb is None and du_ub is None:
+            _lib.check(fn(self._handle, None, None, None, 0, None, 0))
+            self._rate = None
+            return
+        if self.rolling_window > 1:
+            raise ValueError("bind_rate: rolling-window models are not supported")
+        Sa, lo, hi, per_stage = check_rate_args(self.H, self.nu, self.dtype, self.device, u_prev, S, du_lb, du_ub)
+        u_prev = u_prev if u_prev.is_contiguous() else u_prev.contiguous()
+        ptr = lambda a: None if a is None else _as_c_double(a)[1]
+        _lib.check(fn(self._handle, ptr(Sa), ptr(lo), ptr(hi), per_stage, ctypes.c_void_p(u_prev.data_ptr()),
+                      int(u_prev.shape[0])))
+        self._rate = dict(u_prev=u_prev, S=Sa, du_lb=lo, du_ub=hi)
 
     def _bind_rows(self, bind, what, order, xpair, upair, offset):
         """bind_tracking / bind_bounds: check the (B,L,d) device tensors (xpair: the two of width nx, upair: of width nu),

@@ -16,7 +16,7 @@ from .slsqp import Slsqp, SlsqpProblemFactory
 
 class DeviceSqp(Slsqp):
     def __init__(self, max_iteration=200, tolerance=None, verbose=0, init_with_last_result=False, warm_mu=1e-4,
-                 certificate=False, gain=False, **solver_opts):
+                 certificate=False, gain=False, du_weight=None, du_lb=None, du_ub=None, **solver_opts):
         """tolerance: max |defect| and relative step at convergence (tol_constraint = tol_step); None = what an iterate
         of the model's precision can reach (CallbackEngine.solve: 1e-8 for fp64, 1e-4 for fp32 -- an fp32 iterate stalls
         near 1e-5 and would never report success against 1e-8); warm_mu: initial barrier
@@ -26,7 +26,13 @@ class DeviceSqp(Slsqp):
         the point on the device (``last_kkt``: stationarity, primal feasibility, complementarity, dual feasibility --
         CallbackEngine.kkt_residual); without it nothing more than the solve is launched and both stay None.  gain=True:
         every solve also keeps the feedback gain of its result, ``last_gain`` (nu,nx) = du_0*/dx0 for
-        u = u0* + K0 (x_measured - x0), and ``last_gain_status`` (CallbackEngine.sensitivity: 0 ok, else the gain is NaN)."""
+        u = u0* + K0 (x_measured - x0), and ``last_gain_status`` (CallbackEngine.sensitivity: 0 ok, else the gain is NaN).
+        du_weight (nu,nu), du_lb / du_ub (nu,) or (H,nu): an input-rate penalty sum_t du_t' du_weight du_t and rate limits on
+        du_t = u_t - u_{t-1} (CallbackEngine.bind_rate).  u_{-1} is the first control of the last successful solve -- the one
+        NMPC.next's caller applied --, zeros on the first call, or what ``NMPC.next(u_prev=)`` / ``set_u_prev`` gave for the
+        next solve.  Not together with certificate or gain (the library refuses multipliers under a rate binding)."""
+        if (du_weight is not None or du_lb is not None or du_ub is not None) and (certificate or gain):
+            raise ValueError("DeviceSqp: du_weight / du_lb / du_ub cannot be combined with certificate=True or gain=True")
         super().__init__(max_iteration=max_iteration, tolerance=tolerance, verbose=verbose,
                          init_with_last_result=init_with_last_result)
         self.warm_mu = warm_mu
@@ -38,6 +44,17 @@ class DeviceSqp(Slsqp):
         self.gain = bool(gain)
         self.last_gain = None
         self.last_gain_status = None
+        self.rate = None if du_weight is None and du_lb is None and du_ub is None else dict(S=du_weight, du_lb=du_lb, du_ub=du_ub)
+        self._u_prev = None
+
+    def set_u_prev(self, u_prev, nu=None):
+        """The control applied before the next solve (nu,), for the rate terms."""
+        if self.rate is None:
+            raise ValueError("DeviceSqp: u_prev needs rate terms (du_weight, du_lb or du_ub)")
+        v = np.asarray(u_prev, dtype=np.float64).reshape(-1)
+        if nu is not None and v.shape != (int(nu),):
+            raise ValueError(f"u_prev must have shape {(int(nu),)}, got {tuple(np.shape(u_prev))}")
+        self._u_prev = v
 
     def get_factory(self):
         return SlsqpProblemFactory()      # the same problem object: x0, parameters, fused evaluator, initial values
@@ -60,6 +77,19 @@ class DeviceSqp(Slsqp):
             opts["mu_init"] = self.warm_mu
         opts.update(self.solver_opts)
         X0 = eng.to_device(np.asarray(problem.get_init_value(), dtype=np.float64).reshape(1, -1))
+        if self.rate is not None:
+            up = np.zeros(eng.nu) if self._u_prev is None else self._u_prev
+            eng.bind_rate(u_prev=eng.to_device(up.reshape(1, -1)), **self.rate)
+            try:
+                Z, status, iters = eng.solve(X0, eng.to_device(z0), lb, ub, **opts)
+            finally:
+                eng.bind_rate()
+            self.last_iterations = iters
+            if int(status[0].item()) != 0:
+                return Optimizer.FAIL
+            self.prev_result = Z[0].to("cpu").double().numpy()
+            self._u_prev = self.prev_result[H * eng.nx:H * eng.nx + eng.nu].copy()
+            return Optimizer.SUCCESS
         if self.certificate or self.gain:
             Z, status, iters, duals = eng.solve(X0, eng.to_device(z0), lb, ub, return_duals=True, **opts)
             if self.certificate:
