@@ -11,6 +11,7 @@
 
 #include "nempc_internal.h"
 #include "activations.h"
+#include "stage_aug.h"      // window_var: the window's column order
 
 namespace nempc {
 
@@ -87,22 +88,6 @@ int dev_alloc(P** p, size_t bytes) {
     return NEMPC_OK;
 }
 
-// decision variable (index into z) that tile / block column d of step t reads, or -1 when that window slot is
-// data (x0 or the bound history).  Column order = the network's input order: w state rows then w control rows,
-// oldest first unless rev (model/tensorflow.py:112-130).  For w = 1: [x_{t-1} | u_t].
-int window_var(const Handle& h, int t, int d) {
-    const int H = h.cfg.H, nx = h.cfg.nx, nu = h.cfg.nu, back = h.w - 1, wx = h.w * nx;
-    if (d < wx) {
-        const int j = d / nx, c = d % nx;
-        const int tau = t + (h.rev ? -j : j - back);   // index into [x0 ; states]
-        return tau >= 1 ? (tau - 1) * nx + c : -1;
-    }
-    d -= wx;
-    const int j = d / nu, c = d % nu;
-    const int tau = t + (h.rev ? -j : j - back);
-    return tau >= 0 ? H * nx + tau * nu + c : -1;
-}
-
 int rebuild_structure(Handle& h) {
     const int H = h.cfg.H, nx = h.cfg.nx, nu = h.cfg.nu, nin = h.nin, n = h.n;
     h.m = H * nx + (h.box ? H * nx : 0);
@@ -126,7 +111,7 @@ int rebuild_structure(Handle& h) {
             const int base = t * nx * nin + i * nin;
             ent.clear();
             for (int d = 0; d < nin; ++d) {
-                const int v = window_var(h, t, d);
+                const int v = window_var(H, nx, nu, h.w, h.rev, t, d);
                 if (v >= 0) ent.emplace_back(v, base + d);
             }
             ent.emplace_back(t * nx + i, MAP_MINUS_ONE);   // -x_t; the window only reaches state blocks < t
@@ -193,7 +178,7 @@ int upload_objective(Handle& h, const ObjHost& o_in) {
         std::vector<std::vector<int32_t>> codes((size_t)n * n);
         std::vector<int> wv(nin);
         for (int t = 0; t < H; ++t) {
-            for (int d = 0; d < nin; ++d) wv[d] = window_var(h, t, d);
+            for (int d = 0; d < nin; ++d) wv[d] = window_var(H, nx, nu, h.w, h.rev, t, d);
             for (int pp = 0; pp < nin; ++pp)
                 for (int qq = 0; qq < nin; ++qq)
                     if (wv[pp] >= 0 && wv[qq] >= 0) codes[(size_t)wv[pp] * n + wv[qq]].push_back(t * nin * nin + pp * nin + qq);

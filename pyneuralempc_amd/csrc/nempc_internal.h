@@ -10,6 +10,7 @@
 
 #include "jac_resident.h"
 #include "mfma_plan.h"
+#include "obj_offsets.h"      // ObjOffsets / obj_offsets: the objective table's layout
 #include "post_plan.h"
 #include "nempc.h"
 
@@ -246,26 +247,6 @@ struct Handle {
     mutable int last_rollout_kernel = ROLLOUT_NONE;  // RolloutKernel of the most recent roll-out (nempc_last_rollout_kernel)
     int last_egrad_kernel = 0;                       // EgradKernel (egrad_plan.h) of the most recent nempc_extra_grad
 };
-
-struct ObjOffsets {  // element offsets into Handle::d_obj
-    int Q, Qs, R, Rs, xref, uref, cx, cu, QT, QTs, total;   // QT: weight of the last step (terminal cost), QTs = QT + QT^T
-};
-__host__ __device__ inline ObjOffsets obj_offsets(int H, int nx, int nu) {
-    ObjOffsets o;
-    int p = 0;
-    o.Q = p; p += nx * nx;
-    o.Qs = p; p += nx * nx;
-    o.R = p; p += nu * nu;
-    o.Rs = p; p += nu * nu;
-    o.xref = p; p += H * nx;
-    o.uref = p; p += H * nu;
-    o.cx = p; p += H * nx;
-    o.cu = p; p += H * nu;
-    o.QT = p; p += nx * nx;
-    o.QTs = p; p += nx * nx;
-    o.total = p;
-    return o;
-}
 
 // Dynamic LDS above 64 KiB needs hipFuncAttributeMaxDynamicSharedMemorySize, which is a per-device property of the
 // kernel: remember the largest size configured per (device, kernel) so the attribute call stays off the hot path.

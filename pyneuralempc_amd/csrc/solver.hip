@@ -46,6 +46,10 @@
 //     solver_compact_impl.h  partition / gather of the unconverged problems, scatter of the results
 //     solver_roll_impl.h     rolling-window models: RollTables and the roll_* kernels
 //     solver_rate_impl.h     input-rate penalty and limits (nempc_bind_rate): the rate_* kernels (index arithmetic: rate_index.h)
+//     solver_aug.h           StageAug<T>: what of a solve is specific to a stage augmentation (window, rate) -- workspace, bounds,
+//                            start, the callbacks in augmented form, the solution handed back; host side, launches the two above
+//     stage_aug.h            ... and its host arithmetic (nothing of HIP: tests/stage_aug_check.cpp): stage dimensions, window_var,
+//                            the window's tables, bound slots, the objective table over the augmented stage
 // The merit and bound headers come first because the LQ kernels call their bodies.
 #include <chrono>
 #include <cmath>
@@ -69,23 +73,14 @@
 #include "solver_compact_impl.h"
 #include "solver_roll_impl.h"
 #include "solver_rate_impl.h"
+#include "solver_aug.h"
 
 namespace nempc {
 
 namespace {
 
-// The stage the solver runs on: the handle's own, or an augmentation of it -- the window of a rolling-window model
-// (solver_roll_impl.h) or [x ; u] with the control move as the stage control (nempc_bind_rate, solver_rate_impl.h)
-enum Augmentation { AUG_NONE = 0, AUG_WINDOW = 1, AUG_RATE = 2 };
-
 struct SolverWs {
-    int aug = AUG_NONE;                       // the augmentation the buffers were sized for
-    // augmented problems: the window's tables, the caller-side evaluation buffers and the augmented objective table
-    RollTables rt;
-    void *rZ = nullptr, *rg = nullptr, *rtiles = nullptr, *rhblk = nullptr, *rgrad = nullptr, *rlam = nullptr,
-         *rZin = nullptr, *rS0 = nullptr, *rZout = nullptr, *robj = nullptr;
-    std::vector<int> prim_host;               // (n_r) primary copy of every caller variable
-    std::vector<unsigned char> robj_host;     // the augmented objective table as last uploaded
+    AugWs aug;                                // what a stage augmentation keeps (solver_aug.h); aug.kind: the one the buffers were sized for
     void *Zt = nullptr, *f = nullptr, *ft = nullptr, *grad = nullptr, *g = nullptr, *gt = nullptr, *tiles = nullptr;
     void *tiles_t = nullptr, *grad_t = nullptr;     // trial point's tiles and objective gradient (carried over on acceptance)
     void *lam_t = nullptr, *hblk_t = nullptr;       // ... its multipliers and Lagrangian blocks (blocks + evaluation in one launch)
@@ -187,20 +182,17 @@ struct SolverKnobs : ProcessKnobs {
     bool soc = env_enabled("NEMPC_SOLVER_SOC");      // (read per solve)
 };
 
-struct RollTablesHost { std::vector<int> src, src0, prim, isprim, dcol, shift; };
-
 // One solve: handle, workspace, options, knobs, dimensions, what plan_lq decides, the kernels' arguments and the state the
 // iteration carries from one step to the next.  run() is the algorithm; the members behind it are its steps.
 template <typename T>
 struct Solve {
     Handle& h; SolverWs& ws; const nempc_solver_opts& o; const int B; const void* const X0; const hipStream_t s;
     const SolverDuals duals;      // where the multipliers of the returned iterates go (nempc_solve_duals; all null: nowhere)
-    // rolling-window models and rate bindings run as a plain problem in an augmented state, see RollTables / rate_index.h:
-    // nx, nin, n, m are the SOLVER's stage dimensions; *_r the handle's (the caller's variables, the callbacks' shapes)
-    const int aug; const bool augmented, rolling, rate;      // rolling: AUG_WINDOW, rate: AUG_RATE
-    const int H, nx_r, nu, nin_r, n_r, m_r, back, nx, nin, n, m;
-    const RateDims rd;
-    const size_t ex_per; const unsigned gBn, gRn;      // grids of the element-wise kernels over the solver's / the caller's variables
+    // rolling-window models and rate bindings run as a plain problem in an augmented state (solver_aug.h): H, nx, nu, nin, n, m are
+    // the SOLVER's stage dimensions
+    StageAug<T> aug; const bool augmented;
+    const int H, nu, nx, nin, n, m;
+    const size_t ex_per; const unsigned gBn;      // grid of the element-wise kernels over the solver's variables
     const SolverKnobs kn = read_knobs();
     ExtraBindingGuard extra_guard; SolverArgs a{}; bool has_bounds = false;
     // plan_lq decides (besides fields of `a`): the kernel; stages wide enough to spread over a wave (matrix-core-bound
@@ -226,13 +218,10 @@ struct Solve {
     static SolverWs& workspace(Handle& h) { return *static_cast<SolverWs*>(h.solver_ws ? h.solver_ws : (h.solver_ws = new SolverWs())); }
     Solve(Handle& hh, int BB, const void* X0_, const nempc_solver_opts& oo, const SolverDuals& dd, hipStream_t ss)
         : h(hh), ws(workspace(hh)), o(oo), B(BB), X0(X0_), s(ss), duals(dd),
-          aug(h.w > 1 ? AUG_WINDOW : (h.rate.on() ? AUG_RATE : AUG_NONE)), augmented(aug != AUG_NONE), rolling(aug == AUG_WINDOW),
-          rate(aug == AUG_RATE), H(h.cfg.H), nx_r(h.cfg.nx), nu(h.cfg.nu),
-          nin_r(h.nin), n_r(h.n), m_r(h.m), back(h.w - 1), nx(rolling ? h.w * nx_r + back * nu : (rate ? nx_r + nu : nx_r)),
-          nin(augmented ? nx + nu : nin_r), n(augmented ? H * (nx + nu) : n_r), m(augmented ? H * nx : m_r),
-          rd(rate_dims(h.cfg.H, h.cfg.nx, h.cfg.nu)), ex_per((size_t)H * h.ne),
-          gBn((unsigned)(((size_t)BB * std::max(n, std::max(m, nx)) + 255) / 256)),
-          gRn((unsigned)(((size_t)BB * n_r + 255) / 256)), extra_guard(hh), Bact(BB), last_nact(BB) {}
+          aug(hh, ws.aug, BB, ss), augmented(aug.on()), H(h.cfg.H), nu(h.cfg.nu), nx(aug.d.nx), nin(aug.d.nin), n(aug.d.n),
+          m(augmented ? aug.d.m : h.m),      // (plain: the handle's rows, box rows included)
+          ex_per((size_t)H * h.ne), gBn((unsigned)(((size_t)BB * std::max(n, std::max(m, nx)) + 255) / 256)),
+          extra_guard(hh), Bact(BB), last_nact(BB) {}
     int run(void* Z, const double* lb, const double* ub, int32_t* status_dev, int32_t* iters_host) {
         int rc;
         if ((rc = ensure_workspace()) || (rc = upload_bounds(lb, ub)) || (rc = start(Z))) return rc;
@@ -250,60 +239,13 @@ struct Solve {
         }
         return finish(Z, status_dev, iters_host);
     }
-    // index tables of a rolling-window model (RollTables, on the host).  x-slot k of s_tau is x_{tau-k} (index into
-    // [x0 ; states]), u-slot k is u_{tau-1-k}
-    RollTablesHost build_roll_tables() const {
-        const int wx = h.w * nx_r;
-        auto data_x = [&](int tau, int c) { return tau == 0 ? c : nx_r + (back + tau) * nx_r + c; };           // tau <= 0
-        auto data_u = [&](int tau, int c) { return nx_r + back * nx_r + (back + tau) * nu + c; };               // tau < 0
-        RollTablesHost t{std::vector<int>(n), std::vector<int>(nx), std::vector<int>(n_r, -1), std::vector<int>(n, 0),
-                         std::vector<int>(nin, -1), std::vector<int>(nx, -1)};
-        auto slot_source = [&](int tau_s, int i) {     // entry i of s_{tau_s}: caller variable or -(1 + data index)
-            if (i < wx) {
-                const int tau = tau_s - i / nx_r, c = i % nx_r;
-                return tau >= 1 ? (tau - 1) * nx_r + c : -(1 + data_x(tau, c));
-            }
-            const int k = (i - wx) / nu, c = (i - wx) % nu, tau = tau_s - 1 - k;
-            return tau >= 0 ? H * nx_r + tau * nu + c : -(1 + data_u(tau, c));
-        };
-        for (int i = 0; i < nx; ++i) t.src0[i] = slot_source(0, i);
-        for (int st = 0; st < H; ++st) {
-            for (int i = 0; i < nx; ++i) {
-                t.src[st * nx + i] = slot_source(st + 1, i);
-                if (i < nx_r) { t.isprim[st * nx + i] = 1; t.prim[st * nx_r + i] = st * nx + i; }
-            }
-            for (int c = 0; c < nu; ++c) {
-                const int k = H * nx + st * nu + c;
-                t.src[k] = H * nx_r + st * nu + c; t.isprim[k] = 1; t.prim[H * nx_r + st * nu + c] = k;
-            }
-        }
-        // window column d of step t (network input order, window_var in nempc_api.hip) -> column of (s_t, u_t)
-        for (int dw = 0; dw < nin_r; ++dw) {
-            int col;
-            if (dw < wx) {
-                const int j = dw / nx_r, c = dw % nx_r;
-                col = (h.rev ? j : back - j) * nx_r + c;                 // x_{t - k}: x-slot k of s_t
-            } else {
-                const int j = (dw - wx) / nu, c = (dw - wx) % nu, k = h.rev ? j : back - j;   // u_{t - k}
-                col = k == 0 ? nx + c : wx + (k - 1) * nu + c;
-            }
-            t.dcol[col] = dw;
-        }
-        // shift rows of s_{t+1}: x-slot k >= 1 copies x-slot k-1 of s_t; u-slot 0 copies u_t, u-slot k copies u-slot k-1
-        for (int i = nx_r; i < nx; ++i) {
-            if (i < wx) t.shift[i] = i - nx_r;
-            else { const int k = (i - wx) / nu, c = (i - wx) % nu; t.shift[i] = k == 0 ? nx + c : wx + (k - 1) * nu + c; }
-        }
-        return t;
-    }
     // a workspace that holds B problems of these dimensions: kept when the handle has one, rebuilt otherwise
     int ensure_workspace() {
-        if (ws.cap >= B && ws.ex_per == ex_per && ws.m == m && ws.n == n && ws.aug == aug) return NEMPC_OK;
+        if (ws.cap >= B && ws.ex_per == ex_per && ws.m == m && ws.n == n && ws.aug.kind == aug.kind) return NEMPC_OK;
         ws.release(); ws = SolverWs();
         SolverWs& w = ws;
         const size_t e = sizeof(T), Bn = (size_t)B;
-        struct Req { void** p; size_t bytes; };
-        std::vector<Req> al = {
+        std::vector<BufReq> al = {
             {&w.Zt, Bn * n * e}, {&w.f, Bn * e}, {&w.ft, Bn * e}, {&w.grad, Bn * n * e}, {&w.g, Bn * m * e},
             {&w.gt, Bn * m * e}, {&w.tiles, Bn * H * nx * nin * e}, {&w.lb, (size_t)n * e}, {&w.ub, (size_t)n * e},
             {&w.alpha, Bn * e}, {&w.phi0, Bn * e},
@@ -325,30 +267,14 @@ struct Solve {
                              {(void**)&w.pend[1], Bn * sizeof(int)},
                              {(void**)&w.n_active, 8 * sizeof(int)},   // [unconverged, still backtracking, blocks done, -, unconverged (odd iterations)]
                              {(void**)&w.perm, Bn * sizeof(int)}, {(void**)&w.count, sizeof(int)}});
-        if (augmented)
-            al.insert(al.end(), {
-                {&w.rZ, Bn * n_r * e}, {&w.rg, Bn * m_r * e}, {&w.rtiles, Bn * H * nx_r * nin_r * e},
-                {&w.rhblk, Bn * H * nin_r * nin_r * e}, {&w.rlam, Bn * m_r * e},
-                {&w.rZin, Bn * n * e}, {&w.rS0, Bn * nx * e}, {&w.rZout, Bn * n * e},
-                {&w.robj, (size_t)obj_offsets(H, nx, nu).total * e}});
-        if (rolling) al.push_back({&w.rgrad, Bn * n_r * e});     // (rate: the gradient comes from the augmented table)
-        for (const Req& x : al) if (int rc = w.alloc(x.p, x.bytes)) return rc;
+        aug.buffers(al);
+        for (const BufReq& x : al) if (int rc = w.alloc(x.p, x.bytes)) return rc;
         NEMPC_HIP(hipMemset(w.n_active, 0, 8 * sizeof(int)));
         if (int rc = w.alloc((void**)&w.hpoll, 4 * sizeof(int), hipHostMallocDefault)) return rc;
         if (int rc = w.alloc((void**)&w.hpub, 8 * sizeof(int), hipHostMallocMapped)) return rc;
         NEMPC_HIP(hipHostGetDevicePointer((void**)&w.hpub_dev, w.hpub, 0));
-        if (augmented) NEMPC_HIP(hipMemsetAsync(w.rlam, 0, Bn * m_r * e, s));     // (box rows of the handle keep zero multipliers)
-        if (rolling) {
-            const RollTablesHost t = build_roll_tables();
-            struct { int** p; const std::vector<int>* v; } tb[] = {{&w.rt.src, &t.src}, {&w.rt.src0, &t.src0}, {&w.rt.prim, &t.prim},
-                                                                   {&w.rt.isprim, &t.isprim}, {&w.rt.dcol, &t.dcol}, {&w.rt.shift, &t.shift}};
-            for (auto& x : tb) {
-                if (int rc = w.alloc((void**)x.p, x.v->size() * sizeof(int))) return rc;
-                NEMPC_HIP(hipMemcpy(*x.p, x.v->data(), x.v->size() * sizeof(int), hipMemcpyHostToDevice));
-            }
-            w.prim_host = t.prim;
-        }
-        w.cap = B; w.m = m; w.n = n; w.ex_per = ex_per; w.aug = aug;
+        if (int rc = aug.upload_tables()) return rc;
+        w.cap = B; w.m = m; w.n = n; w.ex_per = ex_per;
         return NEMPC_OK;
     }
     // bounds -> device (dtype T); +-inf become +-max so that comparisons stay exact.  Box ROWS on the states
@@ -356,26 +282,18 @@ struct Solve {
     // state variables for this solver: intersected here, what controller.py:101-105 of this package does on the host.
     int upload_bounds(const double* lb, const double* ub) {
         const T big = std::numeric_limits<T>::max();
-        std::vector<T> hl(n, -big), hu(n, big);      // (rolling: the copies inside the window state carry no bounds of their own;
-                                                     //  rate: the caller's bounds sit on the s slots, the limits on v)
+        std::vector<T> hl(n, -big), hu(n, big);      // (augmented: a slot that is nobody's carries no bound -- the copies inside a
+                                                     //  window state)
         std::vector<double> blo, bhi;
         if (int rc = intersect_bounds(h, lb, ub, true, "nempc_solve", blo, bhi)) return rc;
-        for (int i = 0; i < n_r; ++i) {
+        aug.append_bounds(blo, bhi);                 // (rate: the limits, behind the caller's bounds)
+        for (size_t i = 0; i < blo.size(); ++i) {
             const double lo = blo[i], hi = bhi[i];
-            const int k = rolling ? ws.prim_host[i] : (rate ? rate_bound_slot(rd, i) : i);
+            const int k = ws.aug.bslot[i];
             hl[k] = std::isfinite(lo) ? (T)lo : -big;
             hu[k] = std::isfinite(hi) ? (T)hi : big;
             has_bounds = has_bounds || std::isfinite(lo) || std::isfinite(hi);
         }
-        if (rate)
-            for (int t = 0; t < H; ++t)
-                for (int j = 0; j < nu; ++j) {
-                    const double lo = h.rate.dlo[(size_t)t * nu + j], hi = h.rate.dhi[(size_t)t * nu + j];
-                    const int k = rate_limit_slot(rd, t, j);
-                    hl[k] = std::isfinite(lo) ? (T)lo : -big;
-                    hu[k] = std::isfinite(hi) ? (T)hi : big;
-                    has_bounds = has_bounds || std::isfinite(lo) || std::isfinite(hi);
-                }
         // per-problem bounds live on the device: whether a problem has a finite bound is decided there, per problem
         // (solver_init_bound_kernel: mu = 0 for one that has none); the host plans for the barrier
         bound_rows = h.bbind.on();
@@ -390,82 +308,6 @@ struct Solve {
             ws.bounds_host.resize(2 * nb);
             memcpy(ws.bounds_host.data(), hl.data(), nb);
             memcpy(ws.bounds_host.data() + nb, hu.data(), nb);
-        }
-        return NEMPC_OK;
-    }
-    // rolling: the objective table over the augmented stage -- the caller's weights on the primary block of s, zeros on the
-    // copies (uploaded when it changes, like the bounds)
-    int upload_roll_objective() {
-        const ObjOffsets ao = obj_offsets(H, nx, nu);
-        const ObjHost& oh = h.obj_host;
-        const std::vector<double>& QT = h.obj_QT.empty() ? oh.Q : h.obj_QT;
-        std::vector<T> tab((size_t)ao.total, T(0));
-        for (int i = 0; i < nx_r; ++i)
-            for (int j = 0; j < nx_r; ++j) {
-                tab[ao.Q + i * nx + j] = (T)oh.Q[i * nx_r + j];
-                tab[ao.Qs + i * nx + j] = (T)(oh.Q[i * nx_r + j] + oh.Q[j * nx_r + i]);
-                tab[ao.QT + i * nx + j] = (T)QT[i * nx_r + j];
-                tab[ao.QTs + i * nx + j] = (T)(QT[i * nx_r + j] + QT[j * nx_r + i]);
-            }
-        for (int i = 0; i < nu; ++i)
-            for (int j = 0; j < nu; ++j) {
-                tab[ao.R + i * nu + j] = (T)oh.R[i * nu + j];
-                tab[ao.Rs + i * nu + j] = (T)(oh.R[i * nu + j] + oh.R[j * nu + i]);
-            }
-        for (int t = 0; t < H; ++t) {
-            for (int i = 0; i < nx_r; ++i) {
-                tab[ao.xref + t * nx + i] = (T)oh.xref[t * nx_r + i];
-                tab[ao.cx + t * nx + i] = (T)oh.cx[t * nx_r + i];
-            }
-            for (int i = 0; i < nu; ++i) {
-                tab[ao.uref + t * nu + i] = (T)oh.uref[t * nu + i];
-                tab[ao.cu + t * nu + i] = (T)oh.cu[t * nu + i];
-            }
-        }
-        return upload_aug_table(tab);
-    }
-    // rate: Q_aug = blkdiag(Q, R), QT_aug = blkdiag(QT, R) and [xref ; uref], [cx ; cu] on s = [x ; u]; R_aug = S and zero
-    // reference / linear cost on the control move v
-    int upload_rate_objective() {
-        const ObjOffsets ao = obj_offsets(H, nx, nu);
-        const ObjHost& oh = h.obj_host;
-        const std::vector<double>& QT = h.obj_QT.empty() ? oh.Q : h.obj_QT;
-        const std::vector<double>& S = h.rate.S;
-        std::vector<T> tab((size_t)ao.total, T(0));
-        for (int i = 0; i < nx_r; ++i)
-            for (int j = 0; j < nx_r; ++j) {
-                tab[ao.Q + i * nx + j] = (T)oh.Q[i * nx_r + j];
-                tab[ao.Qs + i * nx + j] = (T)(oh.Q[i * nx_r + j] + oh.Q[j * nx_r + i]);
-                tab[ao.QT + i * nx + j] = (T)QT[i * nx_r + j];
-                tab[ao.QTs + i * nx + j] = (T)(QT[i * nx_r + j] + QT[j * nx_r + i]);
-            }
-        for (int i = 0; i < nu; ++i)
-            for (int j = 0; j < nu; ++j) {
-                const int e = (nx_r + i) * nx + nx_r + j;
-                tab[ao.Q + e] = tab[ao.QT + e] = (T)oh.R[i * nu + j];
-                tab[ao.Qs + e] = tab[ao.QTs + e] = (T)(oh.R[i * nu + j] + oh.R[j * nu + i]);
-                tab[ao.R + i * nu + j] = (T)S[i * nu + j];
-                tab[ao.Rs + i * nu + j] = (T)(S[i * nu + j] + S[j * nu + i]);
-            }
-        for (int t = 0; t < H; ++t) {
-            for (int i = 0; i < nx_r; ++i) {
-                tab[ao.xref + t * nx + i] = (T)oh.xref[t * nx_r + i];
-                tab[ao.cx + t * nx + i] = (T)oh.cx[t * nx_r + i];
-            }
-            for (int i = 0; i < nu; ++i) {
-                tab[ao.xref + t * nx + nx_r + i] = (T)oh.uref[t * nu + i];
-                tab[ao.cx + t * nx + nx_r + i] = (T)oh.cu[t * nu + i];
-            }
-        }
-        return upload_aug_table(tab);
-    }
-    // (uploaded when it changes, like the bounds)
-    int upload_aug_table(const std::vector<T>& tab) {
-        const size_t tb = tab.size() * sizeof(T);
-        if (ws.robj_host.size() != tb || memcmp(ws.robj_host.data(), tab.data(), tb) != 0) {
-            NEMPC_HIP(hipMemcpyAsync(ws.robj, tab.data(), tb, hipMemcpyHostToDevice, s));
-            NEMPC_HIP(hipStreamSynchronize(s));   // tab is stack-owned
-            ws.robj_host.assign((const unsigned char*)tab.data(), (const unsigned char*)tab.data() + tb);
         }
         return NEMPC_OK;
     }
@@ -547,23 +389,10 @@ struct Solve {
             h.extra_B = B;
         }
         const void *Zstart = Z, *X0start = X0, *obj_dev = h.d_obj;
-        if (rolling) {
-            // the window state's start (augmented guess, s_0) and the objective table over the augmented stage
-            hipLaunchKernelGGL(roll_build_kernel<T>, dim3(gBn), dim3(256), 0, s, B, n, nx, n_r, nx_r, nu, back, ws.rt, (const T*)Z,
-                               (const T*)X0, (const T*)h.d_hist_x, (const T*)h.d_hist_u, (const T*)ws.lb, (const T*)ws.ub,
-                               (T)o.mu_init, has_bounds ? 1 : 0, (T*)ws.rZin, (T*)ws.rS0);
-            Zstart = ws.rZin; X0start = ws.rS0;
-            if ((rc = upload_roll_objective())) return rc;
-            obj_dev = ws.robj;
-        }
-        if (rate) {
-            // the same for the rate state: augmented guess, s_{-1} = [x0 ; u_prev], the table with S on the control move
-            hipLaunchKernelGGL(rate_build_kernel<T>, dim3(gBn), dim3(256), 0, s, B, rd, (const T*)Z, (const T*)X0,
-                               (const T*)h.rate.u_prev, (const T*)ws.lb, (const T*)ws.ub, (T)o.mu_init, has_bounds ? 1 : 0,
-                               (T*)ws.rZin, (T*)ws.rS0);
-            Zstart = ws.rZin; X0start = ws.rS0;
-            if ((rc = upload_rate_objective())) return rc;
-            obj_dev = ws.robj;
+        if (augmented) {
+            if ((rc = aug.start(Z, X0, ws.lb, ws.ub, (T)o.mu_init, has_bounds ? 1 : 0, gBn))) return rc;
+            Zstart = ws.aug.rZin; X0start = ws.aug.rS0; obj_dev = ws.aug.robj;
+            aug.f = ws.f; aug.g = ws.g; aug.gt = ws.gt; aug.tiles = ws.tiles; aug.hblk = ws.hblk; aug.grad = ws.grad;
         }
         if (bound_rows && !ws.lbw) {     // (a rebuilt workspace starts without them; sized like its other buffers)
             const size_t nb = (size_t)ws.cap * n * sizeof(T);
@@ -624,15 +453,12 @@ struct Solve {
         compact = o.compact != 0 && !trace && !augmented;
         return NEMPC_OK;
     }
-    // ---- callbacks.  Plain models: the handle's launches on the solver's buffers.  Rolling: gather the caller's
-    //      variables, launch on them, spread the results into the window-state form (RollTables)
+    // ---- callbacks.  Plain models: the handle's launches on the solver's buffers (augmented: StageAug::eval)
     int launch_rows(int nb, const void* Zs, const void* X0s, void* g, void* tiles, void* tiles_scratch) {
-        if (h.variant != NEMPC_KERNEL_VALU) return launch_rows_mfma(h, nb, Zs, X0s, fused_eval_out(g, tiles, nullptr, nullptr), s);
-        return launch_rows_valu(h, nb, Zs, X0s, g, tiles ? tiles : tiles_scratch, s);
+        return callback_rows(h, nb, Zs, X0s, g, tiles, tiles_scratch, s);
     }
     int launch_blocks(int nb, const void* Zs, const void* X0s, const void* lam, void* blocks) {
-        if (h.variant != NEMPC_KERNEL_VALU) return launch_rowhess_mfma(h, nb, Zs, X0s, lam, blocks_eval_out(blocks, nullptr, nullptr), s);
-        return launch_rowhess_valu(h, nb, Zs, X0s, lam, blocks, s);
+        return callback_blocks(h, nb, Zs, X0s, lam, blocks, s);
     }
     // The launches a compiled shape has, asked of the plan (mfma_plan.h) at the call's batch size (several gates depend on it):
     // blocks + defects + tiles from one launch of the Hessian kernel ...
@@ -644,39 +470,6 @@ struct Solve {
     RowsOut fused_eval_out(void* g, void* tiles, void* f, void* grad) const { RowsOut ro; ro.g = g; ro.tiles = tiles; ro.f = f; ro.grad = grad; return ro; }
     bool has_fused_eval(int nb, const RowsOut& ro) const {
         return h.variant != NEMPC_KERNEL_VALU && h.mfma.blob && (mfma_plan_rows(h, nb, ro).covers & COVERS_OBJ);
-    }
-    // everything at an iterate: defects, tiles, f, gradient, Lagrangian blocks (into the iterate's buffers); a trial point
-    // (lam_aug = null): defects only, into gt (the acceptance kernel evaluates the objective from the augmented table itself)
-    int roll_eval(const void* Zaug, const void* lam_aug) {
-        const bool full = lam_aug != nullptr;
-        hipLaunchKernelGGL(roll_in_kernel<T>, dim3(gRn), dim3(256), 0, s, B, n, n_r, H, nx_r, nx, m_r, ws.rt, (const T*)Zaug,
-                           (T*)ws.rZ, (const T*)lam_aug, full ? (T*)ws.rlam : (T*)nullptr);
-        int r = launch_rows(B, ws.rZ, X0, ws.rg, full ? ws.rtiles : nullptr, h.d_tiles_ws);
-        if (r) return r;
-        if (full && ((r = launch_blocks(B, ws.rZ, X0, ws.rlam, ws.rhblk)) || (r = launch_objective(h, B, ws.rZ, ws.f, ws.rgrad, s))))
-            return r;
-        hipLaunchKernelGGL(roll_out_kernel<T>, dim3(B * H), dim3(256), 0, s, H, nx_r, nu, nx, nin_r, n_r, m_r, ws.rt,
-                           (const T*)Zaug, (const T*)ws.rS0, (const T*)ws.rg, full ? (const T*)ws.rtiles : (const T*)nullptr,
-                           full ? (const T*)ws.rhblk : (const T*)nullptr, full ? (const T*)ws.rgrad : (const T*)nullptr,
-                           full ? (T*)ws.g : (T*)ws.gt, full ? (T*)ws.tiles : (T*)nullptr, full ? (T*)ws.hblk : (T*)nullptr,
-                           full ? (T*)ws.grad : (T*)nullptr);
-        return NEMPC_OK;
-    }
-    // the same for a rate binding (solver_rate_impl.h): the network at x_t, u_{t-1} + v_t; f and the gradient from the
-    // augmented table inside the spread kernel (no objective launch on the caller's variables)
-    int rate_eval(const void* Zaug, const void* lam_aug) {
-        const bool full = lam_aug != nullptr;
-        hipLaunchKernelGGL(rate_gather_kernel<T>, dim3(gRn), dim3(256), 0, s, B, rd, m_r, 0, (const T*)Zaug, (const T*)ws.rS0,
-                           (T*)ws.rZ, (const T*)lam_aug, full ? (T*)ws.rlam : (T*)nullptr);
-        int r = launch_rows(B, ws.rZ, X0, ws.rg, full ? ws.rtiles : nullptr, h.d_tiles_ws);
-        if (r) return r;
-        if (full && (r = launch_blocks(B, ws.rZ, X0, ws.rlam, ws.rhblk))) return r;
-        hipLaunchKernelGGL(rate_spread_kernel<T>, dim3(B * H), dim3(256), 0, s, rd, m_r, (const T*)Zaug, (const T*)ws.rS0,
-                           (const T*)ws.rg, full ? (const T*)ws.rtiles : (const T*)nullptr,
-                           full ? (const T*)ws.rhblk : (const T*)nullptr, (const T*)ws.robj, obj_offsets(H, nx, nu),
-                           full ? (T*)ws.g : (T*)ws.gt, full ? (T*)ws.tiles : (T*)nullptr, full ? (T*)ws.hblk : (T*)nullptr,
-                           full ? (T*)ws.grad : (T*)nullptr, full ? (T*)ws.f : (T*)nullptr);
-        return NEMPC_OK;
     }
     // (A block-wise mirrored convexification of the stage Hessians, for the problems whose sweep needed damping, was built and
     // measured in round 4 -- profiles/r04_solver_convexify_c3.txt: +3 - 5 % problems converged at 1.5 ms per iteration; removed
@@ -692,7 +485,7 @@ struct Solve {
         int rc;
         if (augmented) {
             fused_eval = true;                  // (f and grad come with it)
-            rc = rolling ? roll_eval(Zc, lam) : rate_eval(Zc, lam);
+            rc = aug.eval(Zc, lam);
         } else if (have_eval) {
             // deferred backtracking on a compiled shape: the trial evaluation of the last iteration was a full one and the
             // acceptance kernel kept, per problem, the evaluation of the point it stands on -- only the blocks are new, and
@@ -796,7 +589,7 @@ struct Solve {
     // 24.9 ms), in the wide phase because a trial evaluation costs real time and among the stragglers because each
     // extra trial is a latency-bound launch chain plus a host poll.  It spends more ITERATIONS on a hard problem
     // (a retry is an iteration), so max_iter budgets are larger than with the inner loop.
-    // (rolling: one trial per iteration whatever was asked for -- the dense trial lists of the inner loop would need the
+    // (augmented: one trial per iteration whatever was asked for -- the dense trial lists of the inner loop would need the
     //  callbacks' x0 / history gathered per list)
     int line_search() {
         void* Zc = ws.Zc[cur];
@@ -844,7 +637,7 @@ struct Solve {
             }
             if (trial_done) {
             } else if (augmented) {
-                rc = rolling ? roll_eval(ws.Zt, nullptr) : rate_eval(ws.Zt, nullptr);
+                rc = aug.eval(ws.Zt, nullptr);
             } else {
                 if (!fused_trial) {
                     const RowsOut ro = fused_eval_out(ws.gt, nullptr, ws.ft, nullptr);
@@ -1014,13 +807,8 @@ struct Solve {
         if (accept_pending) accept_now();           // (the loop was left with a trial point evaluated and not yet tested)
         hipLaunchKernelGGL(solver_scatter_kernel<T>, dim3(B), dim3(256), 0, s, B, n, (const T*)ws.Zc[cur],
                            (const int*)ws.stc[cur], (const int*)ws.orig[cur], (const int*)ws.itc[cur],
-                           augmented ? (T*)ws.rZout : (T*)Z, status_dev, (int*)o.iters_out);
-        if (rolling)      // the caller's variables are the primary copies
-            hipLaunchKernelGGL(roll_in_kernel<T>, dim3(gRn), dim3(256), 0, s, B, n, n_r, H, nx_r, nx, m_r, ws.rt, (const T*)ws.rZout,
-                               (T*)Z, (const T*)nullptr, (T*)nullptr);
-        if (rate)         // ... or, under a rate binding, the x and u slots of the state
-            hipLaunchKernelGGL(rate_gather_kernel<T>, dim3(gRn), dim3(256), 0, s, B, rd, m_r, 1, (const T*)ws.rZout, (const T*)ws.rS0,
-                               (T*)Z, (const T*)nullptr, (T*)nullptr);
+                           (T*)aug.solution_buffer(Z), status_dev, (int*)o.iters_out);
+        aug.hand_back(Z);     // (augmented: the caller's variables out of the augmented solution)
         if (duals.any())  // (plain models only, solver_run: n, m are the caller's)
             hipLaunchKernelGGL(solver_scatter_duals_kernel<T>, dim3(B), dim3(256), 0, s, B, n, m, H * nx, (const T*)ws.Zc[cur],
                                (const T*)ws.lamc[cur], (const T*)ws.zlc[cur], (const T*)ws.zuc[cur], (const T*)ws.muc[cur],

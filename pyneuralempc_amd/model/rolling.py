@@ -6,7 +6,7 @@ The network of step t reads the last ``rolling_window`` states and controls
 (oldest first, or newest first with ``forward_rolling=False``), the history ``prev_x / prev_u`` being supplied with
 ``set_prev_data`` before each solve.  The reference differentiates through that gather with TF / JAX and projection
 matrices; here the gather is part of the row kernels' input staging and the band structure of the Jacobian / Hessian is
-built once on the host (csrc/nempc_api.hip window_var)."""
+built once on the host (csrc/stage_aug.h window_var)."""
 import numpy as np
 import torch
 
