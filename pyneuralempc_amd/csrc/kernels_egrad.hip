@@ -239,7 +239,7 @@ int launch_form(Handle& h, const EgradPlan& p, const EgNet& net, long long rows,
     auto kern = egrad_rows_kernel<T, LANES, SECOND, SAVE_WS>;
     if (p.lds_bytes > 65536) NEMPC_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), p.lds_bytes));
     hipLaunchKernelGGL(kern, dim3((unsigned)egrad_grid(p, rows)), dim3(64), p.lds_bytes, s, net, (T)h.cfg.DT, h.cfg.H, rows, p.maxdim,
-                       p.stride, p.save_elems, (const T*)Z, (const T*)X0, (const T*)lam, (const T*)v, (const T*)w, (T*)h.d_egrad_ws,
+                       p.stride, p.save_elems, (const T*)Z, (const T*)X0, (const T*)lam, (const T*)v, (const T*)w, h.d_egrad_ws.as<T>(),
                        (T*)gE);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
@@ -274,24 +274,13 @@ int launch_extra_grad(Handle& h, int B, const void* Z, const void* X0, const voi
         return NEMPC_EUNSUPPORTED;
     }
     const size_t bytes = (size_t)egrad_ws_elems(p, (long long)h.cfg.max_batch * h.cfg.H) * h.esz;
-    if (bytes > h.egrad_ws_bytes) {
-        NEMPC_HIP(hipDeviceSynchronize());
-        dev_free(h.d_egrad_ws);
-        h.egrad_ws_bytes = 0;
-        hipError_t e = hipMalloc(&h.d_egrad_ws, bytes);
-        if (e != hipSuccess) {
-            h.d_egrad_ws = nullptr;
-            set_error(std::string("hipMalloc (nempc_extra_grad workspace): ") + hipGetErrorString(e));
-            return NEMPC_ENOMEM;
-        }
-        h.egrad_ws_bytes = bytes;
-    }
+    if (int rc = h.d_egrad_ws.ensure(bytes, "nempc_extra_grad workspace")) return rc;
     EgNet net{};
     net.nl = h.nl; net.nin = h.nin; net.nx = h.cfg.nx; net.ne = h.ne; net.nstage = h.cfg.integrator == NEMPC_RK4 ? 4 : 1; net.m = h.m;
     net.extra = h.d_extra; net.gk = h.gather();
     for (int l = 0; l < h.nl; ++l) {
         net.din[l] = h.din[l]; net.dout[l] = h.dout[l]; net.act[l] = h.act[l]; net.actp[l] = h.actp[l];
-        net.W[l] = h.d_W[l]; net.Wt[l] = h.d_Wt[l]; net.b[l] = h.d_b[l];
+        net.W[l] = h.d_W[l].get(); net.Wt[l] = h.d_Wt[l].get(); net.b[l] = h.d_b[l].get();
         net.soff[l] = net.souts; net.souts += h.dout[l];
     }
     const long long rows = (long long)B * h.cfg.H;
@@ -299,11 +288,6 @@ int launch_extra_grad(Handle& h, int B, const void* Z, const void* X0, const voi
                                             : run<float>(h, p, net, rows, Z, X0, lam, v, w, gE, s);
     if (rc == NEMPC_OK) h.last_egrad_kernel = p.code;
     return rc;
-}
-
-void egrad_free(Handle& h) {
-    dev_free(h.d_egrad_ws);
-    h.egrad_ws_bytes = 0;
 }
 
 }  // namespace nempc

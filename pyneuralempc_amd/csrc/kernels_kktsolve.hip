@@ -156,29 +156,18 @@ int launch_kkt_solve(Handle& h, int B, const void* Z, const void* tiles, const v
     const size_t Bm = (size_t)h.cfg.max_batch, H = (size_t)h.cfg.H, nx = (size_t)h.cfg.nx, nu = (size_t)h.cfg.nu;
     // the plan's global region: allocated on the first call that needs one, grown (never shrunk) with nrhs and max_batch
     const size_t need = kktsolve_ws_doubles(h, Bm, nrhs);
-    if (need > h.kktsolve_ws_doubles) {
-        NEMPC_HIP(hipDeviceSynchronize());      // an earlier call may still run out of the old region on some stream
-        dev_free(h.d_kktsolve_ws);
-        h.kktsolve_ws_doubles = 0;
-        const hipError_t e = hipMalloc((void**)&h.d_kktsolve_ws, need * sizeof(double));
-        if (e != hipSuccess) {
-            h.d_kktsolve_ws = nullptr;
-            set_error(std::string("hipMalloc (nempc_kkt_solve workspace): ") + hipGetErrorString(e));
-            return NEMPC_ENOMEM;
-        }
-        h.kktsolve_ws_doubles = need;
-    }
+    if (int rc = h.d_kktsolve_ws.ensure(need * sizeof(double), "nempc_kkt_solve workspace")) return rc;
     KktSolveArgs a;
     a.B = B; a.H = h.cfg.H; a.nx = h.cfg.nx; a.nu = h.cfg.nu; a.nrhs = nrhs; a.ppw = p.ppw; a.use_lds = p.use_lds ? 1 : 0;
     a.staged = p.staged ? 1 : 0;
     a.stride = p.stride; a.aff = p.aff; a.base = p.base; a.per_problem = p.per_problem;
-    a.Z = Z; a.tiles = tiles; a.blocks = blocks; a.zl = zl; a.zu = zu; a.obj = h.d_obj; a.rz = rz; a.rg = rg;
+    a.Z = Z; a.tiles = tiles; a.blocks = blocks; a.zl = zl; a.zu = zu; a.obj = h.d_obj.get(); a.rz = rz; a.rg = rg;
     a.oo = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     a.lb = lb; a.ub = ub; a.bb = h.bbind;
-    a.Kst = h.d_sens_ws;
+    a.Kst = h.d_sens_ws.as<double>();
     a.Pst = a.Kst + Bm * H * nu * nx;
     a.sig = a.Pst + Bm * H * nx * nx;
-    a.scratch = h.d_kktsolve_ws;
+    a.scratch = h.d_kktsolve_ws.as<double>();
     a.v = v; a.w = w; a.gx0 = gx0; a.status = status;
     const size_t lds = p.use_lds ? (size_t)p.ppw * p.per_problem : 0;
     const dim3 grid((unsigned)((B + p.ppw - 1) / p.ppw)), block((unsigned)(64 * p.ppw));
@@ -191,11 +180,6 @@ int launch_kkt_solve(Handle& h, int B, const void* Z, const void* tiles, const v
     }
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
-}
-
-void kktsolve_free(Handle& h) {
-    dev_free(h.d_kktsolve_ws);
-    h.kktsolve_ws_doubles = 0;
 }
 
 }  // namespace nempc

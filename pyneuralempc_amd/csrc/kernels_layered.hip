@@ -59,7 +59,7 @@ GemmArgs forward_product(const Handle& h, int l, const void* in, int R, long lon
     GemmArgs a{};
     a.mode = LG_FORWARD; a.act = h.act[l]; a.actp = h.actp[l];
     a.A = in; a.lda = Rp; a.ldd = Rp;
-    a.Bw = h.d_W[l]; a.ldb = h.dout[l]; a.bias = h.d_b[l];
+    a.Bw = h.d_W[l].get(); a.ldb = h.dout[l]; a.bias = h.d_b[l].get();
     a.M = R; a.N = h.dout[l]; a.K = h.din[l];
     return a;
 }
@@ -140,7 +140,7 @@ struct Sweep {
             T* const E = p.dfa[l] || !e ? nullptr : at(e[l]);
             if (l == 0 && p.first) {
                 LG_TRY(launch_first<T>(h.act[0], nin + ne, dim3((unsigned)((R + 63) / 64), (unsigned)lg_fblocks(h.dout[0])), s, gk, nin, ne,
-                                       typed(h.d_extra), Z, X0, r0, R, Rp, typed(h.d_W[0]), h.dout[0], typed(h.d_b[0]), h.act[0],
+                                       typed(h.d_extra), Z, X0, r0, R, Rp, typed(h.d_W[0].get()), h.dout[0], typed(h.d_b[0].get()), h.act[0],
                                        (T)h.actp[0], out, D, E));
                 in = out;
                 continue;
@@ -150,18 +150,18 @@ struct Sweep {
                 // the last hidden layer: its activations go straight into the output layer's contraction (only s' -- or, dfa,
                 // the activation itself, through the D slot -- is stored); partial sums per feature block
                 a.D = at(o.d[l]); a.E = E; a.store_a = p.dfa[l] ? 1 : 0;
-                contract_into(a, h.d_W[nl - 1], nx, nx, at(sums->region), Rp, (long long)nx * Rp);
+                contract_into(a, h.d_W[nl - 1].get(), nx, nx, at(sums->region), Rp, (long long)nx * Rp);
                 LG_TRY((gemm_forward<T, LG_CONTRACT_FORWARD>(h.num_cus, s, a)));
                 if (!out_step) return NEMPC_OK;
                 return launch(layered_outfinish_kernel<T>, rg, rb, at(sums->region), lg_fblocks(h.dout[l]), a.jp_stride, nx, R, Rp,
-                              h.d_b[nl - 1], h.act[nl - 1], h.actp[nl - 1], at(o.f), at(o.dl), elp);
+                              h.d_b[nl - 1].get(), h.act[nl - 1], h.actp[nl - 1], at(o.f), at(o.dl), elp);
             }
             a.C = out; a.ldc = Rp; a.D = D; a.E = E;
             LG_TRY((gemm_forward<T, LG_CONTRACT_NONE>(h.num_cus, s, a)));
             in = out;
         }
         if (!out_step) return NEMPC_OK;
-        return skinny<T>(s, in, Rp, typed(h.d_W[nl - 1]), nx, h.din[nl - 1], nx, (long long)R, at(o.f), Rp, typed(h.d_b[nl - 1]), 0,
+        return skinny<T>(s, in, Rp, typed(h.d_W[nl - 1].get()), nx, h.din[nl - 1], nx, (long long)R, at(o.f), Rp, typed(h.d_b[nl - 1].get()), 0,
                          h.act[nl - 1], at(o.dl), (T)h.actp[nl - 1], elp);
     }
 
@@ -179,11 +179,11 @@ struct Sweep {
         T* const Jp = p.jac_sums.used() ? at(p.jac_sums.region) : at(o.j);
         for (int l = nl - 3; l >= 0; --l) {
             const bool seed = l == nl - 3, last = l == 0, even = (nl - 3 - l) % 2 == 0;     // products nl-3 .. 0 write g0, g1, g0, ...
-            GemmArgs a = reverse_product(h.d_Wt[l + 1], h.dout[l], h.dout[l + 1], ldg, Rp);
+            GemmArgs a = reverse_product(h.d_Wt[l + 1].get(), h.dout[l], h.dout[l + 1], ldg, Rp);
             derivs_from(a, h, l, p.dfa[l], at(o.d[l]), Rp);
-            if (seed) seed_from(a, h, nl - 2, p.dfa[nl - 2], at(o.d[nl - 2]), Rp, h.d_W[nl - 1], nx, p.lin_skip ? nullptr : at(o.dl));
+            if (seed) seed_from(a, h, nl - 2, p.dfa[nl - 2], at(o.d[nl - 2]), Rp, h.d_W[nl - 1].get(), nx, p.lin_skip ? nullptr : at(o.dl));
             else { a.A = at(even ? o.g1 : o.g0); a.lda = ldg; }
-            if (last) contract_into(a, h.d_Wt[0], h.din[0], nin, Jp, ldg, (long long)nin * ldg);
+            if (last) contract_into(a, h.d_Wt[0].get(), h.din[0], nin, Jp, ldg, (long long)nin * ldg);
             else { a.C = at(even ? o.g0 : o.g1); a.ldc = ldg; }
             LG_TRY(gemm_reverse_fused<T>(s, a, seed, last));
         }
@@ -196,13 +196,13 @@ struct Sweep {
     int rows_reverse_plain() const {
         const long long ldg = (long long)nx * Rp;
         T* G = at(o.g0);
-        LG_TRY(launch(layered_seed_kernel<T>, dim3(rg.x, (unsigned)h.dout[nl - 2]), rb, h.d_W[nl - 1], h.dout[nl - 2], nx, at(o.dl),
+        LG_TRY(launch(layered_seed_kernel<T>, dim3(rg.x, (unsigned)h.dout[nl - 2]), rb, h.d_W[nl - 1].get(), h.dout[nl - 2], nx, at(o.dl),
                       at(o.d[nl - 2]), R, Rp, G, p.dfa[nl - 2] ? h.act[nl - 2] : 0, h.actp[nl - 2]));
         for (int l = nl - 3; l >= 0; --l) {
             // G_l = (W_{l+1} G_{l+1}) . D_l : K = dout[l+1], N = dout[l], operand W_{l+1}^T row-major (out, in) = d_Wt[l+1]
             // the nx blocks of Rp columns are covered as one run of columns
             T* Gn = (G == at(o.g0)) ? at(o.g1) : at(o.g0);
-            GemmArgs a = reverse_product(h.d_Wt[l + 1], h.dout[l], h.dout[l + 1], ldg, Rp);
+            GemmArgs a = reverse_product(h.d_Wt[l + 1].get(), h.dout[l], h.dout[l + 1], ldg, Rp);
             a.A = G; a.lda = ldg; a.C = Gn; a.ldc = ldg;
             derivs_from(a, h, l, p.dfa[l], at(o.d[l]), Rp);
             a.dactp = h.actp[l];        // (passed whether or not dact is set; read only with it)
@@ -210,7 +210,7 @@ struct Sweep {
             G = Gn;
         }
         // J^T[d][k Rp + r] = sum_o W_0[d][o] G_0[o][.]: operand W_0^T (out, in) = d_Wt[0], only the nin decision inputs
-        return skinny<T>(s, G, ldg, typed(h.d_Wt[0]), h.din[0], h.dout[0], nin, (long long)(nx - 1) * Rp + R, at(o.j), ldg, nullptr, 2, 0,
+        return skinny<T>(s, G, ldg, typed(h.d_Wt[0].get()), h.din[0], h.dout[0], nin, (long long)(nx - 1) * Rp + R, at(o.j), ldg, nullptr, 2, 0,
                          nullptr, T(0));
     }
     // RK4: the stage's record for the Hessian pipeline (when asked for), then k_s, dk_s and the weighted sums
@@ -238,7 +238,7 @@ struct Sweep {
         return launch(layered_finish_kernel<T>, dim3(rg.x, (unsigned)nx), rb, gk, h.cfg.integrator, h.cfg.DT, nin, Z, X0, r0, R, Rp,
                       fsums ? at(p.out_sums.region) : at(o.f), jsums ? at(p.jac_sums.region) : at(o.j), p.rk4 ? at(o.acck) : nullptr,
                       p.rk4 ? at(o.accdk) : nullptr, g, h.m, h.box ? 1 : 0, tiles, jsums ? lg_fblocks(h.dout[0]) : 1, jstride,
-                      fsums ? lg_fblocks(h.dout[nl - 2]) : 0, fstride, h.d_b[nl - 1]);
+                      fsums ? lg_fblocks(h.dout[nl - 2]) : 0, fstride, h.d_b[nl - 1].get());
     }
 
     // reverse with the multipliers as the one cotangent: curvature weights w_l of every hidden layer -- and, fuse_l0, layer 0's
@@ -248,11 +248,11 @@ struct Sweep {
         LG_TRY(launch(layered_hmult_kernel<T>, rg, rb, h.cfg.H, nx, h.m, lam, direct ? 1 : 0, r0, R, Rp, at(o.dl), h.act[nl - 1], at(o.cl),
                       at(o.wl)));
         T* dq = at(o.q0);
-        LG_TRY(launch(layered_hseed_kernel<T>, dim3(rg.x, (unsigned)h.dout[nl - 2]), rb, h.d_W[nl - 1], h.dout[nl - 2], nx, at(o.cl),
+        LG_TRY(launch(layered_hseed_kernel<T>, dim3(rg.x, (unsigned)h.dout[nl - 2]), rb, h.d_W[nl - 1].get(), h.dout[nl - 2], nx, at(o.cl),
                       at(o.d[nl - 2]), E(nl - 2), R, Rp, dq, at(o.cw[nl - 2]), p.dfa[nl - 2] ? h.act[nl - 2] : 0, h.actp[nl - 2]));
         for (int l = nl - 3; l >= 0; --l) {
             T* dn = (dq == at(o.q0)) ? at(o.q1) : at(o.q0);
-            GemmArgs a = reverse_product(h.d_Wt[l + 1], h.dout[l], h.dout[l + 1], Rp, Rp);
+            GemmArgs a = reverse_product(h.d_Wt[l + 1].get(), h.dout[l], h.dout[l + 1], Rp, Rp);
             a.A = dq; a.lda = Rp;
             derivs_from(a, h, l, p.dfa[l], at(o.d[l]), Rp);
             a.E = E(l);
@@ -260,7 +260,7 @@ struct Sweep {
                 // w_0 = q_0 . E_0 contracted with the pair products
                 a.D = E(0);
                 a.duse = 1;
-                contract_into(a, h.d_layered_pairs, p.npair, p.npair, at(p.l0p_stack.region), Rp, (long long)p.npair * Rp);
+                contract_into(a, h.d_layered_pairs.get(), p.npair, p.npair, at(p.l0p_stack.region), Rp, (long long)p.npair * Rp);
                 return gemm_ft<T, 1, false, LG_CONTRACT_REVERSE>(s, a);
             }
             a.C = l > 0 ? dn : nullptr; a.C2 = at(o.cw[l]); a.ldc = Rp;
@@ -278,10 +278,10 @@ struct Sweep {
         for (int l = 1; l < nl - 1; ++l) {
             T* tn = (ta == at(o.a0)) ? at(o.a1) : at(o.a0);
             const bool need_a = l < nl - 2 || !p.lin_out;     // D_l . P_l feeds the next layer (or the output layer's curvature)
-            GemmArgs a = reverse_product(h.d_W[l], h.dout[l], h.din[l], Mt, p.fold ? (long long)R : Rp);
+            GemmArgs a = reverse_product(h.d_W[l].get(), h.dout[l], h.din[l], Mt, p.fold ? (long long)R : Rp);
             derivs_from(a, h, l, p.dfa[l], at(o.d[l]), Rp);
             a.C = need_a ? tn : nullptr; a.Craw = p.fold ? nullptr : at(o.P); a.ldc = ldt;
-            if (l == 1) seed_from(a, h, 0, p.dfa[0], at(o.d[0]), Rp, h.d_Wt[0], h.din[0], nullptr);     // P_0 = W_0^T, constant
+            if (l == 1) seed_from(a, h, 0, p.dfa[0], at(o.d[0]), Rp, h.d_Wt[0].get(), h.din[0], nullptr);     // P_0 = W_0^T, constant
             else { a.A = ta; a.lda = ldt; }
             if (p.fold) {
                 // (LG_CONTRACT_HPAIR: the weights w_l with the stride of D, as many inputs as the tile has)
@@ -305,14 +305,14 @@ struct Sweep {
         LG_TRY(forward(o.e, p.contract_out ? &p.out_sums : nullptr, !p.lin_noout, &o.wl));
         LG_TRY(hess_cotangents(lam, stage != nullptr));
         // layer 0: constant tangents W_0^T
-        if (!p.fuse_l0) LG_TRY(hcontract<T>(s, nullptr, 0, typed(h.d_W[0]), h.dout[0], at(o.cw[0]), h.dout[0], nin, R, Rp, Hacc, false));
+        if (!p.fuse_l0) LG_TRY(hcontract<T>(s, nullptr, 0, typed(h.d_W[0].get()), h.dout[0], at(o.cw[0]), h.dout[0], nin, R, Rp, Hacc, false));
         const long long ldt = p.fold ? ((long long)R + 15) / 16 * 16 * nin : (long long)nin * Rp;
         const T* ta = nullptr;
         bool hacc_used = !p.fuse_l0;
         LG_TRY(hess_tangents(ldt, ta, hacc_used));
         if (!p.lin_out) {
             // the output layer's own curvature: P_L = W_L^T (D_{L-2} . P_{L-2}), weights mult . s_L''
-            LG_TRY(skinny<T>(s, ta, ldt, typed(h.d_W[nl - 1]), nx, h.din[nl - 1], nx, (long long)(nin - 1) * Rp + R, at(o.pl), ldt, nullptr,
+            LG_TRY(skinny<T>(s, ta, ldt, typed(h.d_W[nl - 1].get()), nx, h.din[nl - 1], nx, (long long)(nin - 1) * Rp + R, at(o.pl), ldt, nullptr,
                              2, 0, nullptr, T(0)));
             LG_TRY(hcontract<T>(s, at(o.pl), ldt, nullptr, 0, at(o.wl), nx, nin, R, Rp, Hacc, hacc_used));
             hacc_used = true;
@@ -327,7 +327,7 @@ int run_layered(Handle& h, int B, const void* Z, const void* X0, void* g, void* 
                 int stage_stride = 0) {
     const RowsPlan p = plan_rows(layered_net(h), layered_knobs());
     LG_TRY(check_loans({&p.out_sums, &p.jac_sums}));
-    Sweep<T, RowsPlan> c{h, p, static_cast<T*>(h.d_layered_ws), s, static_cast<const T*>(Z), static_cast<const T*>(X0)};
+    Sweep<T, RowsPlan> c{h, p, h.d_layered_ws.as<T>(), s, static_cast<const T*>(Z), static_cast<const T*>(X0)};
     while (c.next_chunk((long long)B * h.cfg.H, h.layered_chunk_rows)) {
         for (int st = 0; st < (p.rk4 ? 4 : 1); ++st) {
             const T DT = (T)h.cfg.DT, cdt = st == 0 ? T(0) : (st == 3 ? DT : T(0.5) * DT);
@@ -364,10 +364,10 @@ int run_layered_hess(Handle& h, int B, const void* Z, const void* X0, const void
                      const void* stage = nullptr, int stage_stride = 0, long long nrows = 0) {
     const HessPlan p = plan_hess(layered_net(h), layered_knobs(), stage != nullptr);
     LG_TRY(check_loans({&p.out_sums, &p.l0p_stack}));
-    Sweep<T, HessPlan> c{h, p, static_cast<T*>(h.d_layered_hws), s, static_cast<const T*>(Z), static_cast<const T*>(X0)};
+    Sweep<T, HessPlan> c{h, p, h.d_layered_hws.as<T>(), s, static_cast<const T*>(Z), static_cast<const T*>(X0)};
     if (p.fuse_l0 && !h.layered_pairs_valid) {
         const dim3 grid((unsigned)((h.dout[0] + 255) / 256));
-        LG_TRY(c.launch(layered_pairs_kernel<T>, grid, dim3(256), h.d_W[0], h.dout[0], h.dout[0], h.nin, h.d_layered_pairs));
+        LG_TRY(c.launch(layered_pairs_kernel<T>, grid, dim3(256), h.d_W[0].get(), h.dout[0], h.dout[0], h.nin, h.d_layered_pairs.get()));
         h.layered_pairs_valid = true;
     }
     while (c.next_chunk(stage ? nrows : (long long)B * h.cfg.H, h.layered_hess_chunk_rows))
@@ -398,32 +398,19 @@ static size_t layered_chunk_rows(bool wide, size_t rc_rows, size_t cap) {
 // B*H = 30720 in fp64 is one chunk of 2.3 GB).  Reallocates only when the chunk length changes.
 static int layered_prepare(Handle& h, bool hess) {
 #ifdef NEMPC_STAMPS
-    g_lg_dbg = h.d_dbg;         // (diagnostic builds: every launch of the path passes here first)
+    g_lg_dbg = h.d_dbg.get();         // (diagnostic builds: every launch of the path passes here first)
 #endif
-    void*& ws = hess ? h.d_layered_hws : h.d_layered_ws;
+    DevBuf<>& ws = hess ? h.d_layered_hws : h.d_layered_ws;
     long long& chunk_rows = hess ? h.layered_hess_chunk_rows : h.layered_chunk_rows;
     const LayeredNet n = layered_net(h);
     const size_t per_row = hess ? layered_hess_offsets(n).total : layered_offsets(n).total;
     const size_t rc_rows = layered_chunk_rows(lg_wide(n), ((size_t)6144 << 20) / (per_row * h.esz), (size_t)h.cfg.max_batch * h.cfg.H);
-    hipError_t e = hipSuccess;
+    const char* const what = hess ? "layered Hessian workspace" : "layered workspace";
     // (with the Hessian workspace, once: layer 0's pair table -- 32 pairs at most, either dtype; the one place that allocates it)
-    if (hess && !h.d_layered_pairs) e = hipMalloc(&h.d_layered_pairs, (size_t)h.maxw * 32 * sizeof(double));
-    if (e == hipSuccess && !(ws && chunk_rows == (long long)rc_rows)) {
-        if (ws) (void)hipFree(ws);
-        ws = nullptr;
-        chunk_rows = (long long)rc_rows;
-        e = hipMalloc(&ws, per_row * rc_rows * h.esz);
-    }
-    if (e == hipSuccess) return NEMPC_OK;
-    set_error(std::string(hess ? "hipMalloc (layered Hessian workspace): " : "hipMalloc (layered workspace): ") + hipGetErrorString(e));
-    return NEMPC_ENOMEM;
-}
-
-void layered_free(Handle& h) {
-    for (void** p : {&h.d_layered_ws, &h.d_layered_hws, &h.d_layered_pairs}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
+    if (hess && !h.d_layered_pairs) LG_TRY(h.d_layered_pairs.alloc((size_t)h.maxw * 32 * sizeof(double), what));
+    if (ws && chunk_rows == (long long)rc_rows) return NEMPC_OK;
+    chunk_rows = (long long)rc_rows;
+    return ws.alloc(per_row * rc_rows * h.esz, what);
 }
 
 // Lagrangian blocks on the GEMM path: Discret / Unity directly, RK4 through the stage pipeline of kernels_rk4hess.hip.

@@ -73,11 +73,6 @@ bool mfma_hess_on_layered(const Handle& h) {
     return padded_width(h) == 128 && (h.nl - 1 == 3 || (h.nl - 1 == 2 && h.mfma_act == NEMPC_ACT_RUNTIME));
 }
 
-void mfma_free(Handle& h) {
-    if (h.mfma.blob) (void)hipFree(h.mfma.blob);
-    h.mfma.blob = nullptr;
-}
-
 // Pack every layer into MFMA A-operand fragments (lane-linear: element [frag*64 + lane]).
 // lane = kq*16 + i16 supplies A[M index i16][K index kq]; the K index of k-step (mt, r) stands for
 // feature 16*mt + row(kq, r) where row() is the accumulator register->row map of the dtype
@@ -152,22 +147,19 @@ int mfma_pack_weights(Handle& h, const double* const* W, const double* const* b)
     for (int i = 0; i < o.coop_small_elems; ++i) blob[o.fx_small + i] = blob[o.coop_small + i];
     for (int i = 0; i < nin * MT * 16; ++i) blob[o.fx_small + o.coop_small_elems + i] = blob[o.p0tab + i];
 
-    mfma_free(h);
-    hipError_t e = hipMalloc(&h.mfma.blob, blob.size() * h.esz);
-    if (e != hipSuccess) {
-        set_error(std::string("hipMalloc(mfma blob): ") + hipGetErrorString(e));
-        return NEMPC_ENOMEM;
-    }
+    // (into a buffer of its own: a failure leaves the handle's packed network as it was)
+    DevBuf<> dev;
+    if (int rc = dev.alloc(blob.size() * h.esz, "mfma blob")) return rc;
     if (f64) {
-        NEMPC_HIP(hipMemcpy(h.mfma.blob, blob.data(), blob.size() * 8, hipMemcpyHostToDevice));
+        NEMPC_HIP(hipMemcpy(dev.get(), blob.data(), blob.size() * 8, hipMemcpyHostToDevice));
     } else {
         std::vector<float> tmp(blob.begin(), blob.end());
-        NEMPC_HIP(hipMemcpy(h.mfma.blob, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
+        NEMPC_HIP(hipMemcpy(dev.get(), tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice));
     }
+    h.mfma.blob = std::move(dev);
     h.mfma.wp = wp;
     h.mfma.nh = nh;
     h.mfma.kin = 4 * ks;
-    h.mfma.blob_elems = blob.size();
     return NEMPC_OK;
 }
 
@@ -207,7 +199,7 @@ int launch_typed(const Handle& h, const P& p, const Plan& plan, hipStream_t s) {
 // the parameters every matrix-core kernel reads: network, dims, inputs, gather
 MfmaParams base_params(const Handle& h, int B, const void* Z, const void* X0, int ntiles, int scratch_per_wave) {
     MfmaParams p{};
-    p.blob = h.mfma.blob;
+    p.blob = h.mfma.blob.get();
     p.nx = h.cfg.nx; p.nu = h.cfg.nu; p.nin = h.nin; p.ks = (h.nin + h.ne + 3) / 4; p.mb = (h.nin + 15) / 16;
     p.ne = h.ne; p.extra = h.d_extra;
     p.off = make_offsets(h.mfma.wp, h.mfma.nh, p.ks, p.nx, p.nin, (int)h.esz);
@@ -269,20 +261,20 @@ int launch_rows_mfma(Handle& h, int B, const void* Z, const void* X0, const Rows
     MfmaParams p = base_params(h, B, Z, X0, (int)(((size_t)B * h.cfg.H + 15) / 16), mfma_shape(h, B).rows_scratch());
     p.g = o.g;
     // (a launch that writes the dense rows / band values itself has no assembly launch behind it: the caller's tiles only)
-    p.tiles = o.tiles ? o.tiles : (o.need_tiles && !(plan.covers & (COVERS_DENSE | COVERS_SPARSE)) ? h.d_tiles_ws : nullptr);
+    p.tiles = o.tiles ? o.tiles : (o.need_tiles && !(plan.covers & (COVERS_DENSE | COVERS_SPARSE)) ? h.d_tiles_ws.get() : nullptr);
     p.stage_out = o.stage_out; p.stage_stride = o.stage_stride;
-    p.dbg = h.d_dbg;
+    p.dbg = h.d_dbg.get();
     p.fuse_obj = plan.fuse;
     if (plan.covers & COVERS_DENSE) { p.fuse_jac = o.jac; p.jac_resident = plan.fuse && o.jac_resident; }
     if (plan.covers & COVERS_SPARSE) { p.fuse_sparse = o.sparse; p.sp_nnz = (int)h.jac_rows.size(); }
     if (plan.fuse || (plan.covers & COVERS_OBJ)) {      // (the fused evaluation reads the table's size whatever it writes)
-        p.fuse_f = o.f; p.fuse_grad = o.grad; p.obj = h.d_obj;
+        p.fuse_f = o.f; p.fuse_grad = o.grad; p.obj = h.d_obj.get();
         p.oo = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     }
     if (plan.covers & COVERS_GN) {
-        p.g = h.d_g_ws; p.tiles = nullptr;
-        p.gn_hvals = o.gn_hvals; p.gn_sigma = o.gn_sigma; p.gn_w = o.gn_w; p.gn_smap = h.d_hess_smap;
-        p.gn_objc = (const char*)h.d_obj + (size_t)obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu).total * h.esz;
+        p.g = h.d_g_ws.get(); p.tiles = nullptr;
+        p.gn_hvals = o.gn_hvals; p.gn_sigma = o.gn_sigma; p.gn_w = o.gn_w; p.gn_smap = h.d_hess_smap.get();
+        p.gn_objc = h.d_obj.as<const char>() + (size_t)obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu).total * h.esz;
         p.gn_nnz = (int)h.hess_rows.size(); p.gn_n_orph = h.hess_n_orph;
     }
     const int rc = h.cfg.dtype == NEMPC_F64 ? launch_typed<double>(h, p, plan, s) : launch_typed<float>(h, p, plan, s);
@@ -316,8 +308,8 @@ int launch_rowhess_mfma(Handle& h, int B, const void* Z, const void* X0, const v
     hp.lambda = lambda; hp.blocks = (plan.covers & COVERS_HVALS) ? nullptr : o.blocks;
     hp.ev_g = o.ev_g; hp.ev_tiles = o.ev_tiles;
     if (plan.covers & COVERS_HVALS) {       // the kernel assembles the tril values itself
-        hp.hvals = o.hvals; hp.sigma = o.sigma; hp.smap = h.d_hess_smap;
-        hp.objc = (const char*)h.d_obj + (size_t)obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu).total * h.esz;
+        hp.hvals = o.hvals; hp.sigma = o.sigma; hp.smap = h.d_hess_smap.get();
+        hp.objc = h.d_obj.as<const char>() + (size_t)obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu).total * h.esz;
         hp.nnz = (int)h.hess_rows.size(); hp.n_orph = h.hess_n_orph;
     }
     hp.p0tab = p.off.p0tab; hp.wLb = p.off.wLb; hp.ksx = (h.cfg.nx + 3) / 4;

@@ -259,10 +259,10 @@ int launch_objective_tracking(Handle& h, int B, const void* Z, void* f, void* gr
     ObjOffsets o = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     if (h.cfg.dtype == NEMPC_F64)
         hipLaunchKernelGGL(objective_tracking_kernel<double>, dim3(B), dim3(64), 0, s, B, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
-                           (const double*)h.d_obj, h.track, prob, (const double*)Z, (double*)f, (double*)grad);
+                           h.d_obj.as<const double>(), h.track, prob, (const double*)Z, (double*)f, (double*)grad);
     else
         hipLaunchKernelGGL(objective_tracking_kernel<float>, dim3(B), dim3(64), 0, s, B, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
-                           (const float*)h.d_obj, h.track, prob, (const float*)Z, (float*)f, (float*)grad);
+                           h.d_obj.as<const float>(), h.track, prob, (const float*)Z, (float*)f, (float*)grad);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
 }
@@ -272,10 +272,10 @@ int launch_objective(Handle& h, int B, const void* Z, void* f, void* grad, hipSt
     ObjOffsets o = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     if (h.cfg.dtype == NEMPC_F64)
         hipLaunchKernelGGL(objective_kernel<double>, dim3(B), dim3(64), 0, s, B, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
-                           (const double*)h.d_obj, (const double*)Z, (double*)f, (double*)grad);
+                           h.d_obj.as<const double>(), (const double*)Z, (double*)f, (double*)grad);
     else
         hipLaunchKernelGGL(objective_kernel<float>, dim3(B), dim3(64), 0, s, B, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
-                           (const float*)h.d_obj, (const float*)Z, (float*)f, (float*)grad);
+                           h.d_obj.as<const float>(), (const float*)Z, (float*)f, (float*)grad);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
 }
@@ -290,7 +290,7 @@ int launch_post_flat(Handle& h, int B, unsigned magic, const void* tiles, void* 
     h.last_dense_writer = DENSE_WRITER_FLAT;
     ObjOffsets o = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     hipLaunchKernelGGL(post_flat_kernel<T>, dim3((unsigned)(nb_asm + nb_obj)), dim3(256), 0, s, nb_asm, B, mn, magic, te,
-                       h.d_dense_map, (const T*)tiles, (T*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o, (const T*)h.d_obj,
+                       h.d_dense_map.get(), (const T*)tiles, (T*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o, h.d_obj.as<const T>(),
                        (const T*)Z, (T*)f, (T*)grad);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
@@ -310,8 +310,8 @@ int launch_post_scatter(Handle& h, int B, const void* tiles, void* jac, const vo
     h.last_dense_writer = DENSE_WRITER_SCATTER;
     ObjOffsets o = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     hipLaunchKernelGGL(post_scatter_kernel<T>, dim3((unsigned)(nb_asm + nb_obj)), dim3(256), 0, s, nb_asm, B, nnz, magic,
-                       h.m * h.n, te, h.d_sparse_map, h.d_sparse_pos, (const T*)tiles, (T*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
-                       (const T*)h.d_obj, (const T*)Z, (T*)f, (T*)grad);
+                       h.m * h.n, te, h.d_sparse_map.get(), h.d_sparse_pos.get(), (const T*)tiles, (T*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
+                       h.d_obj.as<const T>(), (const T*)Z, (T*)f, (T*)grad);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
 }
@@ -329,10 +329,10 @@ int launch_assemble_dense(Handle& h, int B, const void* tiles, void* jac, hipStr
     const dim3 block(256), grid((unsigned)post_problem_blocks((unsigned)mn, (unsigned)h.esz), (unsigned)B);
     h.last_dense_writer = DENSE_WRITER_ASSEMBLE;
     if (h.cfg.dtype == NEMPC_F64)
-        hipLaunchKernelGGL(assemble_dense_kernel<double>, grid, block, 0, s, mn, te, h.d_dense_map,
+        hipLaunchKernelGGL(assemble_dense_kernel<double>, grid, block, 0, s, mn, te, h.d_dense_map.get(),
                            (const double*)tiles, (double*)jac);
     else
-        hipLaunchKernelGGL(assemble_dense_kernel<float>, grid, block, 0, s, mn, te, h.d_dense_map,
+        hipLaunchKernelGGL(assemble_dense_kernel<float>, grid, block, 0, s, mn, te, h.d_dense_map.get(),
                            (const float*)tiles, (float*)jac);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
@@ -354,12 +354,12 @@ int launch_post(Handle& h, int B, const void* tiles, void* jac, const void* Z, v
     const dim3 block(256), grid((unsigned)(nb + 1), (unsigned)B);
     h.last_dense_writer = DENSE_WRITER_POST;
     if (h.cfg.dtype == NEMPC_F64)
-        hipLaunchKernelGGL(post_kernel<double>, grid, block, 0, s, nb, mn, te, h.d_dense_map, (const double*)tiles,
-                           (double*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o, (const double*)h.d_obj, (const double*)Z,
+        hipLaunchKernelGGL(post_kernel<double>, grid, block, 0, s, nb, mn, te, h.d_dense_map.get(), (const double*)tiles,
+                           (double*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o, h.d_obj.as<const double>(), (const double*)Z,
                            (double*)f, (double*)grad);
     else
-        hipLaunchKernelGGL(post_kernel<float>, grid, block, 0, s, nb, mn, te, h.d_dense_map, (const float*)tiles,
-                           (float*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o, (const float*)h.d_obj, (const float*)Z,
+        hipLaunchKernelGGL(post_kernel<float>, grid, block, 0, s, nb, mn, te, h.d_dense_map.get(), (const float*)tiles,
+                           (float*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o, h.d_obj.as<const float>(), (const float*)Z,
                            (float*)f, (float*)grad);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
@@ -379,12 +379,12 @@ int launch_post_sparse(Handle& h, int B, const void* tiles, void* vals, const vo
     ObjOffsets o = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     if (h.cfg.dtype == NEMPC_F64)
         hipLaunchKernelGGL(post_sparse_kernel<double>, dim3((unsigned)(nb_asm + nb_obj)), dim3(256), 0, s, nb_asm, B, nnz,
-                           magic, te, h.d_sparse_map, (const double*)tiles, (double*)vals, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
-                           (const double*)h.d_obj, (const double*)Z, (double*)f, (double*)grad);
+                           magic, te, h.d_sparse_map.get(), (const double*)tiles, (double*)vals, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
+                           h.d_obj.as<const double>(), (const double*)Z, (double*)f, (double*)grad);
     else
         hipLaunchKernelGGL(post_sparse_kernel<float>, dim3((unsigned)(nb_asm + nb_obj)), dim3(256), 0, s, nb_asm, B, nnz,
-                           magic, te, h.d_sparse_map, (const float*)tiles, (float*)vals, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
-                           (const float*)h.d_obj, (const float*)Z, (float*)f, (float*)grad);
+                           magic, te, h.d_sparse_map.get(), (const float*)tiles, (float*)vals, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
+                           h.d_obj.as<const float>(), (const float*)Z, (float*)f, (float*)grad);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
 }
@@ -394,10 +394,10 @@ int launch_assemble_sparse(Handle& h, int B, const void* tiles, void* vals, hipS
     const int te = h.cfg.H * h.cfg.nx * h.nin;
     const dim3 block(256), grid((unsigned)((nnz + 255) / 256), (unsigned)B);
     if (h.cfg.dtype == NEMPC_F64)
-        hipLaunchKernelGGL(assemble_sparse_kernel<double>, grid, block, 0, s, nnz, te, h.d_sparse_map,
+        hipLaunchKernelGGL(assemble_sparse_kernel<double>, grid, block, 0, s, nnz, te, h.d_sparse_map.get(),
                            (const double*)tiles, (double*)vals);
     else
-        hipLaunchKernelGGL(assemble_sparse_kernel<float>, grid, block, 0, s, nnz, te, h.d_sparse_map,
+        hipLaunchKernelGGL(assemble_sparse_kernel<float>, grid, block, 0, s, nnz, te, h.d_sparse_map.get(),
                            (const float*)tiles, (float*)vals);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
@@ -443,24 +443,24 @@ int launch_assemble_hess(Handle& h, int B, const void* blocks, const void* sigma
     const int be = h.cfg.H * h.nin * h.nin;
     const dim3 block(256);
     const size_t esz = h.esz;
-    const char* objc = (const char*)h.d_obj + (size_t)obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu).total * esz;
+    const char* objc = h.d_obj.as<const char>() + (size_t)obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu).total * esz;
     if (hvals) {
         const dim3 grid((unsigned)((nnz + 255) / 256), (unsigned)B);
         if (h.cfg.dtype == NEMPC_F64)
-            hipLaunchKernelGGL(assemble_hess_kernel<double>, grid, block, 0, s, nnz, h.w, be, h.d_hess_map,
+            hipLaunchKernelGGL(assemble_hess_kernel<double>, grid, block, 0, s, nnz, h.w, be, h.d_hess_map.get(),
                                (const double*)objc, (const double*)blocks, (const double*)sigma, (double*)hvals);
         else
-            hipLaunchKernelGGL(assemble_hess_kernel<float>, grid, block, 0, s, nnz, h.w, be, h.d_hess_map,
+            hipLaunchKernelGGL(assemble_hess_kernel<float>, grid, block, 0, s, nnz, h.w, be, h.d_hess_map.get(),
                                (const float*)objc, (const float*)blocks, (const float*)sigma, (float*)hvals);
     }
     if (hdense) {
         const dim3 grid((unsigned)((nn + 255) / 256), (unsigned)B);
         if (h.cfg.dtype == NEMPC_F64)
-            hipLaunchKernelGGL(assemble_hess_kernel<double>, grid, block, 0, s, nn, h.w, be, h.d_hess_map + (size_t)nnz * h.w,
+            hipLaunchKernelGGL(assemble_hess_kernel<double>, grid, block, 0, s, nn, h.w, be, h.d_hess_map.get() + (size_t)nnz * h.w,
                                (const double*)(objc + (size_t)nnz * esz), (const double*)blocks,
                                (const double*)sigma, (double*)hdense);
         else
-            hipLaunchKernelGGL(assemble_hess_kernel<float>, grid, block, 0, s, nn, h.w, be, h.d_hess_map + (size_t)nnz * h.w,
+            hipLaunchKernelGGL(assemble_hess_kernel<float>, grid, block, 0, s, nn, h.w, be, h.d_hess_map.get() + (size_t)nnz * h.w,
                                (const float*)(objc + (size_t)nnz * esz), (const float*)blocks, (const float*)sigma,
                                (float*)hdense);
     }
@@ -474,7 +474,7 @@ int launch_assemble_hess_gn(Handle& h, int B, const void* tiles, const void* w, 
     const int nn = h.n * h.n;
     const dim3 block(256);
     const size_t esz = h.esz;
-    const char* objc = (const char*)h.d_obj + (size_t)obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu).total * esz;
+    const char* objc = h.d_obj.as<const char>() + (size_t)obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu).total * esz;
     auto go = [&](int cnt, const int32_t* map, const char* oc, void* out) {
         const dim3 grid((unsigned)((cnt + 255) / 256), (unsigned)B);
         if (h.cfg.dtype == NEMPC_F64)
@@ -484,8 +484,8 @@ int launch_assemble_hess_gn(Handle& h, int B, const void* tiles, const void* w, 
             hipLaunchKernelGGL(assemble_hess_gn_kernel<float>, grid, block, 0, s, cnt, h.w, h.cfg.H, h.cfg.nx, h.nin, map,
                                (const float*)oc, (const float*)tiles, (const float*)w, (const float*)sigma, (float*)out);
     };
-    if (hvals) go(nnz, h.d_hess_map, objc, hvals);
-    if (hdense) go(nn, h.d_hess_map + (size_t)nnz * h.w, objc + (size_t)nnz * esz, hdense);
+    if (hvals) go(nnz, h.d_hess_map.get(), objc, hvals);
+    if (hdense) go(nn, h.d_hess_map.get() + (size_t)nnz * h.w, objc + (size_t)nnz * esz, hdense);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
 }

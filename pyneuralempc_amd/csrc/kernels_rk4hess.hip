@@ -116,14 +116,13 @@ int congruence_waves(const Handle& h) {
     return 0;
 }
 
-int dev_alloc_rk4(void** p, size_t bytes) {
-    if (*p) return NEMPC_OK;
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        set_error(std::string("hipMalloc(rk4 hessian workspace): ") + hipGetErrorString(e));
-        return NEMPC_ENOMEM;
-    }
+// the pipeline's three buffers, sized for max_batch on first use (nempc_reserve empties them)
+int alloc_rk4_ws(Handle& h) {
+    const size_t Rcap = (size_t)h.cfg.max_batch * h.cfg.H, nx = (size_t)h.cfg.nx, nin = (size_t)h.nin;
+    int rc;
+    if (!h.d_rk4_stage && (rc = h.d_rk4_stage.alloc(Rcap * 4 * (nin + 2 * nx * nin) * h.esz, "rk4 hessian workspace"))) return rc;
+    if (!h.d_rk4_nu && (rc = h.d_rk4_nu.alloc(Rcap * 4 * nx * h.esz, "rk4 hessian workspace"))) return rc;
+    if (!h.d_rk4_ht && (rc = h.d_rk4_ht.alloc(Rcap * 4 * nin * nin * h.esz, "rk4 hessian workspace"))) return rc;
     return NEMPC_OK;
 }
 
@@ -132,14 +131,14 @@ int run_small_kernels(Handle& h, size_t R, const void* lambda, void* blocks, int
     const int nx = h.cfg.nx, nin = h.nin;
     if (!congruence) {
         hipLaunchKernelGGL(rk4_nu_kernel<T>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, R, h.cfg.H, nx, nin, h.m,
-                           (T)h.cfg.DT, (const T*)lambda, (const T*)h.d_rk4_stage, stride, (T*)h.d_rk4_nu);
+                           (T)h.cfg.DT, (const T*)lambda, h.d_rk4_stage.as<const T>(), stride, h.d_rk4_nu.as<T>());
     } else {
         const int nw = congruence_waves(h);
         if (nw < 1) return NEMPC_EUNSUPPORTED;       // (the pipelines ask before their first launch: not reached)
         const size_t lds = (size_t)nw * (size_t)(8 * nin * nin + 3 * nx * nin) * sizeof(T);
         NEMPC_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(rk4_congruence_kernel<T>), lds));
         hipLaunchKernelGGL(rk4_congruence_kernel<T>, dim3((unsigned)((R + nw - 1) / nw)), dim3((unsigned)(64 * nw)), lds, s, R, nx, nin,
-                           (T)h.cfg.DT, (const T*)h.d_rk4_stage, stride, (const T*)h.d_rk4_ht, (T*)blocks);
+                           (T)h.cfg.DT, h.d_rk4_stage.as<const T>(), stride, h.d_rk4_ht.as<const T>(), (T*)blocks);
     }
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
@@ -149,28 +148,19 @@ int run_small_kernels(Handle& h, size_t R, const void* lambda, void* blocks, int
 
 bool rk4hess_supported(const Handle& h) { return congruence_waves(h) >= 1; }
 
-void rk4hess_free(Handle& h) {
-    for (void** p : {&h.d_rk4_stage, &h.d_rk4_nu, &h.d_rk4_ht}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-}
-
 int launch_rowhess_rk4_mfma(Handle& h, int B, const void* Z, const void* X0, const void* lambda, void* blocks,
                             hipStream_t s, void* g_out, void* tiles_out) {
     const int nx = h.cfg.nx, nin = h.nin;
     const int stride = nin + 2 * nx * nin;
-    const size_t Rcap = (size_t)h.cfg.max_batch * h.cfg.H, R = (size_t)B * h.cfg.H;
+    const size_t R = (size_t)B * h.cfg.H;
     int rc;
     if (!rk4hess_supported(h)) return NEMPC_EUNSUPPORTED;       // (the callers ask first: not reached)
-    if ((rc = dev_alloc_rk4(&h.d_rk4_stage, Rcap * 4 * stride * h.esz))) return rc;
-    if ((rc = dev_alloc_rk4(&h.d_rk4_nu, Rcap * 4 * nx * h.esz))) return rc;
-    if ((rc = dev_alloc_rk4(&h.d_rk4_ht, Rcap * 4 * nin * nin * h.esz))) return rc;
+    if ((rc = alloc_rk4_ws(h))) return rc;
     // 1. stage records; the launch's defects and tiles go to the caller (the batched solver wants them anyway) or to
     //    the handle's scratch outputs
     RowsOut ro;
-    ro.g = g_out ? g_out : h.d_g_ws; ro.tiles = tiles_out ? tiles_out : h.d_tiles_ws;
-    ro.stage_out = h.d_rk4_stage; ro.stage_stride = stride;
+    ro.g = g_out ? g_out : h.d_g_ws.get(); ro.tiles = tiles_out ? tiles_out : h.d_tiles_ws.get();
+    ro.stage_out = h.d_rk4_stage.get(); ro.stage_stride = stride;
     if ((rc = launch_rows_mfma(h, B, Z, X0, ro, s))) return rc;
     const bool f64 = h.cfg.dtype == NEMPC_F64;
     // 2. stage multipliers
@@ -179,7 +169,7 @@ int launch_rowhess_rk4_mfma(Handle& h, int B, const void* Z, const void* X0, con
         return rc;
     // 3. contracted network Hessians at the four stage inputs
     HessOut ho;
-    ho.blocks = h.d_rk4_ht; ho.xi_direct = h.d_rk4_stage; ho.xi_stride = stride; ho.lam_direct = h.d_rk4_nu; ho.vdiv = 4;
+    ho.blocks = h.d_rk4_ht.get(); ho.xi_direct = h.d_rk4_stage.get(); ho.xi_stride = stride; ho.lam_direct = h.d_rk4_nu.get(); ho.vdiv = 4;
     if ((rc = launch_rowhess_mfma(h, B, Z, X0, lambda, ho, s))) return rc;
     h.last_hess_kernel += HESS_IN_RK4;      // (the network kernel of step 3, inside the pipeline)
     // 4. congruence sum
@@ -192,21 +182,19 @@ int launch_rowhess_rk4_layered(Handle& h, int B, const void* Z, const void* X0, 
                                void* g_out, void* tiles_out) {
     const int nx = h.cfg.nx, nin = h.nin;
     const int stride = nin + 2 * nx * nin;
-    const size_t Rcap = (size_t)h.cfg.max_batch * h.cfg.H, R = (size_t)B * h.cfg.H;
+    const size_t R = (size_t)B * h.cfg.H;
     int rc;
     // (a wave's slice of the congruence kernel does not fit the device's LDS: the generic Hessian kernel, nothing launched here)
     if (congruence_waves(h) < 1) return NEMPC_EUNSUPPORTED;
-    if ((rc = dev_alloc_rk4(&h.d_rk4_stage, Rcap * 4 * stride * h.esz))) return rc;
-    if ((rc = dev_alloc_rk4(&h.d_rk4_nu, Rcap * 4 * nx * h.esz))) return rc;
-    if ((rc = dev_alloc_rk4(&h.d_rk4_ht, Rcap * 4 * nin * nin * h.esz))) return rc;
-    if ((rc = launch_rows_layered_stages(h, B, Z, X0, g_out ? g_out : h.d_g_ws, tiles_out ? tiles_out : h.d_tiles_ws, h.d_rk4_stage,
+    if ((rc = alloc_rk4_ws(h))) return rc;
+    if ((rc = launch_rows_layered_stages(h, B, Z, X0, g_out ? g_out : h.d_g_ws.get(), tiles_out ? tiles_out : h.d_tiles_ws.get(), h.d_rk4_stage.get(),
                                          stride, s)))
         return rc;
     const bool f64 = h.cfg.dtype == NEMPC_F64;
     if ((rc = f64 ? run_small_kernels<double>(h, R, lambda, blocks, stride, false, s)
                   : run_small_kernels<float>(h, R, lambda, blocks, stride, false, s)))
         return rc;
-    if ((rc = launch_rowhess_layered_direct(h, (long long)R * 4, h.d_rk4_stage, stride, h.d_rk4_nu, h.d_rk4_ht, s))) return rc;
+    if ((rc = launch_rowhess_layered_direct(h, (long long)R * 4, h.d_rk4_stage.get(), stride, h.d_rk4_nu.get(), h.d_rk4_ht.get(), s))) return rc;
     h.last_hess_kernel += HESS_IN_RK4;
     return f64 ? run_small_kernels<double>(h, R, lambda, blocks, stride, true, s)
                : run_small_kernels<float>(h, R, lambda, blocks, stride, true, s);

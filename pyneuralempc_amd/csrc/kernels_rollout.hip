@@ -372,7 +372,7 @@ RollNet make_rollnet(const Handle& h, int B) {
     r.extra = h.d_extra;
     for (int l = 0; l < h.nl; ++l) {
         r.din[l] = h.din[l]; r.dout[l] = h.dout[l]; r.act[l] = h.act[l]; r.actp[l] = h.actp[l];
-        r.W[l] = h.d_W[l]; r.b[l] = h.d_b[l];
+        r.W[l] = h.d_W[l].get(); r.b[l] = h.d_b[l].get();
     }
     return r;
 }

@@ -150,10 +150,10 @@ int launch_sensitivity(Handle& h, int B, const void* Z, const void* tiles, const
     a.B = B; a.H = h.cfg.H; a.nx = h.cfg.nx; a.nu = h.cfg.nu; a.ppw = p.ppw; a.use_lds = p.use_lds ? 1 : 0;
     a.staged = p.staged ? 1 : 0;
     a.stride = p.stride; a.per_problem = p.per_problem;
-    a.Z = Z; a.tiles = tiles; a.blocks = blocks; a.zl = zl; a.zu = zu; a.obj = h.d_obj;
+    a.Z = Z; a.tiles = tiles; a.blocks = blocks; a.zl = zl; a.zu = zu; a.obj = h.d_obj.get();
     a.oo = obj_offsets(h.cfg.H, h.cfg.nx, h.cfg.nu);
     a.lb = lb; a.ub = ub; a.bb = h.bbind;
-    a.Kst = h.d_sens_ws;
+    a.Kst = h.d_sens_ws.as<double>();
     a.Pst = a.Kst + Bm * H * nu * nx;
     a.sig = a.Pst + Bm * H * nx * nx;
     a.scratch = a.sig + Bm * (size_t)h.n;

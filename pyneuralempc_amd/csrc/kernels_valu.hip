@@ -486,7 +486,7 @@ NetDev make_netdev(const Handle& h) {
     nd.gk = h.gather();
     for (int l = 0; l < h.nl; ++l) {
         nd.din[l] = h.din[l]; nd.dout[l] = h.dout[l]; nd.act[l] = h.act[l]; nd.actp[l] = h.actp[l];
-        nd.W[l] = h.d_W[l]; nd.Wt[l] = h.d_Wt[l]; nd.b[l] = h.d_b[l];
+        nd.W[l] = h.d_W[l].get(); nd.Wt[l] = h.d_Wt[l].get(); nd.b[l] = h.d_b[l].get();
     }
     return nd;
 }
@@ -503,14 +503,7 @@ size_t valu_workspace_elems(const Handle& h) {
 // allocates it there, on first use.
 int ensure_valu_ws(Handle& h) {
     if (h.d_valu_ws) return NEMPC_OK;
-    h.valu_ws_elems = valu_workspace_elems(h);
-    hipError_t e = hipMalloc(&h.d_valu_ws, h.valu_ws_elems * h.esz ? h.valu_ws_elems * h.esz : 16);
-    if (e != hipSuccess) {
-        h.d_valu_ws = nullptr;
-        set_error(std::string("hipMalloc (generic kernel workspace): ") + hipGetErrorString(e));
-        return NEMPC_ENOMEM;
-    }
-    return NEMPC_OK;
+    return h.d_valu_ws.alloc(valu_workspace_elems(h) * h.esz, "generic kernel workspace");
 }
 
 int launch_rows_valu(Handle& h, int B, const void* Z, const void* X0, void* g, void* tiles, hipStream_t s) {
@@ -525,11 +518,11 @@ int launch_rows_valu(Handle& h, int B, const void* Z, const void* X0, void* g, v
     if (h.cfg.dtype == NEMPC_F64)
         hipLaunchKernelGGL(rows_valu_kernel<double>, grid, block, 0, s, nd, o, h.cfg.integrator, h.cfg.DT, B,
                            h.cfg.H, Rcap, (const double*)Z, (const double*)X0, (double*)g, h.m, (int)h.box,
-                           (double*)tiles, (double*)h.d_valu_ws);
+                           (double*)tiles, h.d_valu_ws.as<double>());
     else
         hipLaunchKernelGGL(rows_valu_kernel<float>, grid, block, 0, s, nd, o, h.cfg.integrator, (float)h.cfg.DT, B,
                            h.cfg.H, Rcap, (const float*)Z, (const float*)X0, (float*)g, h.m, (int)h.box,
-                           (float*)tiles, (float*)h.d_valu_ws);
+                           (float*)tiles, h.d_valu_ws.as<float>());
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
 }
@@ -550,11 +543,11 @@ int launch_rowhess_valu(Handle& h, int B, const void* Z, const void* X0, const v
     if (h.cfg.dtype == NEMPC_F64)
         hipLaunchKernelGGL(rowhess_valu_kernel<double>, grid, block, 0, s, nd, o, h.cfg.integrator, h.cfg.DT, B, h.cfg.H,
                            Rcap, (const double*)Z, (const double*)X0, (const double*)lambda, h.m, (double*)blocks,
-                           (double*)h.d_valu_ws);
+                           h.d_valu_ws.as<double>());
     else
         hipLaunchKernelGGL(rowhess_valu_kernel<float>, grid, block, 0, s, nd, o, h.cfg.integrator, (float)h.cfg.DT, B,
                            h.cfg.H, Rcap, (const float*)Z, (const float*)X0, (const float*)lambda, h.m, (float*)blocks,
-                           (float*)h.d_valu_ws);
+                           h.d_valu_ws.as<float>());
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
 }

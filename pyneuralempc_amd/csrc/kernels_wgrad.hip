@@ -369,7 +369,7 @@ int run(Handle& h, const WgradPlan& p, int B, const void* Z, const void* X0, con
         const int32_t* skip, void* gtheta, hipStream_t s) {
     const int H = h.cfg.H, nx = h.cfg.nx;
     const size_t scr_elems = (size_t)(4 * p.maxdim + 4 * nx) * p.chunk_rows;
-    char* base = (char*)h.d_wgrad_ws;
+    char* base = h.d_wgrad_ws.as<char>();
     T* fac = (T*)base;
     T* scr = (T*)(base + align256((size_t)p.factor_elems * sizeof(T)));
     T* slab = (T*)((char*)scr + align256(scr_elems * sizeof(T)));
@@ -385,7 +385,7 @@ int run(Handle& h, const WgradPlan& p, int B, const void* Z, const void* X0, con
     g.nl = h.nl; g.npairs = v ? 2 : 1; g.pitch = p.pitch;
     for (int l = 0; l < h.nl; ++l) {
         net.din[l] = h.din[l]; net.dout[l] = h.dout[l]; net.act[l] = h.act[l]; net.actp[l] = h.actp[l];
-        net.W[l] = h.d_W[l]; net.Wt[l] = h.d_Wt[l]; net.b[l] = h.d_b[l];
+        net.W[l] = h.d_W[l].get(); net.Wt[l] = h.d_Wt[l].get(); net.b[l] = h.d_b[l].get();
         const WgradLayer& L = p.L[l];
         net.offA[l] = g.offA[l] = L.offA; net.offAd[l] = g.offAd[l] = L.offAd;
         net.offD[l] = g.offD[l] = L.offD; net.offDd[l] = g.offDd[l] = L.offDd;
@@ -432,25 +432,9 @@ int launch_weight_grad(Handle& h, int B, const void* Z, const void* X0, const vo
     }
     const size_t bytes = align256((size_t)p.factor_elems * h.esz) + align256((size_t)(4 * p.maxdim + 4 * h.cfg.nx) * p.chunk_rows * h.esz) +
                          align256((size_t)p.slab_elems * h.esz) + align256(((size_t)h.cfg.max_batch + 1) * sizeof(int32_t));
-    if (bytes > h.wgrad_ws_bytes) {
-        NEMPC_HIP(hipDeviceSynchronize());
-        dev_free(h.d_wgrad_ws);
-        h.wgrad_ws_bytes = 0;
-        hipError_t e = hipMalloc(&h.d_wgrad_ws, bytes);
-        if (e != hipSuccess) {
-            h.d_wgrad_ws = nullptr;
-            set_error(std::string("hipMalloc (nempc_weight_grad workspace): ") + hipGetErrorString(e));
-            return NEMPC_ENOMEM;
-        }
-        h.wgrad_ws_bytes = bytes;
-    }
+    if (int rc = h.d_wgrad_ws.ensure(bytes, "nempc_weight_grad workspace")) return rc;
     return h.cfg.dtype == NEMPC_F64 ? run<double>(h, p, B, Z, X0, lam, v, w, skip, gtheta, s)
                                     : run<float>(h, p, B, Z, X0, lam, v, w, skip, gtheta, s);
-}
-
-void wgrad_free(Handle& h) {
-    dev_free(h.d_wgrad_ws);
-    h.wgrad_ws_bytes = 0;
 }
 
 }  // namespace nempc

@@ -39,6 +39,28 @@ int hip_fail(hipError_t e, const char* what) {
     return NEMPC_EHIP;
 }
 
+// dev_buf.h's raw functions: the library's only hipMalloc / hipFree outside solver.hip and comm.hip
+int dev_raw_sync() {
+    NEMPC_HIP(hipDeviceSynchronize());
+    return NEMPC_OK;
+}
+
+int dev_raw_alloc(void** p, size_t bytes, const char* what) {
+    *p = nullptr;
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return NEMPC_OK;
+    *p = nullptr;
+    set_error(std::string("hipMalloc (") + what + "): " + hipGetErrorString(e));
+    return NEMPC_ENOMEM;
+}
+
+void dev_raw_free(void* p) { (void)hipFree(p); }
+
+Handle::~Handle() {
+    solver_free(*this);
+    comm_free(*this);
+}
+
 namespace {
 
 int fail(int code, const std::string& msg) {
@@ -76,18 +98,14 @@ int upload(const Handle& h, const std::vector<double>& src, void* dst) {
     return h.cfg.dtype == NEMPC_F64 ? upload_as<double>(src, dst) : upload_as<float>(src, dst);
 }
 
-template <class P>
-int dev_alloc(P** p, size_t bytes) {
-    *p = nullptr;
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc((void**)p, bytes);
-    if (e != hipSuccess) {
-        set_error(std::string("hipMalloc: ") + hipGetErrorString(e));
-        return NEMPC_ENOMEM;
-    }
+// a fresh device copy of a host array of int32 codes
+int upload_map(DevBuf<int32_t>& dst, const std::vector<int32_t>& src, const char* what) {
+    if (int rc = dst.alloc(src.size() * sizeof(int32_t), what)) return rc;
+    NEMPC_HIP(hipMemcpy(dst.get(), src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     return NEMPC_OK;
 }
 
+// the row count, the Jacobian's structure and its assembly maps
 int rebuild_structure(Handle& h) {
     const int H = h.cfg.H, nx = h.cfg.nx, nu = h.cfg.nu, nin = h.nin, n = h.n;
     h.m = H * nx + (h.box ? H * nx : 0);
@@ -121,19 +139,11 @@ int rebuild_structure(Handle& h) {
     if (h.box)
         for (int k = 0; k < H * nx; ++k) put(H * nx + k, k, MAP_PLUS_ONE);
 
-    dev_free(h.d_dense_map);
-    dev_free(h.d_sparse_map);
-    dev_free(h.d_sparse_pos);
-    dev_free(h.d_g_ws);
+    h.d_sparse_map.reset(); h.d_sparse_pos.reset();     // (no map of the old shape behind a failure)
     int rc;
-    if ((rc = dev_alloc(&h.d_dense_map, dense.size() * sizeof(int32_t)))) return rc;
-    if ((rc = dev_alloc(&h.d_sparse_map, sparse.size() * sizeof(int32_t)))) return rc;
-    if ((rc = dev_alloc(&h.d_sparse_pos, pos.size() * sizeof(int32_t)))) return rc;
-    if ((rc = dev_alloc(&h.d_g_ws, (size_t)h.cfg.max_batch * m * h.esz))) return rc;
-    NEMPC_HIP(hipMemcpy(h.d_dense_map, dense.data(), dense.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    NEMPC_HIP(hipMemcpy(h.d_sparse_map, sparse.data(), sparse.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    NEMPC_HIP(hipMemcpy(h.d_sparse_pos, pos.data(), pos.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    return NEMPC_OK;
+    if ((rc = upload_map(h.d_dense_map, dense, "dense map"))) return rc;
+    if ((rc = upload_map(h.d_sparse_map, sparse, "sparse map"))) return rc;
+    return upload_map(h.d_sparse_pos, pos, "sparse positions");
 }
 
 // Objective upload, in two parts.  The Hessian maps (tril structure, gather / scatter maps) depend on the problem's
@@ -203,11 +213,9 @@ int upload_objective(Handle& h, const ObjHost& o_in) {
         for (int r = 0; r < n; ++r)
             for (int c = 0; c < n; ++c) emit(r, c);
 
-        dev_free(h.d_hess_map);
-        if ((rc = dev_alloc(&h.d_hess_map, hmap.size() * sizeof(int32_t)))) return rc;
-        NEMPC_HIP(hipMemcpy(h.d_hess_map, hmap.data(), hmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        if ((rc = upload_map(h.d_hess_map, hmap, "Hessian map"))) return rc;
         // scatter form of the tril map for the Hessian kernel's fused assembly (plain models: one block element per entry)
-        dev_free(h.d_hess_smap);
+        h.d_hess_smap.reset();
         h.hess_n_orph = -1;
         if (w == 1) {
             const int nnz_t = (int)h.hess_rows.size(), be = H * nin * nin;
@@ -218,8 +226,7 @@ int upload_objective(Handle& h, const ObjHost& o_in) {
             }
             if ((int)orph.size() <= nin * nin) {
                 smap.insert(smap.end(), orph.begin(), orph.end());
-                if ((rc = dev_alloc(&h.d_hess_smap, smap.size() * sizeof(int32_t)))) return rc;
-                NEMPC_HIP(hipMemcpy(h.d_hess_smap, smap.data(), smap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+                if ((rc = upload_map(h.d_hess_smap, smap, "Hessian scatter map"))) return rc;
                 h.hess_n_orph = (int)orph.size();
             }
         }
@@ -247,45 +254,11 @@ int upload_objective(Handle& h, const ObjHost& o_in) {
         for (int r = 0; r < n; ++r)
             for (int c = 0; c < n; ++c) oc[(size_t)r * n + c] = obj_const(r, c, &st);
     }
-    if (!h.d_obj || h.obj_elems != all.size()) {
-        dev_free(h.d_obj);
-        h.obj_elems = 0;
-        if ((rc = dev_alloc(&h.d_obj, all.size() * h.esz))) return rc;
-        h.obj_elems = all.size();
-    }
-    if ((rc = upload(h, all, h.d_obj))) return rc;
+    if (!h.d_obj || h.d_obj.bytes() != all.size() * h.esz)
+        if ((rc = h.d_obj.alloc(all.size() * h.esz, "objective table"))) return rc;
+    if ((rc = upload(h, all, h.d_obj.get()))) return rc;
     h.have_objective = true;
     return NEMPC_OK;
-}
-
-void destroy_impl(Handle* h) {
-    for (int l = 0; l < NEMPC_MAX_LAYERS; ++l) {
-        dev_free(h->d_W[l]);
-        dev_free(h->d_Wt[l]);
-        dev_free(h->d_b[l]);
-    }
-    mfma_free(*h);
-    layered_free(*h);
-    rk4hess_free(*h);
-    solver_free(*h);
-    comm_free(*h);
-    dev_free(h->d_obj);
-    dev_free(h->d_dense_map);
-    dev_free(h->d_sparse_map);
-    dev_free(h->d_sparse_pos);
-    dev_free(h->d_hess_map);
-    dev_free(h->d_hess_smap);
-    dev_free(h->d_tiles_ws);
-    dev_free(h->d_g_ws);
-    dev_free(h->d_valu_ws);
-    dev_free(h->d_hess_ws);
-    dev_free(h->d_kkt_grad);
-    dev_free(h->d_kkt_bounds);
-    dev_free(h->d_sens_ws);
-    kktsolve_free(*h);
-    wgrad_free(*h);
-    egrad_free(*h);
-    delete h;
 }
 
 // The variable bounds nempc_kkt_residual and nempc_sensitivity see -- the caller's lb / ub (n host doubles each, null =
@@ -303,32 +276,49 @@ int cached_bounds(Handle& h, const double* lb, const double* ub, const char* who
     // (bit-wise comparison: -inf / inf compare equal to themselves either way, and a NaN is uploaded every time)
     if (h.kkt_bounds_host.size() != both.size() ||
         std::memcmp(h.kkt_bounds_host.data(), both.data(), both.size() * sizeof(double)) != 0) {
-        NEMPC_HIP(hipMemcpyAsync(h.d_kkt_bounds, both.data(), both.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        NEMPC_HIP(hipMemcpyAsync(h.d_kkt_bounds.get(), both.data(), both.size() * sizeof(double), hipMemcpyHostToDevice, s));
         NEMPC_HIP(hipStreamSynchronize(s));   // `both` is stack-owned
         h.kkt_bounds_host = both;
     }
-    dlb = h.d_kkt_bounds; dub = h.d_kkt_bounds + h.n;
+    dlb = h.d_kkt_bounds.get(); dub = dlb + h.n;
     return NEMPC_OK;
 }
 
-// The workspaces sized by cfg.max_batch (nempc_create, nempc_reserve), all null on entry.  Not d_g_ws: its row count is
-// rebuild_structure's.  Sized and allocated here, not inside the first callback: an allocation is a synchronising call, is not
-// stream-capture safe, and an out-of-memory belongs to create / reserve, not to the middle of a solve.
+// d_g_ws, (Bmax, m): sized with the batch workspaces below and again when the row count changes (nempc_set_box_rows)
+size_t g_ws_bytes(const Handle& h) { return (size_t)h.cfg.max_batch * h.m * h.esz; }
+
+// The buffers sized by cfg.max_batch that nempc_reserve replaces, named once, with their bytes at the current max_batch.
+// what == nullptr: not sized here -- its first user does that (d_valu_ws: ensure_valu_ws; the RK4 Hessian pipeline's three;
+// d_sens_ws of a rolling-window handle is never needed: nempc_sensitivity refuses those).  Not on the list: the layered path's
+// chunk workspaces (layered_prepare replaces them when the chunk length changes) and the ones a call grows (DevBuf::ensure).
+struct BatchWs {
+    DevBuf<>& buf;
+    size_t bytes;
+    const char* what;
+};
+std::vector<BatchWs> batch_workspaces(Handle& h) {
+    const size_t Bm = (size_t)h.cfg.max_batch, rows = Bm * h.cfg.H;
+    return {
+        {h.d_tiles_ws, rows * h.cfg.nx * h.nin * h.esz, "tiles workspace"},
+        {h.d_hess_ws, rows * h.nin * h.nin * h.esz, "Lagrangian blocks workspace"},
+        {h.d_kkt_grad, Bm * h.n * h.esz, "nempc_kkt_residual gradient"},
+        {h.d_sens_ws, h.w == 1 ? sens_ws_doubles(h, Bm) * sizeof(double) : 0, h.w == 1 ? "nempc_sensitivity workspace" : nullptr},
+        {h.d_g_ws, g_ws_bytes(h), "defect workspace"},
+        {h.d_valu_ws, 0, nullptr},
+        {h.d_rk4_stage, 0, nullptr}, {h.d_rk4_nu, 0, nullptr}, {h.d_rk4_ht, 0, nullptr},
+    };
+}
+
+// nempc_create / nempc_reserve: the listed workspaces (all empty on entry), then the row kernels' own.  Sized and allocated
+// here, not inside the first callback: an allocation is a synchronising call, is not stream-capture safe, and an
+// out-of-memory belongs to create / reserve, not to the middle of a solve.
 int alloc_batch_workspaces(Handle& h) {
-    const size_t Bm = (size_t)h.cfg.max_batch;
-    int rc;
-    if ((rc = dev_alloc(&h.d_tiles_ws, Bm * h.cfg.H * h.cfg.nx * h.nin * h.esz))) return rc;
-    if (h.layered) {
-        if ((rc = layered_reserve(h))) return rc;
-    } else {
-        if ((rc = ensure_valu_ws(h))) return rc;
-        if (h.layered_hess && (rc = layered_reserve(h))) return rc;
-    }
-    if ((rc = dev_alloc(&h.d_hess_ws, Bm * h.cfg.H * h.nin * h.nin * h.esz))) return rc;
-    if ((rc = dev_alloc(&h.d_kkt_grad, Bm * h.n * h.esz))) return rc;               // nempc_kkt_residual's evaluation
-    // nempc_sensitivity's double workspaces (plain models only: the call refuses rolling windows)
-    if (h.w == 1 && (rc = dev_alloc(&h.d_sens_ws, sens_ws_doubles(h, Bm) * sizeof(double)))) return rc;
-    return NEMPC_OK;
+    for (const BatchWs& w : batch_workspaces(h))
+        if (w.what)
+            if (int rc = w.buf.alloc(w.bytes, w.what)) return rc;
+    if (h.layered) return layered_reserve(h);
+    if (int rc = ensure_valu_ws(h)) return rc;
+    return h.layered_hess ? layered_reserve(h) : NEMPC_OK;
 }
 
 // nempc_set_objective; every null argument is its default (Q = I, R = 0.1 I, zero references and linear costs)
@@ -411,11 +401,11 @@ int point_prepare(nempc_handle hh, const char* who, unsigned needs, int32_t B, c
         return fail(NEMPC_ESTATE, who, ": the handle's workspaces are gone (a failed nempc_reserve)");
     pc.s = reinterpret_cast<hipStream_t>(stream);
     if (int rc = cached_bounds(h, lb, ub, who, pc.s, pc.dlb, pc.dub)) return rc;
-    void* const grad = (needs & POINT_GRAD) ? h.d_kkt_grad : nullptr;
-    if (int rc = nempc_eval(hh, B, Z, X0, nullptr, grad, h.d_g_ws, nullptr, h.d_tiles_ws, nullptr, stream)) return rc;
+    void* const grad = (needs & POINT_GRAD) ? h.d_kkt_grad.get() : nullptr;
+    if (int rc = nempc_eval(hh, B, Z, X0, nullptr, grad, h.d_g_ws.get(), nullptr, h.d_tiles_ws.get(), nullptr, stream)) return rc;
     // (blocks only: the objective factor, which nempc_hess asks for and only its assembly reads, is not used -- any pointer)
     if (needs & POINT_BLOCKS)
-        if (int rc = nempc_hess(hh, B, Z, X0, lam, lam, nullptr, nullptr, h.d_hess_ws, stream)) return rc;
+        if (int rc = nempc_hess(hh, B, Z, X0, lam, lam, nullptr, nullptr, h.d_hess_ws.get(), stream)) return rc;
     pc.dg.set(h.cfg.device);
     if (!pc.dg.ok) return fail(NEMPC_EHIP, who, ": hipSetDevice failed");
     return NEMPC_OK;
@@ -543,12 +533,10 @@ int nempc_create(const nempc_config* cfg, nempc_handle* out) {
     }
 
     int rc;
-    if ((rc = alloc_batch_workspaces(*h)) || (rc = dev_alloc(&h->d_kkt_bounds, (size_t)2 * h->n * sizeof(double))) ||
-        (rc = rebuild_structure(*h)) ||                                          // (d_g_ws with the maps)
+    if ((rc = rebuild_structure(*h)) ||                                          // (the row count: d_g_ws is sized by it)
+        (rc = alloc_batch_workspaces(*h)) || (rc = h->d_kkt_bounds.alloc((size_t)2 * h->n * sizeof(double), "variable bounds")) ||
         (rc = set_objective(*h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) {
-        std::string keep = g_last_error;
-        destroy_impl(h);
-        set_error(keep);
+        delete h;           // (frees set no error text: the failure's message stands)
         return rc;
     }
     *out = reinterpret_cast<nempc_handle>(h);
@@ -560,7 +548,7 @@ int nempc_destroy(nempc_handle hh) {
     Handle* h = reinterpret_cast<Handle*>(hh);
     DeviceGuard dg(h->cfg.device);
     h->jac_resident.drop_all();
-    destroy_impl(h);
+    delete h;
     return NEMPC_OK;
 }
 
@@ -574,12 +562,9 @@ int nempc_reserve(nempc_handle hh, int32_t max_batch) {
     // an evaluation may still be running out of the old workspaces on some stream
     NEMPC_HIP(hipDeviceSynchronize());
     h.cfg.max_batch = max_batch;
-    rk4hess_free(h);      // sized lazily from max_batch on their next use
     solver_free(h);
-    dev_free(h.d_tiles_ws); dev_free(h.d_valu_ws); dev_free(h.d_hess_ws); dev_free(h.d_g_ws); dev_free(h.d_kkt_grad);
-    dev_free(h.d_sens_ws);
-    int rc = alloc_batch_workspaces(h);
-    if (!rc) rc = dev_alloc(&h.d_g_ws, (size_t)max_batch * h.m * h.esz);
+    for (const BatchWs& w : batch_workspaces(h)) w.buf.reset();
+    const int rc = alloc_batch_workspaces(h);
     if (rc) h.cfg.max_batch = 0;   // workspaces are gone: every evaluation is refused until a reserve succeeds
     return rc;
 }
@@ -589,6 +574,8 @@ int nempc_set_weights(nempc_handle hh, const double* const* W, const double* con
     Handle& h = *reinterpret_cast<Handle*>(hh);
     DeviceGuard dg(h.cfg.device);
     if (!dg.ok) return fail(NEMPC_EHIP, "nempc_set_weights: hipSetDevice failed");
+    // every layer into new buffers first, into the handle only when all of them are up: a failure leaves the previous network
+    DevBuf<> nW[NEMPC_MAX_LAYERS], nWt[NEMPC_MAX_LAYERS], nb[NEMPC_MAX_LAYERS];
     for (int l = 0; l < h.nl; ++l) {
         if (!W[l] || !b[l]) return fail(NEMPC_EINVAL, "nempc_set_weights: null layer pointer");
         const int win = h.din[l], wout = h.dout[l];
@@ -598,17 +585,18 @@ int nempc_set_weights(nempc_handle hh, const double* const* W, const double* con
         for (int i = 0; i < win; ++i)
             for (int j = 0; j < wout; ++j) wt[(size_t)j * win + i] = w[(size_t)i * wout + j];
         int rc;
-        dev_free(h.d_W[l]); dev_free(h.d_Wt[l]); dev_free(h.d_b[l]);
-        if ((rc = dev_alloc(&h.d_W[l], w.size() * h.esz))) return rc;
-        if ((rc = dev_alloc(&h.d_Wt[l], wt.size() * h.esz))) return rc;
-        if ((rc = dev_alloc(&h.d_b[l], bb.size() * h.esz))) return rc;
-        if ((rc = upload(h, w, h.d_W[l]))) return rc;
-        if ((rc = upload(h, wt, h.d_Wt[l]))) return rc;
-        if ((rc = upload(h, bb, h.d_b[l]))) return rc;
+        if ((rc = nW[l].alloc(w.size() * h.esz, "layer weights"))) return rc;
+        if ((rc = nWt[l].alloc(wt.size() * h.esz, "transposed layer weights"))) return rc;
+        if ((rc = nb[l].alloc(bb.size() * h.esz, "layer biases"))) return rc;
+        if ((rc = upload(h, w, nW[l].get()))) return rc;
+        if ((rc = upload(h, wt, nWt[l].get()))) return rc;
+        if ((rc = upload(h, bb, nb[l].get()))) return rc;
     }
-    if (h.variant != NEMPC_KERNEL_VALU) {
-        int rc = mfma_pack_weights(h, W, b);
-        if (rc) return rc;
+    // (the packed copy of the matrix-core kernels likewise: it replaces the old one only once it is up, and nothing after it fails)
+    if (h.variant != NEMPC_KERNEL_VALU)
+        if (int rc = mfma_pack_weights(h, W, b)) return rc;
+    for (int l = 0; l < h.nl; ++l) {
+        h.d_W[l] = std::move(nW[l]); h.d_Wt[l] = std::move(nWt[l]); h.d_b[l] = std::move(nb[l]);
     }
     h.have_weights = true;
     h.layered_pairs_valid = false;      // (the layered Hessian's table of first-layer weight products follows the weights)
@@ -726,7 +714,9 @@ int nempc_set_box_rows(nempc_handle hh, int enabled, const double* lo, const dou
         h.box_lo.assign(lo, lo + h.cfg.nx);
         h.box_hi.assign(hi, hi + h.cfg.nx);
     }
-    return rebuild_structure(h);
+    h.d_g_ws.reset();       // (its row count changes: no buffer of the old one behind a failure)
+    if (int rc = rebuild_structure(h)) return rc;
+    return h.d_g_ws.alloc(g_ws_bytes(h), "defect workspace");
 }
 
 int nempc_jac_dense_resident(nempc_handle hh, void* jac, int32_t B) {
@@ -817,8 +807,8 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
     h.last_dense_writer = DENSE_WRITER_NONE;
     int rc;
     if (need_rows && h.variant == NEMPC_KERNEL_VALU) {
-        void* tiles = jac_tiles ? jac_tiles : h.d_tiles_ws;
-        if ((rc = launch_rows_valu(h, B, Z, X0, g ? g : h.d_g_ws, tiles, s))) return rc;
+        void* tiles = jac_tiles ? jac_tiles : h.d_tiles_ws.get();
+        if ((rc = launch_rows_valu(h, B, Z, X0, g ? g : h.d_g_ws.get(), tiles, s))) return rc;
         // sparse contract with the objective and without the dense matrix: one fused launch
         if (jac_sparse && !jac_dense && (ff || gf)) return launch_post_sparse(h, B, tiles, jac_sparse, Z, ff, gf, s);
         if (jac_sparse && (rc = launch_assemble_sparse(h, B, tiles, jac_sparse, s))) return rc;
@@ -834,13 +824,13 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
         // cooperative kernel all the same: correct, and measured not worth a flag in rows_coop_kernel -- DESIGN 5.2.)
         // Defects only (IpoptProblem.constraints on its own): the matrix-core kernel skips its reverse sweeps.
         RowsOut ro;
-        ro.g = g ? g : h.d_g_ws; ro.tiles = jac_tiles; ro.need_tiles = jac_dense || jac_sparse;
+        ro.g = g ? g : h.d_g_ws.get(); ro.tiles = jac_tiles; ro.need_tiles = jac_dense || jac_sparse;
         ro.jac = jac_dense; ro.sparse = jac_sparse; ro.f = ff; ro.grad = gf; ro.jac_resident = jres;
         unsigned covers = 0;
         if ((rc = launch_rows_mfma(h, B, Z, X0, ro, s, &covers))) return rc;
         if (covers & COVERS_DENSE) h.last_dense_writer = DENSE_WRITER_ROWS;
         // what the launch left over: assembly, post, objective
-        const void* tiles = jac_tiles ? jac_tiles : h.d_tiles_ws;
+        const void* tiles = jac_tiles ? jac_tiles : h.d_tiles_ws.get();
         const bool obj_left = (ff || gf) && !(covers & COVERS_OBJ);
         const bool dense_left = jac_dense && !(covers & COVERS_DENSE), sparse_left = jac_sparse && !(covers & COVERS_SPARSE);
         // sparse contract with the objective and without the dense matrix: one fused launch
@@ -866,7 +856,7 @@ int nempc_hess(nempc_handle hh, int32_t B, const void* Z, const void* X0, const 
     if (!dg.ok) return fail(NEMPC_EHIP, "nempc_hess: hipSetDevice failed");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int rc;
-    void* blocks = hblocks ? hblocks : h.d_hess_ws;
+    void* blocks = hblocks ? hblocks : h.d_hess_ws.get();
     unsigned covers = 0;
     if (h.variant == NEMPC_KERNEL_VALU) rc = launch_rowhess_valu(h, B, Z, X0, lambda, blocks, s);
     else if (h.cfg.integrator == NEMPC_RK4) {
@@ -900,16 +890,16 @@ int nempc_hess_gn(nempc_handle hh, int32_t B, const void* Z, const void* X0, con
     int rc;
     if (h.variant != NEMPC_KERNEL_VALU) {
         RowsOut ro;
-        ro.g = h.d_g_ws; ro.tiles = h.d_tiles_ws;
+        ro.g = h.d_g_ws.get(); ro.tiles = h.d_tiles_ws.get();
         if (hvals && !hdense && !hblocks) { ro.gn_hvals = hvals; ro.gn_w = w; ro.gn_sigma = sigma; }
         unsigned covers = 0;
         rc = launch_rows_mfma(h, B, Z, X0, ro, s, &covers);
         if (rc == NEMPC_OK && (covers & COVERS_GN)) return rc;
-    } else rc = launch_rows_valu(h, B, Z, X0, h.d_g_ws, h.d_tiles_ws, s);
+    } else rc = launch_rows_valu(h, B, Z, X0, h.d_g_ws.get(), h.d_tiles_ws.get(), s);
     if (rc) return rc;
     // the caller does not ask for the per-row blocks: the assembly forms their elements where it uses them
-    if (!hblocks) return (hvals || hdense) ? launch_assemble_hess_gn(h, B, h.d_tiles_ws, w, sigma, hvals, hdense, s) : NEMPC_OK;
-    if ((rc = launch_gn_blocks(h, B, h.d_tiles_ws, w, hblocks, s))) return rc;
+    if (!hblocks) return (hvals || hdense) ? launch_assemble_hess_gn(h, B, h.d_tiles_ws.get(), w, sigma, hvals, hdense, s) : NEMPC_OK;
+    if ((rc = launch_gn_blocks(h, B, h.d_tiles_ws.get(), w, hblocks, s))) return rc;
     if (!hvals && !hdense) return NEMPC_OK;
     return launch_assemble_hess(h, B, hblocks, sigma, hvals, hdense, s);
 }
@@ -978,7 +968,7 @@ int nempc_kkt_residual(nempc_handle hh, int32_t B, const void* Z, const void* X0
     PointCall pc;
     if (int rc = point_prepare(hh, who, POINT_GRAD, B, Z, X0, lam, lb, ub, stream, pc)) return rc;
     Handle& h = *reinterpret_cast<Handle*>(hh);
-    return launch_kkt_residual(h, B, Z, h.d_kkt_grad, h.d_g_ws, h.d_tiles_ws, lam, zl, zu, pc.dlb, pc.dub, r, stat, pc.s);
+    return launch_kkt_residual(h, B, Z, h.d_kkt_grad.get(), h.d_g_ws.get(), h.d_tiles_ws.get(), lam, zl, zu, pc.dlb, pc.dub, r, stat, pc.s);
 }
 
 int nempc_sensitivity(nempc_handle hh, int32_t B, const void* Z, const void* X0, const void* lam, const void* zl,
@@ -996,7 +986,7 @@ int nempc_sensitivity(nempc_handle hh, int32_t B, const void* Z, const void* X0,
     PointCall pc;
     if (int rc = point_prepare(hh, who, POINT_TRACKING | POINT_BLOCKS, B, Z, X0, lam, lb, ub, stream, pc)) return rc;
     Handle& h = *reinterpret_cast<Handle*>(hh);
-    return launch_sensitivity(h, B, Z, h.d_tiles_ws, h.d_hess_ws, zl, zu, pc.dlb, pc.dub, dU0, dZ, dlam, gains, status, pc.s);
+    return launch_sensitivity(h, B, Z, h.d_tiles_ws.get(), h.d_hess_ws.get(), zl, zu, pc.dlb, pc.dub, dU0, dZ, dlam, gains, status, pc.s);
 }
 
 int nempc_kkt_solve(nempc_handle hh, int32_t B, const void* Z, const void* X0, const void* lam, const void* zl,
@@ -1015,7 +1005,7 @@ int nempc_kkt_solve(nempc_handle hh, int32_t B, const void* Z, const void* X0, c
     PointCall pc;
     if (int rc = point_prepare(hh, who, POINT_TRACKING | POINT_BLOCKS, B, Z, X0, lam, lb, ub, stream, pc)) return rc;
     Handle& h = *reinterpret_cast<Handle*>(hh);
-    return launch_kkt_solve(h, B, Z, h.d_tiles_ws, h.d_hess_ws, zl, zu, pc.dlb, pc.dub, nrhs, rz, rg, v, w, gx0, status, pc.s);
+    return launch_kkt_solve(h, B, Z, h.d_tiles_ws.get(), h.d_hess_ws.get(), zl, zu, pc.dlb, pc.dub, nrhs, rz, rg, v, w, gx0, status, pc.s);
 }
 
 int nempc_n_params(nempc_handle hh, int64_t* P) {
@@ -1107,12 +1097,12 @@ int nempc_debug_stamps(nempc_handle hh, long long* host_out) {
     Handle& h = *reinterpret_cast<Handle*>(hh);
     DeviceGuard dg(h.cfg.device);
     if (!h.d_dbg) {
-        NEMPC_HIP(hipMalloc((void**)&h.d_dbg, sizeof(long long) * NEMPC_DBG_WORDS));
-        NEMPC_HIP(hipMemset(h.d_dbg, 0, sizeof(long long) * NEMPC_DBG_WORDS));
+        if (int rc = h.d_dbg.alloc(sizeof(long long) * NEMPC_DBG_WORDS, "stamp buffer")) return rc;
+        NEMPC_HIP(hipMemset(h.d_dbg.get(), 0, sizeof(long long) * NEMPC_DBG_WORDS));
         return NEMPC_OK;
     }
     NEMPC_HIP(hipDeviceSynchronize());
-    NEMPC_HIP(hipMemcpy(host_out, h.d_dbg, sizeof(long long) * NEMPC_DBG_WORDS, hipMemcpyDeviceToHost));
+    NEMPC_HIP(hipMemcpy(host_out, h.d_dbg.get(), sizeof(long long) * NEMPC_DBG_WORDS, hipMemcpyDeviceToHost));
     return NEMPC_OK;
 }
 #endif

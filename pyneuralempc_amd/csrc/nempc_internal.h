@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_buf.h"          // DevBuf: every device allocation a Handle owns
 #include "jac_resident.h"
 #include "mfma_plan.h"
 #include "obj_offsets.h"      // ObjOffsets / obj_offsets: the objective table's layout
@@ -37,13 +38,6 @@ inline bool env_set(const char* name) { return getenv(name) != nullptr; }       
         hipError_t _e = (call);                                    \
         if (_e != hipSuccess) return ::nempc::hip_fail(_e, #call); \
     } while (0)
-
-// frees a device allocation and nulls the pointer that named it (so that no later free sees the address again)
-template <class P>
-void dev_free(P*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
 
 // How one (problem, step) row reads its network inputs: plain models read [x_{t-1} | u_t]; rolling-window models
 // (model/tensorflow.py:112-130 rolling_input) read the last w states and controls, reaching into x0 and the bound
@@ -112,8 +106,7 @@ struct MfmaNet {
     int nh = 0;        // hidden layers
     int kin = 0;       // padded input width (multiple of 4)
     int ldw = 0;       // leading dimension (elements) of every packed matrix
-    void* blob = nullptr;  // device, dtype T; see kernels_mfma.hip for the layout
-    size_t blob_elems = 0;
+    DevBuf<> blob;     // device, dtype T; see kernels_mfma.hip for the layout
 };
 
 struct ObjHost {   // host copy of the objective parameters (doubles), re-uploaded whenever one of them changes
@@ -148,7 +141,11 @@ struct RateBind {
     bool on() const { return u_prev != nullptr; }
 };
 
+// Device memory: every allocation the handle owns is a DevBuf member (dev_buf.h) and goes with the handle; a new workspace is
+// one more member and nothing else.  What a caller bound (d_extra, d_hist_*, the bindings, jac_resident's entries) stays a
+// raw pointer.  solver_ws and comm are opaque to everyone but their units, which free them (solver_free, comm_free).
 struct Handle {
+    ~Handle();                   // (nempc_api.hip: solver_free, comm_free; the members free themselves)
     nempc_config cfg{};
     int num_cus = 256;           // compute units of cfg.device (nempc_create)
     size_t lds_limit = 65536;    // LDS a workgroup of cfg.device may ask for (hipDeviceProp_t::sharedMemPerBlock, nempc_create)
@@ -186,14 +183,13 @@ struct Handle {
     size_t esz = 8;
 
     // network, dtype T on device. W[l] (in,out) row-major; Wt[l] (out,in) row-major
-    void* d_W[NEMPC_MAX_LAYERS]{};
-    void* d_Wt[NEMPC_MAX_LAYERS]{};
-    void* d_b[NEMPC_MAX_LAYERS]{};
+    DevBuf<> d_W[NEMPC_MAX_LAYERS];
+    DevBuf<> d_Wt[NEMPC_MAX_LAYERS];
+    DevBuf<> d_b[NEMPC_MAX_LAYERS];
     MfmaNet mfma;
 
     // objective, dtype T: Q, Qs=Q+Q^T, R, Rs, xref, uref, cx, cu, QT, QTs (one allocation) + Hessian constants
-    void* d_obj = nullptr;
-    size_t obj_elems = 0;        // elements of d_obj (a change of values overwrites it in place)
+    DevBuf<> d_obj;              // (a change of values overwrites it in place)
     bool hess_maps_built = false;   // the Hessian structure / maps depend on the shape only: built once per handle
     ObjHost obj_host;            // last nempc_set_objective arguments (defaults filled in)
     std::vector<double> obj_QT;  // terminal state weight (host copy; empty = same as Q), nempc_set_terminal_weight
@@ -202,41 +198,40 @@ struct Handle {
 
     // structure (host) + assembly maps (device)
     std::vector<int32_t> jac_rows, jac_cols, hess_rows, hess_cols;
-    int32_t* d_dense_map = nullptr;   // (m*n)
-    int32_t* d_sparse_map = nullptr;  // (nnz_jac)
-    int32_t* d_sparse_pos = nullptr;  // (nnz_jac) where each structural non-zero sits in one problem's dense matrix: row * n + col
+    DevBuf<int32_t> d_dense_map;      // (m*n)
+    DevBuf<int32_t> d_sparse_map;     // (nnz_jac)
+    DevBuf<int32_t> d_sparse_pos;     // (nnz_jac) where each structural non-zero sits in one problem's dense matrix: row * n + col
     JacResidentTable jac_resident;    // dense-Jacobian buffers whose structural zeros are in place (nempc_jac_dense_resident)
-    int32_t* d_hess_map = nullptr;    // (nnz_hess + n*n, w) per-row block elements summed into each entry; -1 = none
-    int32_t* d_hess_smap = nullptr;   // plain models: (H*nin*nin) block element -> tril entry (-1 none), then the entries no
+    DevBuf<int32_t> d_hess_map;       // (nnz_hess + n*n, w) per-row block elements summed into each entry; -1 = none
+    DevBuf<int32_t> d_hess_smap;      // plain models: (H*nin*nin) block element -> tril entry (-1 none), then the entries no
     int hess_n_orph = -1;             //   block reaches (hess_n_orph of them; -1: no fused assembly for this handle)
 
-    // workspaces sized for max_batch
-    void* d_tiles_ws = nullptr;  // (Bmax,H,nx,nin) when the caller does not ask for tiles
-    void* d_g_ws = nullptr;      // (Bmax,m) when the caller does not ask for g
-    void* d_valu_ws = nullptr;   // scratch of the generic row kernel
-    size_t valu_ws_elems = 0;
-    void* d_hess_ws = nullptr;   // (Bmax,H,nin,nin) per-row Lagrangian blocks
-    void* d_kkt_grad = nullptr;  // (Bmax,n) objective gradient of nempc_kkt_residual's evaluation (tiles / g: the two above)
-    double* d_kkt_bounds = nullptr;          // (2,n) doubles: lb | ub of the last nempc_kkt_residual, +-inf kept
+    // workspaces sized for max_batch (batch_workspaces, nempc_api.hip, names the ones nempc_reserve empties)
+    DevBuf<> d_tiles_ws;         // (Bmax,H,nx,nin) when the caller does not ask for tiles
+    DevBuf<> d_g_ws;             // (Bmax,m) when the caller does not ask for g
+    DevBuf<> d_valu_ws;          // scratch of the generic row kernel
+    DevBuf<> d_hess_ws;          // (Bmax,H,nin,nin) per-row Lagrangian blocks
+    DevBuf<> d_kkt_grad;         // (Bmax,n) objective gradient of nempc_kkt_residual's evaluation (tiles / g: the two above)
+    DevBuf<double> d_kkt_bounds;             // (2,n) doubles: lb | ub of the last nempc_kkt_residual, +-inf kept
     std::vector<double> kkt_bounds_host;     // ... as last uploaded (empty: nothing uploaded yet)
-    double* d_sens_ws = nullptr;             // nempc_sensitivity (plain models): gains | value matrices | Sigma | scratch (sens_ws_doubles)
-    double* d_kktsolve_ws = nullptr;         // nempc_kkt_solve: per-problem global working sets, when its plan needs them
-    size_t kktsolve_ws_doubles = 0;          //   (allocated and grown by the call itself, kernels_kktsolve.hip)
-    void* d_wgrad_ws = nullptr;              // nempc_weight_grad: factor matrices | sweep scratch | slabs | kept-problem list
-    size_t wgrad_ws_bytes = 0;               //   (allocated and grown by the call itself, kernels_wgrad.hip)
-    void* d_egrad_ws = nullptr;              // nempc_extra_grad: s', s'' z. of the resident workgroups, when its plan keeps them
-    size_t egrad_ws_bytes = 0;               //   outside LDS (allocated by the call itself, kernels_egrad.hip)
-    void* d_rk4_stage = nullptr; // RK4 Hessian pipeline (allocated on first use): (Bmax*H, 4, nin + 2*nx*nin) stage records,
-    void* d_rk4_nu = nullptr;    //   (Bmax*H, 4, nx) stage multipliers,
-    void* d_rk4_ht = nullptr;    //   (Bmax*H, 4, nin, nin) contracted stage Hessians
-    long long* d_dbg = nullptr;  // diagnostic builds only
+    DevBuf<> d_sens_ws;                      // nempc_sensitivity (plain models), doubles: gains | value matrices | Sigma | scratch (sens_ws_doubles)
+    DevBuf<> d_kktsolve_ws;                  // nempc_kkt_solve, doubles: per-problem global working sets, when its plan needs them
+                                             //   (allocated and grown by the call itself, kernels_kktsolve.hip)
+    DevBuf<> d_wgrad_ws;                     // nempc_weight_grad: factor matrices | sweep scratch | slabs | kept-problem list
+                                             //   (allocated and grown by the call itself, kernels_wgrad.hip)
+    DevBuf<> d_egrad_ws;                     // nempc_extra_grad: s', s'' z. of the resident workgroups, when its plan keeps them
+                                             //   outside LDS (allocated by the call itself, kernels_egrad.hip)
+    DevBuf<> d_rk4_stage;        // RK4 Hessian pipeline (allocated on first use): (Bmax*H, 4, nin + 2*nx*nin) stage records,
+    DevBuf<> d_rk4_nu;           //   (Bmax*H, 4, nx) stage multipliers,
+    DevBuf<> d_rk4_ht;           //   (Bmax*H, 4, nin, nin) contracted stage Hessians
+    DevBuf<long long> d_dbg;     // diagnostic builds only
     bool layered = false;        // rows through the layer-at-a-time GEMM pipeline (kernels_layered.hip) instead of rows_valu_kernel
-    void* d_layered_ws = nullptr;   // its chunk workspace (allocated on first use)
+    DevBuf<> d_layered_ws;          // its chunk workspace (allocated on first use)
     long long layered_chunk_rows = 0;
-    void* d_layered_hws = nullptr;  // chunk workspace of its Hessian sweeps (allocated on first use)
+    DevBuf<> d_layered_hws;         // chunk workspace of its Hessian sweeps (allocated on first use)
     long long layered_hess_chunk_rows = 0;
     bool layered_hess = false;          // a register-resident (MFMA) handle whose Lagrangian blocks come from the layered sweeps (mfma_hess_on_layered)
-    void* d_layered_pairs = nullptr;    // (dout[0], nin (nin + 1) / 2): W_0[p][n] W_0[q][n], p >= q (layer 0's curvature term)
+    DevBuf<> d_layered_pairs;           // (dout[0], nin (nin + 1) / 2): W_0[p][n] W_0[q][n], p >= q (layer 0's curvature term)
     bool layered_pairs_valid = false;
     void* solver_ws = nullptr;   // solver.hip
     void* comm = nullptr;        // comm.hip: RCCL communicator of the u0 all-gather
@@ -271,7 +266,6 @@ int launch_rows_layered_stages(Handle& h, int B, const void* Z, const void* X0, 
 // kernels_rk4hess.hip: the RK4 pipeline with the layered launches as steps 1 and 3
 int launch_rowhess_rk4_layered(Handle& h, int B, const void* Z, const void* X0, const void* lambda, void* blocks, hipStream_t s,
                                void* g_out, void* tiles_out);
-void layered_free(Handle& h);
 
 // ---- kernels_rollout.hip : forward simulation x_t = Phi(x_{t-1}, u_t), serial in t, parallel in B
 bool rollout_mfma_supported(const Handle& h);
@@ -310,14 +304,12 @@ MfmaHessPlan mfma_plan_hess(const Handle& h, int B, const HessOut& out);
 int launch_rows_mfma(Handle& h, int B, const void* Z, const void* X0, const RowsOut& out, hipStream_t s, unsigned* covers = nullptr);
 int launch_rowhess_mfma(Handle& h, int B, const void* Z, const void* X0, const void* lambda, const HessOut& out, hipStream_t s,
                         unsigned* covers = nullptr);
-void mfma_free(Handle& h);
 
 // ---- kernels_rk4hess.hip : RK4 Lagrangian blocks on the matrix cores (stage records -> stage multipliers ->
 //      contracted network Hessians of the four stage inputs -> congruence sum)
 bool rk4hess_supported(const Handle& h);     // a wave's slice of the congruence step fits the device's LDS (else: generic kernel)
 int launch_rowhess_rk4_mfma(Handle& h, int B, const void* Z, const void* X0, const void* lambda, void* blocks,
                             hipStream_t s, void* g_out = nullptr, void* tiles_out = nullptr);
-void rk4hess_free(Handle& h);
 
 // ---- kernels_post.hip : objective, dense / sparse assembly, hessian assembly
 int launch_objective(Handle& h, int B, const void* Z, void* f, void* grad, hipStream_t s);   // (the binding's kernel when one is present)
@@ -349,13 +341,12 @@ int launch_sensitivity(Handle& h, int B, const void* Z, const void* tiles, const
                        hipStream_t s);
 
 // ---- kernels_kktsolve.hip : KKT solves with caller-supplied right-hand sides (nempc_kkt_solve)
-size_t kktsolve_ws_doubles(const Handle& h, size_t Bmax, int nrhs);   // elements of Handle::d_kktsolve_ws (0: the plan is on-chip)
+size_t kktsolve_ws_doubles(const Handle& h, size_t Bmax, int nrhs);   // doubles of Handle::d_kktsolve_ws (0: the plan is on-chip)
 // as launch_sensitivity, with rz (B,nrhs,n), rg (B,nrhs,H nx) or null and the outputs of nempc_kkt_solve (each may be null).
 // Uses Handle::d_sens_ws for the gains, value matrices and Sigma; grows Handle::d_kktsolve_ws (a device synchronisation)
 int launch_kkt_solve(Handle& h, int B, const void* Z, const void* tiles, const void* blocks, const void* zl, const void* zu,
                      const double* lb, const double* ub, int nrhs, const void* rz, const void* rg, void* v, void* w, void* gx0,
                      int32_t* status, hipStream_t s);
-void kktsolve_free(Handle& h);
 
 // ---- kernels_wgrad.hip : gradient with respect to the network's weights (nempc_weight_grad)
 long long wgrad_n_params(const Handle& h);
@@ -363,14 +354,12 @@ long long wgrad_n_params(const Handle& h);
 // synchronisation) when the plan needs more than it holds
 int launch_weight_grad(Handle& h, int B, const void* Z, const void* X0, const void* lam, const void* v, const void* w,
                        const int32_t* skip, void* gtheta, hipStream_t s);
-void wgrad_free(Handle& h);
 
 // ---- kernels_egrad.hip : gradient with respect to the extra network inputs (nempc_extra_grad)
 // lam / v both or neither; gE (B,H,ne) is overwritten.  Allocates Handle::d_egrad_ws (a device synchronisation) when the plan
 // keeps the saved activation derivatives outside LDS
 int launch_extra_grad(Handle& h, int B, const void* Z, const void* X0, const void* lam, const void* v, const void* w, void* gE,
                       hipStream_t s);
-void egrad_free(Handle& h);
 
 // ---- solver.hip : batched Gauss-Newton SQP (host driver; its kernels are in solver_args.h and the solver_*_impl.h headers,
 // which only solver.hip includes)

@@ -388,7 +388,7 @@ struct Solve {
             h.d_extra = ws.exc[0];
             h.extra_B = B;
         }
-        const void *Zstart = Z, *X0start = X0, *obj_dev = h.d_obj;
+        const void *Zstart = Z, *X0start = X0, *obj_dev = h.d_obj.get();
         if (augmented) {
             if ((rc = aug.start(Z, X0, ws.lb, ws.ub, (T)o.mu_init, has_bounds ? 1 : 0, gBn))) return rc;
             Zstart = ws.aug.rZin; X0start = ws.aug.rS0; obj_dev = ws.aug.robj;
@@ -642,7 +642,7 @@ struct Solve {
                 if (!fused_trial) {
                     const RowsOut ro = fused_eval_out(ws.gt, nullptr, ws.ft, nullptr);
                     fused_trial = h.variant == NEMPC_KERNEL_MFMA && !tracking && has_fused_eval(nb, ro);
-                    rc = fused_trial ? launch_rows_mfma(h, nb, ws.Zt, X0t, ro, s) : launch_rows(nb, ws.Zt, X0t, ws.gt, nullptr, h.d_tiles_ws);
+                    rc = fused_trial ? launch_rows_mfma(h, nb, ws.Zt, X0t, ro, s) : launch_rows(nb, ws.Zt, X0t, ws.gt, nullptr, h.d_tiles_ws.get());
                 }
             }
             h.d_extra = extra_all;
@@ -674,7 +674,7 @@ struct Solve {
                                    (const T*)ws.gt, (const T*)ws.tiles, (const T*)X0c, (const T*)extra_all, (T*)ws.Zsoc, (T*)ws.X0p,
                                    (T*)ws.exp_, a.n_pending);
                 if (ex_per) h.d_extra = ws.exp_;
-                rc = launch_rows(pending, ws.Zsoc, ws.X0p, ws.gsoc, nullptr, h.d_tiles_ws);
+                rc = launch_rows(pending, ws.Zsoc, ws.X0p, ws.gsoc, nullptr, h.d_tiles_ws.get());
                 h.d_extra = extra_all;
                 if (rc) return rc;
                 hipLaunchKernelGGL(solver_merit_kernel<T>, dim3(pending), dim3(64), 0, s, a, (const T*)ws.Zsoc, (const T*)ws.gsoc,

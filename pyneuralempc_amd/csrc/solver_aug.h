@@ -138,7 +138,7 @@ struct StageAug {
                                (T*)w.rZ, (const T*)lam_aug, lam_r);
             break;
         }
-        int r = callback_rows(h, B, w.rZ, X0, w.rg, full ? w.rtiles : nullptr, h.d_tiles_ws, s);
+        int r = callback_rows(h, B, w.rZ, X0, w.rg, full ? w.rtiles : nullptr, h.d_tiles_ws.get(), s);
         if (r) return r;
         if (full && (r = callback_blocks(h, B, w.rZ, X0, w.rlam, w.rhblk, s))) return r;
         if (full && kind == AUG_WINDOW && (r = launch_objective(h, B, w.rZ, f, w.rgrad, s))) return r;
