@@ -244,6 +244,33 @@ int nempc_bind_bounds(nempc_handle h, const void* xlb, const void* xub, const vo
 int nempc_bind_rate(nempc_handle h, const double* S, const double* dlo, const double* dhi, int32_t per_stage,
                     const void* u_prev, int32_t B);
 
+/* linear stage inequality rows for subsequent nempc_solve calls.  With C = [Cx (nc,nx) | Cu (nc,nu)] shared by every problem
+ * and every step, the solve becomes
+ *    min f(z)    s.t. defects = 0,  lb <= z <= ub (as without the binding),  rlo_t <= Cx x_t + Cu u_t <= rhi_t,  t = 0 .. H-1
+ * Pairing: row block t pairs ROW t of the state block of z with ROW t of its control block -- z = [x rows (H,nx) | u rows
+ * (H,nu)], state row t being the state the t-th step arrives at, Phi(state row t-1, control row t).  It is the pairing of the
+ * reference's Constraint.forward(x, u) on its (H,nx) and (H,nu) arguments and of nempc_bind_bounds (row t of the x arrays
+ * bounds x_t): state-only rows (Cu = 0) cover every state variable, control-only rows (Cx = 0) every control; x0 is data and
+ * no row reads it.
+ *   nc        rows per stage; nc == 0 or C == NULL removes the binding; nc < 0 is NEMPC_EINVAL;
+ *   C         (nc, nx+nu) host doubles, row-major, copied (a non-finite entry is NEMPC_EINVAL);
+ *   rlo, rhi  host doubles, copied: (nc) when per_stage == 0 (every step), (H,nc) when per_stage == 1; NULL or -+INFINITY = no
+ *             limit on that side.  rlo >= rhi on any entry, or a NaN, is NEMPC_EINVAL (the barrier needs an interior: the rule
+ *             of lb == ub; equality rows are not built).
+ * The solver runs the problem stage-wise in the state [x_t ; y_t], y_t = Cx x_t + Cu u_t, with the rows as variable bounds of
+ * y; the returned Z is the x and u of that problem.  Feasibility: at convergence (status 0) every row holds to
+ * tol_constraint * (1 + |Cx row|_1) -- y is strictly inside its limits and both defect families, x_t - Phi and y_t - Cx Phi -
+ * Cu u_t, are below tol_constraint.  The Levenberg term of nempc_solver_opts.reg stays on u.  The products with C accumulate
+ * in the handle's dtype in a fixed order: a solve is bitwise reproducible.
+ * nempc_eval, nempc_hess / nempc_hess_gn and nempc_rollout do not read the binding: they evaluate the plain problem, their
+ * outputs unchanged to the bit.
+ * While a binding is on, these are NEMPC_EUNSUPPORTED, each with a nempc_last_error text that names the call, and the handle
+ * stays usable: nempc_solve_duals with a non-NULL lam, zl or zu; nempc_kkt_residual, nempc_sensitivity and nempc_kkt_solve (they
+ * would certify or differentiate a different problem; the multipliers of the rows are left to a later change); nempc_solve
+ * together with a rate binding (nempc_bind_rate), a tracking binding (nempc_bind_tracking) or per-problem bounds
+ * (nempc_bind_bounds).  On a rolling_window > 1 handle the call itself is NEMPC_EUNSUPPORTED. */
+int nempc_bind_stage_rows(nempc_handle h, int32_t nc, const double* C, const double* rlo, const double* rhi, int32_t per_stage);
+
 /* extra constraint rows g_box = states.ravel() (a Constraint in the sense of constraints.py:36-63
  * with constant selector Jacobian); lo/hi (nx) host doubles are only reported back through
  * nempc_constraint_bounds. enabled=0 removes the rows. */

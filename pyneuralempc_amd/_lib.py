@@ -43,7 +43,7 @@ def split_activation(spec):
     return name, par
 
 EXPORTS = ["nempc_create", "nempc_destroy", "nempc_reserve", "nempc_set_weights", "nempc_set_objective", "nempc_set_terminal_weight", "nempc_set_box_rows", "nempc_bind_extra", "nempc_bind_history",
-           "nempc_bind_tracking", "nempc_bind_bounds", "nempc_bind_rate",
+           "nempc_bind_tracking", "nempc_bind_bounds", "nempc_bind_rate", "nempc_bind_stage_rows",
            "nempc_jac_dense_resident",
            "nempc_dims", "nempc_constraint_bounds", "nempc_jac_structure", "nempc_hess_structure", "nempc_eval",
            "nempc_hess", "nempc_hess_gn", "nempc_solve", "nempc_solve_duals", "nempc_kkt_residual", "nempc_sensitivity", "nempc_kkt_solve", "nempc_n_params", "nempc_weight_grad", "nempc_extra_grad", "nempc_last_extra_grad_kernel", "nempc_rollout", "nempc_last_rollout_kernel", "nempc_sync", "nempc_kernel_variant", "nempc_last_row_kernel", "nempc_last_dense_writer", "nempc_last_hess_kernel", "nempc_last_lq_kernel", "nempc_last_error", "nempc_abi_version",
@@ -104,6 +104,10 @@ def load():
     have_rate = hasattr(lib, "nempc_bind_rate")
     if have_rate:
         lib.nempc_bind_rate.argtypes = [vp, dp, dp, dp, i32, vp, i32]
+    # (likewise the stage rows: CallbackEngine.bind_rows says so)
+    have_rows = hasattr(lib, "nempc_bind_stage_rows")
+    if have_rows:
+        lib.nempc_bind_stage_rows.argtypes = [vp, i32, dp, dp, dp, i32]
     # (an older library of the same ABI loaded through NEMPC_LIB -- the parent side of an A/B -- has no such export: the
     # engine then registers nothing and every evaluation writes the full matrix, which is what that library does anyway)
     have_resident = hasattr(lib, "nempc_jac_dense_resident")
@@ -155,7 +159,8 @@ def load():
         if name != "nempc_last_error" and (name != "nempc_jac_dense_resident" or have_resident) and \
                 (name not in ("nempc_n_params", "nempc_weight_grad") or have_wgrad) and \
                 (name not in ("nempc_extra_grad", "nempc_last_extra_grad_kernel") or have_egrad) and \
-                (name != "nempc_last_dense_writer" or have_writer) and (name != "nempc_bind_rate" or have_rate):
+                (name != "nempc_last_dense_writer" or have_writer) and (name != "nempc_bind_rate" or have_rate) and \
+                (name != "nempc_bind_stage_rows" or have_rows):
             getattr(lib, name).restype = ctypes.c_int
     if lib.nempc_abi_version() != ABI_VERSION:
         raise RuntimeError("libnempc.so ABI version mismatch; rebuild it")

@@ -130,3 +130,85 @@ class BoxStateConstraint(Constraint):
 
     def get_upper_bounds(self, H):
         return np.tile(self.hi, H)
+
+
+class LinearStageConstraint(Constraint):
+    """Linear stage rows lo <= Cx x_t + Cu u_t <= hi for every step t of the horizon, C = [Cx (nc,nx) | Cu (nc,nu)]: a shared
+    actuator budget, a polytopic state set, a mixed limit.  Row block t pairs row t of the (H,nx) states with row t of the (H,nu)
+    controls -- the arguments of forward -- so state row t is the state the t-th step arrives at (x0 is data and no row reads
+    it).  lo / hi: (nc,) for every step or (H,nc) per step, a scalar for all rows, None or -+inf = no limit on that side;
+    lo < hi on every entry (equality rows are not built).  A full Constraint for the host glue (Ipopt, SLSQP); the batched
+    device solver takes it as it is (NMPC.next_batch, NMPC.closed_loop_batch, DeviceSqp; CallbackEngine.bind_rows)."""
+
+    def __init__(self, C, lo=None, hi=None):
+        C = np.asarray(C, dtype=np.float64)
+        if C.ndim != 2 or C.shape[0] < 1 or not np.isfinite(C).all():
+            raise ValueError(f"C must be a finite (nc, nx+nu) matrix with nc >= 1, got shape {C.shape}")
+        nc = C.shape[0]
+        lims = []
+        for name, v, fill in (("lo", lo, -np.inf), ("hi", hi, np.inf)):
+            a = np.full(nc, fill) if v is None else np.asarray(v, dtype=np.float64)
+            if a.ndim == 0:
+                a = np.full(nc, float(a))
+            if a.ndim not in (1, 2) or a.shape[-1] != nc:
+                raise ValueError(f"{name} must have shape {(nc,)} (every step) or (H, {nc}) (per step), got {a.shape}")
+            if np.isnan(a).any():
+                raise ValueError(f"{name} has a NaN")
+            lims.append(a)
+        lo, hi = lims
+        if lo.ndim != hi.ndim:      # one form
+            lo, hi = np.broadcast_arrays(lo, hi)
+        if lo.shape != hi.shape:
+            raise ValueError(f"lo {lo.shape} and hi {hi.shape} do not cover the same steps")
+        if (lo >= hi).any():
+            raise ValueError("lo >= hi on some entry (equality or empty rows are not supported: the solver's barrier needs an interior)")
+        self.C, self.lo, self.hi = np.ascontiguousarray(C), np.ascontiguousarray(lo), np.ascontiguousarray(hi)
+
+    @property
+    def nc(self):
+        return self.C.shape[0]
+
+    def _split_C(self, x, u):
+        x, u = np.asarray(x, dtype=np.float64), np.asarray(u, dtype=np.float64)
+        if x.ndim != 2 or u.ndim != 2 or x.shape[0] != u.shape[0] or x.shape[1] + u.shape[1] != self.C.shape[1]:
+            raise ValueError(f"C has {self.C.shape[1]} columns: x (H,nx) and u (H,nu) must have nx + nu of them, "
+                             f"got {x.shape} and {u.shape}")
+        return x, u, self.C[:, :x.shape[1]], self.C[:, x.shape[1]:]
+
+    def forward(self, x, u, p=None, tvp=None):
+        x, u, Cx, Cu = self._split_C(x, u)
+        return (x @ Cx.T + u @ Cu.T).reshape(-1)
+
+    def jacobian(self, x, u, p=None, tvp=None):
+        x, u, Cx, Cu = self._split_C(x, u)
+        (H, nx), nu, nc = x.shape, u.shape[1], self.nc
+        J = np.zeros((H * nc, H * (nx + nu)))
+        for t in range(H):
+            J[t * nc:(t + 1) * nc, t * nx:(t + 1) * nx] = Cx
+            J[t * nc:(t + 1) * nc, H * nx + t * nu:H * nx + (t + 1) * nu] = Cu
+        return J
+
+    def get_dim(self, H):
+        return int(H) * self.nc
+
+    def limits(self, H):
+        """(lo, hi) as (H,nc) arrays"""
+        if self.lo.ndim == 2 and self.lo.shape[0] != int(H):
+            raise ValueError(f"the limits were given per step for H = {self.lo.shape[0]}, the horizon is {int(H)}")
+        return tuple(np.ascontiguousarray(np.broadcast_to(a, (int(H), self.nc))) for a in (self.lo, self.hi))
+
+    def get_lower_bounds(self, H):
+        return self.limits(self.lo.shape[0] if H is None and self.lo.ndim == 2 else (1 if H is None else H))[0].reshape(-1)
+
+    def get_upper_bounds(self, H):
+        return self.limits(self.hi.shape[0] if H is None and self.hi.ndim == 2 else (1 if H is None else H))[1].reshape(-1)
+
+    @staticmethod
+    def stack(constraints, H, n_cols):
+        """Several constraints as one: (C (sum nc, n_cols), lo (H, sum nc), hi (H, sum nc)), rows in list order."""
+        for c in constraints:
+            if c.C.shape[1] != n_cols:
+                raise ValueError(f"LinearStageConstraint: C has {c.C.shape[1]} columns, the model has nx + nu = {n_cols}")
+        lims = [c.limits(H) for c in constraints]
+        return (np.concatenate([c.C for c in constraints], axis=0), np.concatenate([l[0] for l in lims], axis=1),
+                np.concatenate([l[1] for l in lims], axis=1))

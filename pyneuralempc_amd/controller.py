@@ -86,12 +86,13 @@ class NMPC:
         from .optimizer.base import fused_evaluator
         from .objective.quadratic import QuadraticObjective
         from .integrator.base import DeviceIntegrator
-        from .constraints import BoxStateConstraint
+        from .constraints import BoxStateConstraint, LinearStageConstraint
         boxes = [c for c in self.constraint_list if isinstance(c, BoxStateConstraint)]
+        n_rows = sum(isinstance(c, LinearStageConstraint) for c in self.constraint_list)
         if not (isinstance(self.integrator, DeviceIntegrator) and self.integrator.on_device and isinstance(self.objective_func, QuadraticObjective)
-                and len(boxes) == len(self.constraint_list)):
+                and len(boxes) + n_rows == len(self.constraint_list)):
             raise NotImplementedError(f"{who} needs a device integrator, a QuadraticObjective and no extra "
-                                      "constraint rows other than BoxStateConstraint")
+                                      "constraint rows other than BoxStateConstraint and LinearStageConstraint")
         eng = fused_evaluator(self.integrator, self.objective_func, None).engine
         H = self.integrator.H
         X0t = X0 if isinstance(X0, torch.Tensor) else eng.to_device(np.atleast_2d(np.asarray(X0, dtype=np.float64)))
@@ -185,6 +186,22 @@ class NMPC:
             raise ValueError(f"{who}: rate terms are not supported with rolling-window models")
         return dict(u_prev=u_prev, S=du_weight, du_lb=du_lb, du_ub=du_ub)
 
+    def _stage_rows(self, who, **refused):
+        """The LinearStageConstraints of the constraint list stacked into one (C, lo (H,nc), hi (H,nc)), checked before anything
+        touches a device; None when there is none.  refused: what the device solver does not combine with rows, by name."""
+        from .constraints import LinearStageConstraint
+        rows = [c for c in self.constraint_list if isinstance(c, LinearStageConstraint)]
+        if not rows:
+            return None
+        bad = [name for name, on in refused.items() if on]
+        if bad:
+            raise ValueError(f"{who}: a LinearStageConstraint cannot be combined with {', '.join(bad)} (the device solver refuses "
+                             "those combinations)")
+        model = self.integrator.model
+        if int(getattr(model, "rolling_window", 1)) > 1:
+            raise ValueError(f"{who}: a LinearStageConstraint is not supported with rolling-window models")
+        return LinearStageConstraint.stack(rows, int(self.integrator.H), int(model.x_dim) + int(model.u_dim))
+
     @staticmethod
     def _rate_bind(eng, B, rate):
         """The rate terms bound on the engine (CallbackEngine.bind_rate); returns the (B,nu) device tensor of u_prev, which
@@ -238,12 +255,16 @@ class NMPC:
         ``self.last_gain_status`` (B,), is non-zero.  u_prev (B,nu) or (nu,), du_weight (nu,nu), du_lb / du_ub (nu,) or (H,nu)
         add an input-rate penalty sum_t du_t' du_weight du_t and rate limits du_lb <= du_t <= du_ub on du_t = u_t - u_{t-1},
         u_{-1} = u_prev (CallbackEngine.bind_rate, for this call only); not together with per-problem references or bounds,
-        return_duals or return_gain (the device solver refuses those combinations)."""
+        return_duals or return_gain (the device solver refuses those combinations).  Every LinearStageConstraint of the
+        constraint list is a set of rows lo <= Cx x_t + Cu u_t <= hi of every problem (CallbackEngine.bind_rows, stacked, for
+        this call only); not together with rate arguments, per-problem references or bounds, return_duals or return_gain."""
         import torch
         H = self.integrator.H
         rate = self._rate_check(X0, "next_batch", u_prev, du_weight, du_lb, du_ub)
         given = self._tracking_check(X0, H, "next_batch", xref=xref, uref=uref, cx=cx, cu=cu)
         bounds = self._tracking_check(X0, H, "next_batch", xlb=xlb, xub=xub, ulb=ulb, uub=uub)
+        rows = self._stage_rows("next_batch", **{"rate arguments": rate, "per-problem references": given, "per-problem bounds": bounds,
+                                                 "return_duals": return_duals, "return_gain": return_gain})
         eng, X0t, lb, ub = self._batch_engine(X0, p, tvp, prev_x, prev_u, prev_tvp, "next_batch")
         Zi = None if init_z is None else (init_z if isinstance(init_z, torch.Tensor) else eng.to_device(init_z))
         try:
@@ -253,6 +274,8 @@ class NMPC:
                 self._tracking_bind(eng, int(X0t.shape[0]), bounds, bind=eng.bind_bounds)
             if rate:
                 self._rate_bind(eng, int(X0t.shape[0]), rate)
+            if rows:
+                eng.bind_rows(*rows)
             duals = gain = None
             if return_duals or return_gain:
                 Z, status, iters, duals = eng.solve(X0t, Zi, lb, ub, return_duals=True, **solver_opts)
@@ -269,6 +292,8 @@ class NMPC:
                 eng.bind_bounds()
             if rate:
                 eng.bind_rate()
+            if rows:
+                eng.bind_rows()
         self.last_batch_iterations = iters
         z = Z.to("cpu", torch.float64).numpy()
         B, nx, nu = z.shape[0], eng.nx, eng.nu
@@ -295,7 +320,8 @@ class NMPC:
         intersected with the DomainConstraint and the box rows.  u_prev (B,nu) or (nu,) (the control applied before step 0),
         du_weight (nu,nu), du_lb / du_ub (nu,) or (H,nu) add an input-rate penalty and rate limits to every solve
         (next_batch): after each step the applied u_0 becomes u_prev of the next solve, on the device; the shifted warm start
-        is unchanged.  Returns (X (B,steps+1,nx), U (B,steps,nu), status (steps,B)) as NumPy arrays."""
+        is unchanged.  LinearStageConstraints of the constraint list hold in every solve (next_batch; not together with rate
+        arguments, per-problem references or bounds).  Returns (X (B,steps+1,nx), U (B,steps,nu), status (steps,B)) as NumPy arrays."""
         import torch
         model = self.integrator.model
         steps = int(steps)
@@ -304,6 +330,8 @@ class NMPC:
         given = self._tracking_check(X0, steps + int(self.integrator.H) - 1, "closed_loop_batch", xref=xref, uref=uref, cx=cx, cu=cu)
         bounds = self._tracking_check(X0, steps + int(self.integrator.H) - 1, "closed_loop_batch", xlb=xlb, xub=xub, ulb=ulb, uub=uub)
         rate = self._rate_check(X0, "closed_loop_batch", u_prev, du_weight, du_lb, du_ub)
+        rows = self._stage_rows("closed_loop_batch", **{"rate arguments": rate, "per-problem references": given,
+                                                        "per-problem bounds": bounds})
         if int(getattr(model, "tvp_dim", 0)) > 0:
             raise NotImplementedError("closed_loop_batch: models with time-varying parameters (tvp_dim > 0) are not supported -- "
                                       "a closed loop of `steps` steps needs a tvp schedule of H + steps - 1 rows, longer than the "
@@ -324,6 +352,8 @@ class NMPC:
             track = self._tracking_bind(eng, B, given) if given else None
             bnd = self._tracking_bind(eng, B, bounds, bind=eng.bind_bounds) if bounds else None
             up = self._rate_bind(eng, B, rate) if rate else None
+            if rows:
+                eng.bind_rows(*rows)
             for k in range(steps):
                 if track and k > 0:                               # the horizon's window of the schedules: rows k .. k+H-1
                     eng.bind_tracking(**track, offset=k)
@@ -354,6 +384,8 @@ class NMPC:
                 eng.bind_bounds()
             if rate:
                 eng.bind_rate()
+            if rows:
+                eng.bind_rows()
         self.last_closed_loop_iterations = iters      # outer iterations of every step's solve (a list; next_batch's int is last_batch_iterations)
         return (torch.stack(Xs, dim=1).to("cpu", torch.float64).numpy(), torch.stack(Us, dim=1).to("cpu", torch.float64).numpy(),
                 torch.stack(Ss, dim=0).cpu().numpy())

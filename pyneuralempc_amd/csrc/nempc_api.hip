@@ -11,6 +11,7 @@
 
 #include "nempc_internal.h"
 #include "activations.h"
+#include "rows_index.h"     // rows_limit_entry: where a limit of nempc_bind_stage_rows is read from
 #include "stage_aug.h"      // window_var: the window's column order
 
 namespace nempc {
@@ -369,9 +370,12 @@ int point_enter(nempc_handle hh, int32_t B, const char* who, const char* rolling
     return NEMPC_OK;
 }
 
-// nempc_kkt_residual, nempc_sensitivity, nempc_kkt_solve under a rate binding: they would certify or differentiate the problem
-// WITHOUT the penalty and the limits
+// nempc_kkt_residual, nempc_sensitivity, nempc_kkt_solve under a rate or stage-rows binding: they would certify or
+// differentiate the problem WITHOUT the penalty, the limits and the rows
 int refuse_rate(nempc_handle hh, const char* who) {
+    if (reinterpret_cast<Handle*>(hh)->rows.on())
+        return fail(NEMPC_EUNSUPPORTED, who, ": a stage-rows binding (nempc_bind_stage_rows) is on: the multipliers of the rows are "
+                                             "not mapped back to the caller's problem; unbind it to evaluate the plain problem");
     if (!reinterpret_cast<Handle*>(hh)->rate.on()) return NEMPC_OK;
     return fail(NEMPC_EUNSUPPORTED, who, ": a rate binding (nempc_bind_rate) is on: the multipliers of the augmented problem are not "
                                          "mapped back to the caller's rows; unbind it to evaluate the plain problem");
@@ -701,6 +705,48 @@ int nempc_bind_rate(nempc_handle hh, const double* S, const double* dlo, const d
     return NEMPC_OK;
 }
 
+int nempc_bind_stage_rows(nempc_handle hh, int32_t nc, const double* C, const double* rlo, const double* rhi, int32_t per_stage) {
+    if (!hh) return fail(NEMPC_EINVAL, "nempc_bind_stage_rows: null handle");
+    Handle& h = *reinterpret_cast<Handle*>(hh);
+    if (nc < 0) return fail(NEMPC_EINVAL, "nempc_bind_stage_rows: nc must be >= 0");
+    if (nc == 0 || !C) { h.rows = RowsBind{}; return NEMPC_OK; }      // (d_rows_C stays: a launch in flight may still read it)
+    if (h.w > 1)
+        return fail(NEMPC_EUNSUPPORTED, "nempc_bind_stage_rows: rolling_window > 1 handles are not supported (the window state and "
+                                        "the row state are two augmentations of the stage; their combination is not built)");
+    if (per_stage != 0 && per_stage != 1) return fail(NEMPC_EINVAL, "nempc_bind_stage_rows: per_stage must be 0 or 1");
+    const int H = h.cfg.H, nio = h.cfg.nx + h.cfg.nu;
+    RowsBind rb;
+    rb.nc = nc;
+    rb.C.assign(C, C + (size_t)nc * nio);
+    for (double c : rb.C)
+        if (!std::isfinite(c)) return fail(NEMPC_EINVAL, "nempc_bind_stage_rows: C has a non-finite entry");
+    rb.lo.assign((size_t)H * nc, -INFINITY);
+    rb.hi.assign((size_t)H * nc, INFINITY);
+    const RowsDims d = rows_dims(H, h.cfg.nx, h.cfg.nu, nc);
+    for (int t = 0; t < H; ++t)
+        for (int k = 0; k < nc; ++k) {
+            const int e = rows_limit_entry(d, t, k, per_stage);
+            const double lo = rlo ? rlo[e] : -INFINITY, hi = rhi ? rhi[e] : INFINITY;
+            if (std::isnan(lo) || std::isnan(hi)) return fail(NEMPC_EINVAL, "nempc_bind_stage_rows: a limit is NaN");
+            if (lo >= hi)
+                return fail(NEMPC_EINVAL, "nempc_bind_stage_rows: rlo >= rhi (an equality or empty row has no interior for the barrier)");
+            rb.lo[(size_t)t * nc + k] = lo; rb.hi[(size_t)t * nc + k] = hi;
+        }
+    // C in the handle's dtype on the device, each element cast once
+    DeviceGuard dg(h.cfg.device);
+    if (!dg.ok) return fail(NEMPC_EHIP, "nempc_bind_stage_rows: hipSetDevice failed");
+    const size_t ne = rb.C.size(), bytes = ne * h.esz;
+    if (int rc = h.d_rows_C.ensure(bytes, "stage rows C")) return rc;
+    if (h.cfg.dtype == NEMPC_F64) {
+        NEMPC_HIP(hipMemcpy(h.d_rows_C.get(), rb.C.data(), bytes, hipMemcpyHostToDevice));
+    } else {
+        const std::vector<float> cf(rb.C.begin(), rb.C.end());
+        NEMPC_HIP(hipMemcpy(h.d_rows_C.get(), cf.data(), bytes, hipMemcpyHostToDevice));
+    }
+    h.rows = std::move(rb);
+    return NEMPC_OK;
+}
+
 int nempc_set_box_rows(nempc_handle hh, int enabled, const double* lo, const double* hi) {
     if (!hh) return fail(NEMPC_EINVAL, "nempc_set_box_rows: null handle");
     Handle& h = *reinterpret_cast<Handle*>(hh);
@@ -945,6 +991,24 @@ int nempc_solve_duals(nempc_handle hh, int32_t B, const void* X0, void* Z, const
         if (h.bbind.on())
             return fail(NEMPC_EUNSUPPORTED, "nempc_solve: per-problem bounds (nempc_bind_bounds) with a rate binding (nempc_bind_rate): "
                                             "the bounds of the augmented state are built on the host");
+    }
+    if (h.rows.on()) {
+        if (lam || zl || zu)
+            return fail(NEMPC_EUNSUPPORTED, "nempc_solve_duals: multipliers under a stage-rows binding (nempc_bind_stage_rows) are not "
+                                            "supported (the costates of the augmented state are not mapped back to the caller's rows); "
+                                            "pass NULL for lam, zl and zu");
+        if (h.w > 1)
+            return fail(NEMPC_EUNSUPPORTED, "nempc_solve: a stage-rows binding (nempc_bind_stage_rows) on a rolling_window > 1 handle is "
+                                            "not supported");
+        if (h.rate.on())
+            return fail(NEMPC_EUNSUPPORTED, "nempc_solve: a rate binding (nempc_bind_rate) with a stage-rows binding "
+                                            "(nempc_bind_stage_rows): the two augmentations of the stage are not combined");
+        if (h.track.on())
+            return fail(NEMPC_EUNSUPPORTED, "nempc_solve: per-problem tracking data (nempc_bind_tracking) with a stage-rows binding "
+                                            "(nempc_bind_stage_rows): the objective table over the augmented state is built on the host");
+        if (h.bbind.on())
+            return fail(NEMPC_EUNSUPPORTED, "nempc_solve: per-problem bounds (nempc_bind_bounds) with a stage-rows binding "
+                                            "(nempc_bind_stage_rows): the bounds of the augmented state are built on the host");
     }
     if (opts->max_iter < 1 || opts->max_linesearch < 1 || !(opts->mu_factor > 0.0 && opts->mu_factor < 1.0) ||
         !(opts->mu_init > 0.0) || !(opts->mu_min > 0.0) || opts->lq_kernel < 0 || opts->lq_kernel > 3)

@@ -141,6 +141,14 @@ struct RateBind {
     bool on() const { return u_prev != nullptr; }
 };
 
+// Linear stage inequality rows bound by nempc_bind_stage_rows: host copies of C = [Cx | Cu] (nc, nx + nu) and of the limits
+// (expanded to (H,nc), +-inf = no limit).  The device copy of C, in the handle's dtype, is Handle::d_rows_C.  nc = 0: nothing bound.
+struct RowsBind {
+    int nc = 0;
+    std::vector<double> C, lo, hi;
+    bool on() const { return nc > 0; }
+};
+
 // Device memory: every allocation the handle owns is a DevBuf member (dev_buf.h) and goes with the handle; a new workspace is
 // one more member and nothing else.  What a caller bound (d_extra, d_hist_*, the bindings, jac_resident's entries) stays a
 // raw pointer.  solver_ws and comm are opaque to everyone but their units, which free them (solver_free, comm_free).
@@ -161,6 +169,8 @@ struct Handle {
     TrackBind track;             // bound by nempc_bind_tracking
     BoundBind bbind;             // bound by nempc_bind_bounds
     RateBind rate;               // bound by nempc_bind_rate
+    RowsBind rows;               // bound by nempc_bind_stage_rows
+    DevBuf<> d_rows_C;           // ... and its C on the device, dtype T (nc, nx + nu)
     RowGather gather() const {
         RowGather gk;
         gk.H = cfg.H; gk.nx = cfg.nx; gk.nu = cfg.nu; gk.n = n; gk.w = w; gk.rev = rev;

@@ -46,7 +46,8 @@
 //     solver_compact_impl.h  partition / gather of the unconverged problems, scatter of the results
 //     solver_roll_impl.h     rolling-window models: RollTables and the roll_* kernels
 //     solver_rate_impl.h     input-rate penalty and limits (nempc_bind_rate): the rate_* kernels (index arithmetic: rate_index.h)
-//     solver_aug.h           StageAug<T>: what of a solve is specific to a stage augmentation (window, rate) -- workspace, bounds,
+//     solver_rows_impl.h     linear stage inequality rows (nempc_bind_stage_rows): the rows_* kernels (index arithmetic: rows_index.h)
+//     solver_aug.h           StageAug<T>: what of a solve is specific to a stage augmentation (window, rate, rows) -- workspace, bounds,
 //                            start, the callbacks in augmented form, the solution handed back; host side, launches the two above
 //     stage_aug.h            ... and its host arithmetic (nothing of HIP: tests/stage_aug_check.cpp): stage dimensions, window_var,
 //                            the window's tables, bound slots, the objective table over the augmented stage
@@ -73,6 +74,7 @@
 #include "solver_compact_impl.h"
 #include "solver_roll_impl.h"
 #include "solver_rate_impl.h"
+#include "solver_rows_impl.h"
 #include "solver_aug.h"
 
 namespace nempc {

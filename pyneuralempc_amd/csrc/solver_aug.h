@@ -1,5 +1,5 @@
 // Batched solver, the seam between Solve<T> and a stage augmentation (stage_aug.h: the host arithmetic; solver_roll_impl.h,
-// solver_rate_impl.h: the kernels).  StageAug<T> is everything of one solve that is specific to the augmentation: what the
+// solver_rate_impl.h, solver_rows_impl.h: the kernels).  StageAug<T> is everything of one solve that is specific to the augmentation: what the
 // workspace holds beyond the plain buffers, where bounds land, the augmented start and objective table, the evaluation of
 // the callbacks in augmented form, the solution handed back.  Solve<T> asks it `on()` where the SCHEDULE depends on running
 // augmented; which augmentation is decided here, by a switch on the kind.  Included by solver.hip only, after the kernels.
@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 
+#include "rows_index.h"
 #include "stage_aug.h"
 
 namespace nempc {
@@ -44,14 +45,14 @@ struct StageAug {
     Handle& h; AugWs& w; const hipStream_t s;
     const int kind, B, H, nx_r, nu, nin_r, n_r, m_r;      // *_r: the handle's (the caller's variables, the callbacks' shapes)
     const StageDims d;                                     // the solver's
-    const RateDims rd; const ObjOffsets ao; const unsigned gRn;      // gRn: grid of the element-wise kernels over the caller's variables
+    const RateDims rd; const RowsDims wd; const ObjOffsets ao; const unsigned gRn;      // gRn: grid of the element-wise kernels over the caller's variables
     const void* X0 = nullptr;                              // the caller's initial states (the callbacks read them by problem index)
     void *f = nullptr, *g = nullptr, *gt = nullptr, *tiles = nullptr, *hblk = nullptr, *grad = nullptr;   // the solver's evaluation buffers
     RollTablesHost th;                                     // (between buffers() and upload_tables() of a workspace being built)
     StageAug(Handle& hh, AugWs& ww, int BB, hipStream_t ss)
-        : h(hh), w(ww), s(ss), kind(hh.w > 1 ? AUG_WINDOW : (hh.rate.on() ? AUG_RATE : AUG_NONE)), B(BB), H(hh.cfg.H),
-          nx_r(hh.cfg.nx), nu(hh.cfg.nu), nin_r(hh.nin), n_r(hh.n), m_r(hh.m), d(stage_dims(kind, H, nx_r, nu, hh.w)),
-          rd(rate_dims(H, nx_r, nu)), ao(obj_offsets(H, d.nx, nu)), gRn((unsigned)(((size_t)BB * n_r + 255) / 256)) {}
+        : h(hh), w(ww), s(ss), kind(hh.w > 1 ? AUG_WINDOW : (hh.rate.on() ? AUG_RATE : (hh.rows.on() ? AUG_ROWS : AUG_NONE))),
+          B(BB), H(hh.cfg.H), nx_r(hh.cfg.nx), nu(hh.cfg.nu), nin_r(hh.nin), n_r(hh.n), m_r(hh.m),
+          d(stage_dims(kind, H, nx_r, nu, hh.w, hh.rows.nc)), rd(rate_dims(H, nx_r, nu)), wd(rows_dims(H, nx_r, nu, hh.rows.nc)), ao(obj_offsets(H, d.nx, nu)), gRn((unsigned)(((size_t)BB * n_r + 255) / 256)) {}
     bool on() const { return kind != AUG_NONE; }
     template <typename F> int each_table(F f) {
         const struct { int** p; const std::vector<int>* v; } tb[] = {{&w.rt.src, &th.src}, {&w.rt.src0, &th.src0}, {&w.rt.prim, &th.prim},
@@ -68,13 +69,13 @@ struct StageAug {
             {&w.rhblk, Bn * H * nin_r * nin_r * e}, {&w.rlam, Bn * m_r * e},
             {&w.rZin, Bn * d.n * e}, {&w.rS0, Bn * d.nx * e}, {&w.rZout, Bn * d.n * e}, {&w.robj, (size_t)ao.total * e}});
         if (kind != AUG_WINDOW) return;
-        al.push_back({&w.rgrad, Bn * n_r * e});      // (rate: the gradient comes from the augmented table)
+        al.push_back({&w.rgrad, Bn * n_r * e});      // (rate, rows: the gradient comes from the augmented table)
         th = roll_tables(H, nx_r, nu, h.w, h.rev);
         (void)each_table([&](int** p, const std::vector<int>& v) { al.push_back({(void**)p, v.size() * sizeof(int)}); return 0; });
     }
     int upload_tables() {
         w.kind = kind;
-        w.bslot = bound_slots(kind, H, nx_r, nu, h.w);
+        w.bslot = bound_slots(kind, H, nx_r, nu, h.w, h.rows.nc);
         if (!on()) return NEMPC_OK;
         NEMPC_HIP(hipMemsetAsync(w.rlam, 0, (size_t)B * m_r * sizeof(T), s));     // (box rows of the handle keep zero multipliers)
         if (kind != AUG_WINDOW) return NEMPC_OK;
@@ -83,14 +84,16 @@ struct StageAug {
             return NEMPC_OK;
         });
     }
-    // ---- bounds: the list the augmentation's slots index -- the caller's bounds on z, then what it adds (rate: the limits)
+    // ---- bounds: the list the augmentation's slots index -- the caller's bounds on z, then what it adds (rate: the limits on
+    //      the moves; rows: the limits of the rows)
     void append_bounds(std::vector<double>& lo, std::vector<double>& hi) const {
-        if (kind != AUG_RATE) return;
-        lo.insert(lo.end(), h.rate.dlo.begin(), h.rate.dlo.end());
-        hi.insert(hi.end(), h.rate.dhi.begin(), h.rate.dhi.end());
+        if (kind != AUG_RATE && kind != AUG_ROWS) return;
+        const std::vector<double>&alo = kind == AUG_RATE ? h.rate.dlo : h.rows.lo, &ahi = kind == AUG_RATE ? h.rate.dhi : h.rows.hi;
+        lo.insert(lo.end(), alo.begin(), alo.end());
+        hi.insert(hi.end(), ahi.begin(), ahi.end());
     }
-    // ---- start: the augmented guess and start state (window: s_0 from x0 and the history; rate: s_{-1} = [x0 ; u_prev]) from
-    //      the caller's, and the objective table over the augmented stage.  grid: the solver's element-wise grid
+    // ---- start: the augmented guess and start state (window: s_0 from x0 and the history; rate: s_{-1} = [x0 ; u_prev]; rows:
+    //      s_{-1} = [x0 ; 0]) from the caller's, and the objective table over the augmented stage.  grid: the solver's element-wise grid
     int start(const void* Z, const void* X0_, const void* lb, const void* ub, T mu0, int has_bounds, unsigned grid) {
         X0 = X0_;
         switch (kind) {
@@ -103,11 +106,15 @@ struct StageAug {
             hipLaunchKernelGGL(rate_build_kernel<T>, dim3(grid), dim3(256), 0, s, B, rd, (const T*)Z, (const T*)X0,
                                (const T*)h.rate.u_prev, (const T*)lb, (const T*)ub, mu0, has_bounds, (T*)w.rZin, (T*)w.rS0);
             break;
+        case AUG_ROWS:
+            hipLaunchKernelGGL(rows_build_kernel<T>, dim3(grid), dim3(256), 0, s, B, wd, (const T*)Z, (const T*)X0,
+                               h.d_rows_C.as<const T>(), (const T*)lb, (const T*)ub, mu0, has_bounds, (T*)w.rZin, (T*)w.rS0);
+            break;
         }
         const ObjHost& oh = h.obj_host;
         const AugObjIn in{oh.Q.data(), oh.R.data(), (h.obj_QT.empty() ? oh.Q : h.obj_QT).data(), oh.xref.data(), oh.uref.data(),
                           oh.cx.data(), oh.cu.data(), h.rate.S.data()};
-        return upload_aug_table(aug_objective_table<T>(kind, H, nx_r, nu, h.w, in));
+        return upload_aug_table(aug_objective_table<T>(kind, H, nx_r, nu, h.w, in, h.rows.nc));
     }
     // (uploaded when it changes, like the bounds)
     int upload_aug_table(const std::vector<T>& tab) {
@@ -124,7 +131,8 @@ struct StageAug {
     //      blocks, into the iterate's buffers -- or, at a trial point (lam_aug = null), the defects only, into gt (the acceptance
     //      kernel evaluates the objective from the augmented table itself).
     //      window: the network reads the primary copies, f and the gradient come from the handle's objective kernel;
-    //      rate: the network reads x_t, u_{t-1} + v_t, f and the gradient come from the augmented table inside the spread kernel
+    //      rate: the network reads x_t, u_{t-1} + v_t, f and the gradient come from the augmented table inside the spread kernel;
+    //      rows: the network reads the x and u slots, its multipliers are lam_x + Cx' lam_y, f and the gradient as for rate
     int eval(const void* Zaug, const void* lam_aug) {
         const bool full = lam_aug != nullptr;
         T* const lam_r = full ? (T*)w.rlam : (T*)nullptr;
@@ -135,6 +143,10 @@ struct StageAug {
             break;
         case AUG_RATE:
             hipLaunchKernelGGL(rate_gather_kernel<T>, dim3(gRn), dim3(256), 0, s, B, rd, m_r, 0, (const T*)Zaug, (const T*)w.rS0,
+                               (T*)w.rZ, (const T*)lam_aug, lam_r);
+            break;
+        case AUG_ROWS:
+            hipLaunchKernelGGL(rows_gather_kernel<T>, dim3(gRn), dim3(256), 0, s, B, wd, m_r, h.d_rows_C.as<const T>(), (const T*)Zaug,
                                (T*)w.rZ, (const T*)lam_aug, lam_r);
             break;
         }
@@ -156,11 +168,16 @@ struct StageAug {
                                (const T*)w.rg, tiles_r, hblk_r, (const T*)w.robj, ao, g_a, tiles_a, hblk_a, grad_a,
                                full ? (T*)f : (T*)nullptr);
             break;
+        case AUG_ROWS:
+            hipLaunchKernelGGL(rows_spread_kernel<T>, dim3(B * H), dim3(256), 0, s, wd, m_r, h.d_rows_C.as<const T>(), (const T*)Zaug,
+                               (const T*)w.rg, tiles_r, hblk_r, (const T*)w.robj, ao, g_a, tiles_a, hblk_a, grad_a,
+                               full ? (T*)f : (T*)nullptr);
+            break;
         }
         return NEMPC_OK;
     }
-    // ---- finish: the scatter writes the augmented solution to rZout, the caller's Z is its primary copies (window) or the x
-    //      and u slots of the state (rate)
+    // ---- finish: the scatter writes the augmented solution to rZout, the caller's Z is its primary copies (window), the x
+    //      and u slots of the state (rate) or the x slots and the stage controls (rows)
     void* solution_buffer(void* Z) const { return on() ? w.rZout : Z; }
     void hand_back(void* Z) {
         switch (kind) {
@@ -171,6 +188,10 @@ struct StageAug {
         case AUG_RATE:
             hipLaunchKernelGGL(rate_gather_kernel<T>, dim3(gRn), dim3(256), 0, s, B, rd, m_r, 1, (const T*)w.rZout, (const T*)w.rS0,
                                (T*)Z, (const T*)nullptr, (T*)nullptr);
+            break;
+        case AUG_ROWS:
+            hipLaunchKernelGGL(rows_gather_kernel<T>, dim3(gRn), dim3(256), 0, s, B, wd, m_r, h.d_rows_C.as<const T>(),
+                               (const T*)w.rZout, (T*)Z, (const T*)nullptr, (T*)nullptr);
             break;
         }
     }

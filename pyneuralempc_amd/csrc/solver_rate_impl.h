@@ -75,6 +75,30 @@ __global__ __launch_bounds__(256) void rate_gather_kernel(int B, RateDims d, int
     }
 }
 
+// step t's share of the gradient of an objective table over an augmented stage (P, ao: obj_offsets(H, ns, nu)), by the 256
+// threads of a workgroup: the state block s_t (weights Q_aug, or QT_aug at the last step) and the stage-control block behind
+// the H states; sums in objective_row_value's order.  za: the problem's augmented variables [s_0 .. s_{H-1} | controls]
+template <typename T>
+__device__ __forceinline__ void aug_stage_gradient(int b, int t, int H, int ns, int nu, const T* __restrict__ P, const ObjOffsets& ao,
+                                                   const T* __restrict__ za, T* __restrict__ grad_aug) {
+    const int nin_s = ns + nu;
+    const size_t n_s = (size_t)H * nin_s;
+    const T* Qs = P + (t == H - 1 ? ao.QTs : ao.Qs);
+    const T* st = za + t * ns;
+    const T* vt = za + H * ns + t * nu;
+    for (int i = threadIdx.x; i < nin_s; i += 256) {
+        T acc = T(0);
+        if (i < ns) {
+            for (int j = 0; j < ns; ++j) acc = fma(Qs[i * ns + j], st[j] - P[ao.xref + t * ns + j], acc);
+            grad_aug[(size_t)b * n_s + t * ns + i] = acc + P[ao.cx + t * ns + i];
+        } else {
+            const int iu = i - ns;
+            for (int j = 0; j < nu; ++j) acc = fma(P[ao.Rs + iu * nu + j], vt[j] - P[ao.uref + t * nu + j], acc);
+            grad_aug[(size_t)b * n_s + H * ns + t * nu + iu] = acc + P[ao.cu + t * nu + iu];
+        }
+    }
+}
+
 // the evaluation spread into augmented form; one workgroup per (problem, step), its entries spread over the 256 threads.
 // tiles / hblk / grad / f null: a trial point needs the defects only.  P, ao: the objective table over the augmented stage
 template <typename T>
@@ -110,24 +134,7 @@ __global__ __launch_bounds__(256) void rate_spread_kernel(RateDims d, int m_r, c
         for (int e = threadIdx.x; e < nin_s * nin_s; e += 256)
             ha[e] = hr[rate_handle_col(d, e / nin_s) * nin_r + rate_handle_col(d, e % nin_s)];
     }
-    if (grad_aug) {
-        // this step's share of the gradient of the augmented objective: the state block s_t (weights Q_aug, or QT_aug at the
-        // last step) and the control block v_t ((S + S') v_t); sums in objective_row_value's order
-        const T* Qs = P + (t == H - 1 ? ao.QTs : ao.Qs);
-        const T* st = za + t * ns;
-        const T* vt = za + H * ns + t * nu;
-        for (int i = threadIdx.x; i < nin_s; i += 256) {
-            T acc = T(0);
-            if (i < ns) {
-                for (int j = 0; j < ns; ++j) acc = fma(Qs[i * ns + j], st[j] - P[ao.xref + t * ns + j], acc);
-                grad_aug[(size_t)b * d.n_s + t * ns + i] = acc + P[ao.cx + t * ns + i];
-            } else {
-                const int iu = i - ns;
-                for (int j = 0; j < nu; ++j) acc = fma(P[ao.Rs + iu * nu + j], vt[j] - P[ao.uref + t * nu + j], acc);
-                grad_aug[(size_t)b * d.n_s + H * ns + t * nu + iu] = acc + P[ao.cu + t * nu + iu];
-            }
-        }
-    }
+    if (grad_aug) aug_stage_gradient<T>(b, t, H, ns, nu, P, ao, za, grad_aug);
     // the objective value: the first wave of the problem's first workgroup, lanes over the horizon
     if (f && t == 0 && threadIdx.x < 64) {
         const double acc = objective_row_value<T>(b, (int)threadIdx.x, H, ns, nu, ao, P, za, (T*)nullptr);

@@ -1,7 +1,9 @@
 // Host arithmetic of the stage augmentations nempc_solve runs: the window of a rolling-window model as the stage state
-// (solver_roll_impl.h) and [x ; u] with the control move as the stage control (nempc_bind_rate, solver_rate_impl.h).  Like
+// (solver_roll_impl.h), [x ; u] with the control move as the stage control (nempc_bind_rate, solver_rate_impl.h) and [x ; y]
+// with y the value of the linear stage rows (nempc_bind_stage_rows, solver_rows_impl.h; index arithmetic: rows_index.h).  Like
 // rate_index.h it includes nothing of HIP and nothing of the library beyond the two layout headers, so that a host program
-// checks every table entry by entry (tests/stage_aug_check.cpp).  solver_aug.h is the part that launches.
+// checks every table entry by entry (tests/stage_aug_check.cpp, tests/rows_index_check.cpp).  solver_aug.h is the part that
+// launches.
 //
 // The caller's variables are z = [x_1 .. x_H (H nx) | u_0 .. u_{H-1} (H nu)].  What an augmentation states here: the solver's
 // stage dimensions, where every caller variable (and every bound it adds) sits in the augmented vector, and the objective
@@ -17,12 +19,13 @@
 namespace nempc {
 
 // The stage the solver runs on: the handle's own, or an augmentation of it
-enum Augmentation { AUG_NONE = 0, AUG_WINDOW = 1, AUG_RATE = 2 };
+enum Augmentation { AUG_NONE = 0, AUG_WINDOW = 1, AUG_RATE = 2, AUG_ROWS = 3 };
 
-// ---- stage dimensions of the solver's problem: state, columns of a tile / block, variables, defect rows
+// ---- stage dimensions of the solver's problem: state, columns of a tile / block, variables, defect rows (nc: rows per stage
+// of the rows kind)
 struct StageDims { int nx, nin, n, m; };
-inline StageDims stage_dims(int kind, int H, int nx, int nu, int w) {
-    const int ns = kind == AUG_WINDOW ? w * nx + (w - 1) * nu : (kind == AUG_RATE ? nx + nu : nx);
+inline StageDims stage_dims(int kind, int H, int nx, int nu, int w, int nc = 0) {
+    const int ns = kind == AUG_WINDOW ? w * nx + (w - 1) * nu : (kind == AUG_RATE ? nx + nu : (kind == AUG_ROWS ? nx + nc : nx));
     return {ns, ns + nu, H * (ns + nu), H * ns};
 }
 
@@ -92,13 +95,21 @@ inline RollTablesHost roll_tables(int H, int nx, int nu, int w, int rev) {
 }
 
 // ---- bounds.  Slot in the solver's bound vector (StageDims::n) of entry i of the list [the caller's bounds on z (H (nx + nu)) |
-// rate: the limits on du_t[j] at t nu + j (H nu)]; every other slot carries no bound (the copies inside a window state)
-inline std::vector<int> bound_slots(int kind, int H, int nx, int nu, int w) {
+// rate: the limits on du_t[j] at t nu + j (H nu); rows: the limits of row (t, k) at t nc + k (H nc)]; every other slot carries
+// no bound (the copies inside a window state)
+inline std::vector<int> bound_slots(int kind, int H, int nx, int nu, int w, int nc = 0) {
     const int n_r = H * (nx + nu);
-    std::vector<int> slot(n_r + (kind == AUG_RATE ? H * nu : 0));
+    std::vector<int> slot(n_r + (kind == AUG_RATE ? H * nu : (kind == AUG_ROWS ? H * nc : 0)));
     if (kind == AUG_WINDOW) {
         const std::vector<int> prim = roll_tables(H, nx, nu, w, 0).prim;     // (the direction orders tile columns only)
         for (int v = 0; v < n_r; ++v) slot[v] = prim[v];
+        return slot;
+    }
+    if (kind == AUG_ROWS) {      // s_t = [x_t ; y_t], the controls behind the H states: rows_bound_slot / rows_limit_slot of
+        const int ns = nx + nc;  // rows_index.h restated (this header's includes are fixed; rows_index_check.cpp holds both together)
+        for (int v = 0; v < H * nx; ++v) slot[v] = (v / nx) * ns + v % nx;
+        for (int v = H * nx; v < n_r; ++v) slot[v] = H * ns + (v - H * nx);
+        for (int k = n_r; k < (int)slot.size(); ++k) slot[k] = ((k - n_r) / nc) * ns + nx + (k - n_r) % nc;
         return slot;
     }
     const RateDims rd = rate_dims(H, nx, nu);
@@ -112,11 +123,11 @@ inline std::vector<int> bound_slots(int kind, int H, int nx, int nu, int w) {
 // in double cast once to T; what is not written is zero.
 struct AugObjIn { const double *Q, *R, *QT, *xref, *uref, *cx, *cu, *S; };
 template <typename T>
-std::vector<T> aug_objective_table(int kind, int H, int nx, int nu, int w, const AugObjIn& in) {
-    const int ns = stage_dims(kind, H, nx, nu, w).nx;
+std::vector<T> aug_objective_table(int kind, int H, int nx, int nu, int w, const AugObjIn& in, int nc = 0) {
+    const int ns = stage_dims(kind, H, nx, nu, w, nc).nx;
     const ObjOffsets ao = obj_offsets(H, ns, nu);
     std::vector<T> tab((size_t)ao.total, T(0));
-    // both kinds: the caller's state weights, references and linear costs on the leading (primary) block of s
+    // every kind: the caller's state weights, references and linear costs on the leading (primary) block of s
     for (int i = 0; i < nx; ++i)
         for (int j = 0; j < nx; ++j) {
             tab[ao.Q + i * ns + j] = (T)in.Q[i * nx + j];
@@ -129,7 +140,8 @@ std::vector<T> aug_objective_table(int kind, int H, int nx, int nu, int w, const
             tab[ao.xref + t * ns + i] = (T)in.xref[t * nx + i];
             tab[ao.cx + t * ns + i] = (T)in.cx[t * nx + i];
         }
-    // window: the stage control is the caller's -- R, uref, cu as they are (zeros stay on the copies inside s).
+    // window, rows: the stage control is the caller's -- R, uref, cu as they are (zeros stay on the copies inside s and on the
+    // row values y: they cost nothing).
     // rate: the caller's control is the u block of s = [x ; u] -- Q_aug = blkdiag(Q, R), QT_aug = blkdiag(QT, R),
     // [xref ; uref], [cx ; cu] -- and the stage control is the move v: R_aug = S, zero reference and linear cost
     const bool rate = kind == AUG_RATE;

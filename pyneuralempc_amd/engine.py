@@ -76,6 +76,36 @@ def check_rate_args(H, nu, dtype, device, u_prev, S, du_lb, du_ub):
     return cont(Sa), cont(lims.get("du_lb")), cont(lims.get("du_ub")), per_stage
 
 
+def check_rows_args(H, nx, nu, C, lo, hi):
+    """Arguments of CallbackEngine.bind_rows, checked before the C call (no device is touched): C (nc, nx+nu) finite, nc >= 1;
+    lo / hi (nc,) or (H,nc) -- both the same form when both are given --, no NaN, lo < hi on every entry.
+    -> (C, lo, hi as float64 arrays or None, per_stage 0 | 1)."""
+    H, nio = int(H), int(nx) + int(nu)
+    Ca = np.asarray(C, dtype=np.float64)
+    if Ca.ndim != 2 or Ca.shape[0] < 1 or Ca.shape[1] != nio or not np.isfinite(Ca).all():
+        raise ValueError(f"bind_rows: C must be a finite (nc, {nio}) matrix with nc >= 1, got shape {Ca.shape}")
+    nc = Ca.shape[0]
+    lims, forms = {}, set()
+    for name, v in (("lo", lo), ("hi", hi)):
+        if v is None:
+            continue
+        a = np.asarray(v, dtype=np.float64)
+        if a.shape not in ((nc,), (H, nc)):
+            raise ValueError(f"bind_rows: {name} must have shape {(nc,)} (every step) or {(H, nc)} (per step), got {a.shape}")
+        if np.isnan(a).any():
+            raise ValueError(f"bind_rows: {name} has a NaN")
+        lims[name] = a
+        forms.add(a.ndim)
+    if len(forms) > 1:        # one form in the C interface
+        lims = {k: np.broadcast_to(a, (H, nc)) for k, a in lims.items()}
+    if len(lims) == 2 and (lims["lo"] >= lims["hi"]).any() or \
+            "lo" in lims and np.isposinf(lims["lo"]).any() or "hi" in lims and np.isneginf(lims["hi"]).any():
+        raise ValueError("bind_rows: lo >= hi on some entry (the barrier needs an interior)")
+    per_stage = 1 if any(a.ndim == 2 for a in lims.values()) else 0
+    cont = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    return cont(Ca), cont(lims.get("lo")), cont(lims.get("hi")), per_stage
+
+
 def _ptr(t):
     """device pointer of a tensor for the C ABI; None stays None (an optional argument)"""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
@@ -111,6 +141,7 @@ class CallbackEngine:
         self._tracking = None
         self._bounds = None
         self._rate = None
+        self._rows = None
         self.integrator = integrator if isinstance(integrator, int) else _lib.INTEGRATOR_IDS[integrator]
         self.DT = float(DT)
         self.kernel = kernel
@@ -181,6 +212,8 @@ class CallbackEngine:
             self.bind_bounds(**self._bounds[0], offset=self._bounds[1])
         if self._rate is not None:
             self.bind_rate(**self._rate)
+        if self._rows is not None:
+            self.bind_rows(**self._rows)
         self._refresh_dims()
         self._buffers = {}
 
@@ -389,6 +422,30 @@ class CallbackEngine:
         _lib.check(fn(self._handle, ptr(Sa), ptr(lo), ptr(hi), per_stage, ctypes.c_void_p(u_prev.data_ptr()),
                       int(u_prev.shape[0])))
         self._rate = dict(u_prev=u_prev, S=Sa, du_lb=lo, du_ub=hi)
+
+    def bind_rows(self, C=None, lo=None, hi=None):
+        """Bind linear stage inequality rows for the following solve calls (nempc_bind_stage_rows): every problem is solved
+        inside lo_t <= Cx x_t + Cu u_t <= hi_t for t = 0 .. H-1, C = [Cx | Cu] (nc, nx+nu), x_t / u_t row t of the state / control
+        block of z (x_t: the state the t-th step arrives at).  lo / hi (nc,) for every step or (H,nc) per step, None or -+inf =
+        no limit on that side, lo < hi on every entry.  Host arrays, copied.  bind_rows() with nothing removes the binding.
+        eval / hess / rollout do not read it; kkt_residual, sensitivity, kkt_solve and solve(return_duals=True) refuse while it
+        is on, and so does a solve with bind_rate, bind_tracking or bind_bounds.  At convergence every row holds to
+        tol_constraint * (1 + |Cx row|_1)."""
+        fn = getattr(self.lib, "nempc_bind_stage_rows", None)
+        if fn is None:
+            raise RuntimeError("this libnempc.so has no nempc_bind_stage_rows")
+        if C is None:
+            if lo is not None or hi is not None:
+                raise ValueError("bind_rows: lo / hi need C")
+            _lib.check(fn(self._handle, 0, None, None, None, 0))
+            self._rows = None
+            return
+        if self.rolling_window > 1:
+            raise ValueError("bind_rows: rolling-window models are not supported")
+        Ca, lo, hi, per_stage = check_rows_args(self.H, self.nx, self.nu, C, lo, hi)
+        ptr = lambda a: None if a is None else _as_c_double(a)[1]
+        _lib.check(fn(self._handle, int(Ca.shape[0]), ptr(Ca), ptr(lo), ptr(hi), per_stage))
+        self._rows = dict(C=Ca, lo=lo, hi=hi)
 
     def _bind_rows(self, bind, what, order, xpair, upair, offset):
         """bind_tracking / bind_bounds: check the (B,L,d) device tensors (xpair: the two of width nx, upair: of width nu),

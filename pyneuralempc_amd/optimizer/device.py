@@ -6,11 +6,12 @@ solution.  Same plumbing as ``Slsqp``: problem object from the factory, cold sta
 (``init_with_last_result``), ``prev_result`` for ``NMPC.next`` to split.
 
 Needs the fused device path: a device integrator, a ``QuadraticObjective`` and no extra constraint rows other than one
-``BoxStateConstraint`` (which the solver turns into state bounds); anything else raises ``NotImplementedError`` -- there
-is no CPU fallback."""
+``BoxStateConstraint`` (which the solver turns into state bounds) and any number of ``LinearStageConstraint`` (bound as the
+solver's stage rows for the call); anything else raises ``NotImplementedError`` -- there is no CPU fallback."""
 import numpy as np
 
-from .base import Optimizer
+from ..constraints import BoxStateConstraint, LinearStageConstraint
+from .base import Optimizer, fused_evaluator
 from .slsqp import Slsqp, SlsqpProblemFactory
 
 
@@ -30,7 +31,9 @@ class DeviceSqp(Slsqp):
         du_weight (nu,nu), du_lb / du_ub (nu,) or (H,nu): an input-rate penalty sum_t du_t' du_weight du_t and rate limits on
         du_t = u_t - u_{t-1} (CallbackEngine.bind_rate).  u_{-1} is the first control of the last successful solve -- the one
         NMPC.next's caller applied --, zeros on the first call, or what ``NMPC.next(u_prev=)`` / ``set_u_prev`` gave for the
-        next solve.  Not together with certificate or gain (the library refuses multipliers under a rate binding)."""
+        next solve.  Not together with certificate or gain (the library refuses multipliers under a rate binding).
+        A problem whose constraint list holds LinearStageConstraints is solved inside their rows
+        (CallbackEngine.bind_rows); a ValueError when the optimizer has rate terms, certificate or gain."""
         if (du_weight is not None or du_lb is not None or du_ub is not None) and (certificate or gain):
             raise ValueError("DeviceSqp: du_weight / du_lb / du_ub cannot be combined with certificate=True or gain=True")
         super().__init__(max_iteration=max_iteration, tolerance=tolerance, verbose=verbose,
@@ -56,11 +59,33 @@ class DeviceSqp(Slsqp):
             raise ValueError(f"u_prev must have shape {(int(nu),)}, got {tuple(np.shape(u_prev))}")
         self._u_prev = v
 
+    def _fused_with_rows(self, problem):
+        """(the problem's fused evaluator, None), or -- its constraint list holding LinearStageConstraints next to at most one
+        BoxStateConstraint, which keeps the host glue off the fused path -- (the evaluator of the problem without them, the rows
+        stacked as (C, lo, hi)).  (None, None) when there is no fused path."""
+        fused = getattr(problem, "_fused", None)
+        cons = list(getattr(problem, "constraints_list", None) or [])
+        rows = [c for c in cons if isinstance(c, LinearStageConstraint)]
+        if fused is not None or not rows:
+            return fused, None
+        boxes = [c for c in cons if isinstance(c, BoxStateConstraint)]
+        integ = problem.integrator
+        if len(boxes) + len(rows) != len(cons) or len(boxes) > 1 or not getattr(integ, "on_device", False):
+            return None, None
+        if self.rate is not None or self.certificate or self.gain:
+            raise ValueError("DeviceSqp: a LinearStageConstraint cannot be combined with rate terms, certificate=True or gain=True")
+        from ..objective.quadratic import QuadraticObjective
+        if not isinstance(problem.objective_func, QuadraticObjective):
+            return None, None
+        fused = fused_evaluator(integ, problem.objective_func, boxes[0] if boxes else None)
+        fused.set_parameters(problem.p, problem.tvp)
+        return fused, LinearStageConstraint.stack(rows, int(integ.H), int(integ.model.x_dim) + int(integ.model.u_dim))
+
     def get_factory(self):
         return SlsqpProblemFactory()      # the same problem object: x0, parameters, fused evaluator, initial values
 
     def solve(self, problem, domain_constraint):
-        fused = getattr(problem, "_fused", None)
+        fused, rows = self._fused_with_rows(problem)
         if fused is None:
             raise NotImplementedError("DeviceSqp needs the fused device path: a device integrator, a QuadraticObjective and "
                                       "no extra constraint rows other than one BoxStateConstraint")
@@ -77,6 +102,17 @@ class DeviceSqp(Slsqp):
             opts["mu_init"] = self.warm_mu
         opts.update(self.solver_opts)
         X0 = eng.to_device(np.asarray(problem.get_init_value(), dtype=np.float64).reshape(1, -1))
+        if rows is not None:
+            eng.bind_rows(*rows)
+            try:
+                Z, status, iters = eng.solve(X0, eng.to_device(z0), lb, ub, **opts)
+            finally:
+                eng.bind_rows()
+            self.last_iterations = iters
+            if int(status[0].item()) != 0:
+                return Optimizer.FAIL
+            self.prev_result = Z[0].to("cpu").double().numpy()
+            return Optimizer.SUCCESS
         if self.rate is not None:
             up = np.zeros(eng.nu) if self._u_prev is None else self._u_prev
             eng.bind_rate(u_prev=eng.to_device(up.reshape(1, -1)), **self.rate)
