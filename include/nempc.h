@@ -306,6 +306,17 @@ int nempc_eval(nempc_handle h, int32_t B, const void* Z, const void* X0, void* f
  *   call, not for a captured stream); evaluations on any stream may follow without further ordering.
  *   From then on nempc_eval(..., jac_dense == jac, ...) with at most B problems may write ONLY THE STRUCTURAL NON-ZEROS
  *   (problems beyond the evaluated ones are not touched).  The results are those of the full-matrix path, bit for bit.
+ *   The constant non-zeros -- the -1 of every defect row, the +1 of every box row -- are as fixed as the zeros: the first
+ *   evaluation that reaches a problem of the buffer writes them (one small launch in front of its own, on its stream),
+ *   later ones leave them alone.  (An evaluation on a stream that is being captured before that has happened takes the
+ *   full-matrix path.)
+ *   ORDERING: that fill runs on the stream of the evaluation that issues it.  An evaluation of the same buffer on ANOTHER
+ *   stream skips the constants from then on, so it -- and whoever reads its result -- must be ordered behind that first
+ *   evaluation (an event, or a synchronisation), not only behind the registration.
+ *   GRAPHS: a graph captured from an evaluation into a registered buffer records the launches of that moment -- without
+ *   the zeros, and without the constants once they are in place.  Registering the pointer again (a fresh zero fill),
+ *   nempc_set_box_rows and an unregistration followed by foreign writes invalidate such a graph: a replay would leave the
+ *   buffer without its zeros / constants.  Capture again after any of them.
  *   The one-launch evaluation of the compiled shapes and the assembly launch behind the generic, layered and
  *   wave-per-tile rows do so; a writer that does not (the cooperative kernel's one-launch dense form) writes the full
  *   matrix into a resident buffer as into any other.

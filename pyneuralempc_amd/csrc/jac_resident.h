@@ -6,6 +6,11 @@
 // This table says which pointers are such buffers.  It is small and fixed: a caller that finds it full simply stays on the
 // full-matrix path.  An entry is live while its epoch is the table's; whatever changes m, n or the dense map bumps the
 // epoch, which drops every entry at once (the non-zeros of the old shape would otherwise stay behind as stale values).
+//
+// The constant non-zeros (the -1 of every defect row, the +1 of every box row) are as fixed as the zeros.  A registration
+// leaves the buffer all zero; the first evaluation that finds problems without their constants writes them (one small fill in
+// front of its launches) and says so here: an entry counts the leading problems that have them, and the writers skip those
+// stores like the zeros.  Counted per problem because an evaluation of fewer problems than registered touches only its own.
 #pragma once
 
 namespace nempc {
@@ -17,6 +22,7 @@ struct JacResidentTable {
         const void* ptr = nullptr;
         int B = 0;                  // problems the zero fill covered
         unsigned epoch = 0;
+        int const_B = 0;            // leading problems whose constant entries are in place (<= B)
     };
     Entry slot[kJacResidentSlots];
     unsigned epoch = 1;
@@ -37,14 +43,27 @@ struct JacResidentTable {
         return e && B <= e->B;
     }
 
-    // registers `p` for B problems (a pointer already in the table keeps its slot and takes the new B).
-    // false: the table is full, nothing changed
+    // the leading problems of `p` that hold their constants (0: none, or not registered)
+    int const_count(const void* p) const {
+        const Entry* e = find(p);
+        return e ? e->const_B : 0;
+    }
+
+    // the constants of problems [0, B) of `p` are in place now; never beyond the registered B, never fewer than before
+    void const_filled(const void* p, int B) {
+        for (Entry& e : slot)
+            if (live(e) && e.ptr == p && B > e.const_B) e.const_B = B < e.B ? B : e.B;
+    }
+
+    // registers `p` for B problems, freshly zero-filled: no constants yet (a pointer already in the table keeps its slot
+    // and takes the new B).  false: the table is full, nothing changed
     bool add(const void* p, int B) {
         if (!p || B <= 0) return false;
         Entry* free_slot = nullptr;
         for (Entry& e : slot) {
             if (live(e) && e.ptr == p) {
                 e.B = B;
+                e.const_B = 0;
                 return true;
             }
             if (!live(e) && !free_slot) free_slot = &e;
@@ -53,6 +72,7 @@ struct JacResidentTable {
         free_slot->ptr = p;
         free_slot->B = B;
         free_slot->epoch = epoch;
+        free_slot->const_B = 0;
         return true;
     }
 

@@ -96,6 +96,10 @@ struct FxLayout {   // element offsets inside dynamic LDS, all compile-time
 
 constexpr int FX_ZCOPY = 512;   // elements of Z (the workgroup's problems) parked in LDS for the objective: 2 per thread
 
+// FxArgs::box, read by a pass's epilogue: box rows follow the defect rows; the dense matrix is resident, i.e. its constant
+// -1 / +1 entries are in place like its zeros (fused launch only; one word, so no scalar register more in the epilogue)
+constexpr int FX_BOX_ROWS = 1, FX_BOX_CONST_RESIDENT = 2;
+
 struct FxArgs {   // host-prepared; the fields the first loads need come first
     const void* Z;
     const void* X0;
@@ -106,7 +110,7 @@ struct FxArgs {   // host-prepared; the fields the first loads need come first
     unsigned invH;          // ceil(2^32 / H), 0 for H == 1
     int H, n, m;
     int ident;              // 1: Discret (Phi = x + f), 0: Unity
-    int box;
+    int box;                // FX_BOX_ROWS | FX_BOX_CONST_RESIDENT (below)
     int small_vecs;
     void* g;
     void* tiles;            // may be null in the fused evaluation (nobody asked for the compact tiles)
@@ -659,7 +663,7 @@ __device__ __forceinline__ void fx_pass(const FxCtx<T, WP, NH, TPW, NX, NU>& cx,
             const int t = (int)(r - b * (unsigned)cx.H);
             T* gp = o_g + (size_t)b * a_m + t * NX + i;
             gp[0] = phi - xt;
-            if (a_box) gp[(size_t)cx.H * NX] = xt;
+            if (a_box & FX_BOX_ROWS) gp[(size_t)cx.H * NX] = xt;
             if constexpr (FUSE) {
                 if (o_jac || o_sp) {
                     const int n = cx.n;
@@ -686,10 +690,16 @@ __device__ __forceinline__ void fx_pass(const FxCtx<T, WP, NH, TPW, NX, NU>& cx,
                             for (int jj = 0; jj < NX; ++jj) fx_store_wt(row + (t - 1) * NX + jj, ts[jj]);
                         }
                     }
-                    fx_store_wt(row + t * NX + i, T(-1));
+                    // the row's constants (-1, the box row's +1) belong to the background: a resident matrix holds them
+                    // like its zeros (FX_BOX_CONST_RESIDENT, set exactly when fx_zero_rows saw a null pointer)
+#ifndef NEMPC_EXP_NOCONST      // (timing experiment only)
+                    if (!(a_box & FX_BOX_CONST_RESIDENT)) fx_store_wt(row + t * NX + i, T(-1));
+#endif
 #pragma unroll
                     for (int jj = 0; jj < NU; ++jj) fx_store_wt(row + cx.H * NX + t * NU + jj, ts[NX + jj]);
-                    if (a_box) fx_store_wt(row + (size_t)cx.H * NX * (size_t)n + t * NX + i, T(1));
+#ifndef NEMPC_EXP_NOCONST
+                    if ((a_box & (FX_BOX_ROWS | FX_BOX_CONST_RESIDENT)) == FX_BOX_ROWS) fx_store_wt(row + (size_t)cx.H * NX * (size_t)n + t * NX + i, T(1));
+#endif
                     }
                     if (o_sp) {
                         // the band values of dense row (t, i), in the row's column order: [state block | -1 | control block]
@@ -719,7 +729,7 @@ __device__ __forceinline__ void fx_pass(const FxCtx<T, WP, NH, TPW, NX, NU>& cx,
                                 for (int jj = 0; jj < NU; ++jj) pc[1 + jj] = ts[NX + jj];
                             }
                         }
-                        if (a_box) sp[NX * ROW0 + (cx.H - 1) * NX * ROWT + t * NX + i] = T(1);
+                        if (a_box & FX_BOX_ROWS) sp[NX * ROW0 + (cx.H - 1) * NX * ROWT + t * NX + i] = T(1);
                     }
                 }
             }

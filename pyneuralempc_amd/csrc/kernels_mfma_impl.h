@@ -51,8 +51,8 @@ struct MfmaParams {
     long long* dbg;        // diagnostic builds only (-DNEMPC_STAMPS): per-wave phase stamps of workgroup 0
     // fused evaluation (fixed-shape kernel only): dense Jacobian and objective from the same launch
     bool fuse_obj;         // one-launch evaluation (MfmaRowsPlan::fuse); fuse_jac may be null (no dense matrix)
-    bool jac_resident;     // fuse_jac's structural zeros are in place (nempc_jac_dense_resident): the launch writes the non-zeros
-                           // only.  (Host-side; it sits in fuse_obj's padding -- the kernels that take this struct keep their layout.)
+    bool jac_resident;     // fuse_jac's structural zeros and constants are in place (nempc_jac_dense_resident): the launch writes
+                           // the computed non-zeros only.  (Host-side; it sits in fuse_obj's padding -- the kernels that take this struct keep their layout.)
     void* fuse_jac;
     void* fuse_sparse;     // band-pattern Jacobian values (B, nnz) in nempc_jac_structure order from the row launch (plain models)
     int sp_nnz;

@@ -116,7 +116,7 @@ int launch_coopfx(const MfmaParams& p, const MfmaRowsPlan& plan, hipStream_t s) 
     a.invH = p.H == 1 ? 0u : (unsigned)((0x100000000ull + (unsigned)p.H - 1) / (unsigned)p.H);
     a.H = p.H; a.n = p.gk.n; a.m = p.m;
     a.ident = p.kind == NEMPC_DISCRET ? 1 : 0;
-    a.box = p.box;
+    a.box = (p.box ? FX_BOX_ROWS : 0) | (FUSE && p.jac_resident ? FX_BOX_CONST_RESIDENT : 0);
     a.small_vecs = (p.off.fx_small_elems + VEC - 1) / VEC;
     a.g = p.g; a.tiles = p.tiles;
     a.jac = p.fuse_jac; a.f = p.fuse_f; a.grad = p.fuse_grad; a.P = p.obj; a.p_elems = p_elems; a.oo = p.oo;
@@ -132,10 +132,12 @@ int launch_coopfx(const MfmaParams& p, const MfmaRowsPlan& plan, hipStream_t s) 
     // workgroup i with i + ceil(grid / 2) for the objective and must not wait for the dispatch's own copy of the grid size)
     const unsigned pack = (unsigned)a.tiles_per_wg | ((unsigned)a.tiles_rem << 8) | ((unsigned)a.zp_max << 18) |
                           (a.f ? 1u << 28 : 0u) | (a.grad ? 1u << 29 : 0u) | ((a.tiles || a.jac || a.jac_sp || GN) ? 1u << 30 : 0u) |
-                          (a.box ? 1u << 31 : 0u);
+                          (p.box ? 1u << 31 : 0u);
     // pjac is the pointer the background zeros go to (the non-zeros go to a.jac, read in the epilogue).  A resident matrix
-    // (nempc_jac_dense_resident) holds its zeros already: the kernel is told there is no background to write.  Same kernel,
-    // same registers, no new argument; what is left of the background is the epilogue's vmcnt(0), which then finds only the
+    // (nempc_jac_dense_resident) holds its zeros already, and its constant -1 / +1 entries: the kernel is told there is no
+    // background to write, and the epilogue leaves the constants out (a second bit in a.box, which it reads anyway: keeping
+    // the pointer itself live to the end of the pass cost the sparse contract two spilled scalars).  Same kernel, no new
+    // argument; what is left of the background is the epilogue's vmcnt(0), which then finds only the
     // next pass's input loads (waited for two lines further down anyway) and the previous pass's few stores outstanding.
     void* const bg = FUSE && !p.jac_resident ? a.jac : nullptr;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MT * 64), bytes, s, a.Z, a.X0, a.small, a.wslice, a.P, pack, a.R, a.invH,

@@ -175,9 +175,9 @@ __global__ __launch_bounds__(256) void post_sparse_kernel(int nb_asm, int B, int
     vals[e] = map_value<T>(map[k], tiles + (size_t)b * tile_elems);
 }
 
-// dense contract into a RESIDENT matrix (nempc_jac_dense_resident: its structural zeros are in place): the same flat stream
-// over the structural non-zeros, each value to its place in the problem's dense matrix (pos[k] = row * n + col); the
-// objective on the blocks after them when it is asked for.
+// dense contract into a RESIDENT matrix (nempc_jac_dense_resident: its structural zeros are in place, and so are its constant
+// entries -- jac_constants_kernel): the same flat stream over the structural non-zeros, each value that comes from a tile to
+// its place in the problem's dense matrix (pos[k] = row * n + col); the objective on the blocks after them when it is asked for.
 template <typename T>
 __global__ __launch_bounds__(256) void post_scatter_kernel(int nb_asm, int B, int nnz, unsigned long long magic64, int mn,
                                                            int tile_elems, const int32_t* __restrict__ map,
@@ -194,7 +194,21 @@ __global__ __launch_bounds__(256) void post_scatter_kernel(int nb_asm, int B, in
     if (e >= (unsigned long long)B * nnz) return;
     const unsigned b = (unsigned)__umul64hi(e, magic64);      // e / nnz, exact for e * nnz < 2^64
     const unsigned k = (unsigned)(e - (unsigned long long)b * nnz);
-    jac[(size_t)b * mn + pos[k]] = map_value<T>(map[k], tiles + (size_t)b * tile_elems);
+    const int32_t code = map[k];
+    if (code >= 0) jac[(size_t)b * mn + pos[k]] = tiles[(size_t)b * tile_elems + code];
+}
+
+// The constant entries of problems [b0, b0 + count) of a resident dense matrix, written once (jac_resident.h): -1 at (k, k)
+// of the hx = H nx defect rows, +1 at (hx + k, k) of the box rows.  One lane per (problem, k).
+template <typename T>
+__global__ __launch_bounds__(256) void jac_constants_kernel(int b0, int count, int hx, int n, int mn, int box, T* __restrict__ jac) {
+    const unsigned long long e = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (unsigned long long)count * hx) return;
+    const unsigned b = (unsigned)(e / (unsigned)hx);
+    const unsigned k = (unsigned)(e - (unsigned long long)b * hx);
+    T* const J = jac + (size_t)(b0 + b) * mn;
+    J[(size_t)k * n + k] = T(-1);
+    if (box) J[(size_t)(hx + k) * n + k] = T(1);
 }
 
 template <typename T>
@@ -312,6 +326,18 @@ int launch_post_scatter(Handle& h, int B, const void* tiles, void* jac, const vo
     hipLaunchKernelGGL(post_scatter_kernel<T>, dim3((unsigned)(nb_asm + nb_obj)), dim3(256), 0, s, nb_asm, B, nnz, magic,
                        h.m * h.n, te, h.d_sparse_map.get(), h.d_sparse_pos.get(), (const T*)tiles, (T*)jac, h.cfg.H, h.cfg.nx, h.cfg.nu, o,
                        h.d_obj.as<const T>(), (const T*)Z, (T*)f, (T*)grad);
+    NEMPC_HIP(hipGetLastError());
+    return NEMPC_OK;
+}
+
+int launch_jac_constants(Handle& h, int b0, int b1, void* jac, hipStream_t s) {
+    if (b1 <= b0) return NEMPC_OK;
+    const int hx = h.cfg.H * h.cfg.nx, count = b1 - b0;
+    const dim3 grid((unsigned)(((size_t)count * hx + 255) / 256)), block(256);
+    if (h.cfg.dtype == NEMPC_F64)
+        hipLaunchKernelGGL(jac_constants_kernel<double>, grid, block, 0, s, b0, count, hx, h.n, h.m * h.n, h.box ? 1 : 0, (double*)jac);
+    else
+        hipLaunchKernelGGL(jac_constants_kernel<float>, grid, block, 0, s, b0, count, hx, h.n, h.m * h.n, h.box ? 1 : 0, (float*)jac);
     NEMPC_HIP(hipGetLastError());
     return NEMPC_OK;
 }

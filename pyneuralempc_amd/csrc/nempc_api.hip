@@ -848,7 +848,21 @@ int nempc_eval(nempc_handle hh, int32_t B, const void* Z, const void* X0, void* 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // a resident dense Jacobian (nempc_jac_dense_resident) has its structural zeros in place: the writers below leave them
     static const int resident_on = env_int("NEMPC_JAC_RESIDENT", 1);
-    const bool jres = jac_dense && resident_on && h.jac_resident.resident(jac_dense, B);
+    bool jres = jac_dense && resident_on && h.jac_resident.resident(jac_dense, B);
+    // ... and its constant -1 / +1 entries: problems that lack them get them here, once, in front of the launches that then
+    // skip them (jac_resident.h).  A stream that is being captured would record the fill without running it: such a call
+    // takes the full-matrix path and marks nothing.
+    if (jres && h.jac_resident.const_count(jac_dense) < B) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (s) NEMPC_HIP(hipStreamIsCapturing(s, &cap));      // (the null stream cannot be captured)
+        if (cap != hipStreamCaptureStatusNone) {
+            jres = false;
+        } else {
+            const int b0 = h.jac_resident.const_count(jac_dense);
+            if (int rc0 = launch_jac_constants(h, b0, B, jac_dense, s)) return rc0;
+            h.jac_resident.const_filled(jac_dense, B);
+        }
+    }
     // which kernel writes the dense matrix (nempc_last_dense_writer): the row launch below, or the assembly launch itself
     h.last_dense_writer = DENSE_WRITER_NONE;
     int rc;

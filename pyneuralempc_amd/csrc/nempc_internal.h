@@ -294,7 +294,7 @@ struct RowsOut {
     void *g = nullptr, *tiles = nullptr;    // defects; compact tiles (null with need_tiles: the handle's workspace)
     bool need_tiles = false;                // an assembly launch behind this one reads the tiles
     void *jac = nullptr, *sparse = nullptr, *f = nullptr, *grad = nullptr;
-    bool jac_resident = false;              // jac's structural zeros are in place (nempc_jac_dense_resident)
+    bool jac_resident = false;              // jac's structural zeros and constants are in place (nempc_jac_dense_resident)
     void* stage_out = nullptr;              // RK4 Hessian pipeline: stage records, stage_stride elements each
     int stage_stride = 0;
     void* gn_hvals = nullptr;               // Gauss-Newton tril values with weights gn_w (null = ones) and gn_sigma
@@ -327,7 +327,9 @@ int launch_objective(Handle& h, int B, const void* Z, void* f, void* grad, hipSt
 int launch_objective_tracking(Handle& h, int B, const void* Z, void* f, void* grad, const int* prob, hipStream_t s);
 int launch_assemble_hess_gn(Handle& h, int B, const void* tiles, const void* w, const void* sigma, void* hvals, void* hdense,
                             hipStream_t s);
-// resident: jac's structural zeros are in place (nempc_jac_dense_resident), only the non-zeros are written
+// resident: jac's structural zeros and constant entries are in place (nempc_jac_dense_resident, launch_jac_constants): only
+// the entries that come from the tiles are written
+int launch_jac_constants(Handle& h, int b0, int b1, void* jac, hipStream_t s);   // the -1 / +1 entries of problems [b0, b1)
 int launch_assemble_dense(Handle& h, int B, const void* tiles, void* jac, hipStream_t s, bool resident = false);
 int launch_assemble_sparse(Handle& h, int B, const void* tiles, void* vals, hipStream_t s);
 int launch_post(Handle& h, int B, const void* tiles, void* jac, const void* Z, void* f, void* grad, hipStream_t s,

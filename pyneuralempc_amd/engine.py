@@ -544,7 +544,8 @@ class CallbackEngine:
             self._buffers[key] = buf
             if name == "jac_dense":
                 # the engine's own dense Jacobian is written by nempc_eval of this handle and by nobody else: a resident
-                # buffer (nempc_jac_dense_resident zero-fills it now; the evaluations write the structural non-zeros only).
+                # buffer (nempc_jac_dense_resident zero-fills it now; the first evaluation adds the constant -1 / +1 entries,
+                # and every evaluation writes the computed non-zeros only).
                 # A full table or a failed registration leaves it on the full-matrix path, which is correct as well.
                 fn = getattr(self.lib, "nempc_jac_dense_resident", None)
                 if fn is not None:
@@ -572,8 +573,8 @@ class CallbackEngine:
         f (B,), grad (B,n), g (B,m), jac_dense (B,m,n), jac_tiles (B,H,nx,w*(nx+nu)), jac_sparse (B,nnz_jac).
         Asynchronous on the current torch stream.
         The engine's own output tensors are READ-ONLY for the caller: its jac_dense is a resident buffer whose structural
-        zeros are written once, when it is created, and every evaluation writes the non-zeros only -- whatever a caller
-        writes into it stays there.  Tensors passed through `out` are the caller's: they get the full matrix every call."""
+        zeros and constant -1 / +1 entries are written once, and every evaluation writes the computed non-zeros only --
+        whatever a caller writes into it stays there.  Tensors passed through `out` are the caller's: they get the full matrix every call."""
         B = int(Z.shape[0])
         self._check_in(Z, (B, self.n), "Z")
         self._check_in(X0, (B, self.nx), "X0")
