@@ -11,7 +11,7 @@
 //   couple only (x_{t-1}, u_t), so every QP is still an LQ problem in the linearised dynamics
 //   dx_t = A_t dx_{t-1} + B_t du_t + g_t, solved exactly by one backward Riccati sweep and one forward sweep per
 //   problem (block-tridiagonal KKT, O(H (nx+nu)^3)).  Indefinite control Hessians Quu are handled the DDP way:
-//   the sweep is repeated with a larger Levenberg term (decade steps from 1e-3, at most lq_attempts levels per
+//   the sweep is repeated with a larger Levenberg term (half-decade steps from 1e-3, at most lq_attempts levels per
 //   iteration, tried side by side on lanes of one wave in the per-thread kernel, the first level that goes through is
 //   used: a problem still indefinite then keeps its damping and sits the iteration out, so that the launch does
 //   not wait for it).  Multipliers = Riccati costates of the previous step;

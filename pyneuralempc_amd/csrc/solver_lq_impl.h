@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void solver_lq_kernel(SolverArgs a) {
 
     // Damping levels side by side: a sweep that meets an indefinite pivot has to be repeated with more damping, and the
     // launch waited for the problem in hundreds that needs the third attempt (one sweep is a ~20 us latency chain of one
-    // lane; the levels are known beforehand: decade steps).  `spec` lanes per problem now run the levels of a round at the
+    // lane; the levels are known beforehand: half-decade steps).  `spec` lanes per problem now run the levels of a round at the
     // same time, each into its own region of the problem's block; the FIRST level that goes through is the one used, so
     // the result is what the sequential attempts gave.
     constexpr bool PREF = FIX && NX * (NX + NU) + (NX + NU) * (NX + NU) <= 16;
@@ -463,7 +463,8 @@ __global__ __launch_bounds__(256) void solver_lq_kernel(SolverArgs a) {
             if ((ok >> (jj * ppw + pl)) & 1ull) win = jj;
         if (win >= 0) { any = true; solved = win == aj0; restarts = base + win; }
     }
-    // decade steps from a floor of 1e-3: whenever a sweep of this problem family fails, the damping that lets it through
+    // half-decade steps (reg_raise = sqrt(10); the attempt counts below are whole-decade ones: 1e-3 .. 100 in six) from a floor
+    // of 1e-3: whenever a sweep of this problem family fails, the damping that lets it through
     // is 0.1 .. 100 (NEMPC_SOLVER_STATS), and the whole launch waits for the one problem in hundreds that climbs there --
     // nine attempts from the relaxed value with a floor of 1e-6, six from 1e-3 (the kernel runs 37 us clean, 10 us more
     // per attempt).  Remembering per problem the level that worked last time did not help: the restarting problems are

@@ -143,11 +143,14 @@ def stage_problem(prob, z, x0, lam):
     return dict(A=A, B=B, c=c, W=W, Qs=Qs, Rs=prob.R + prob.R.T, gx=gx, gu=gu, ns=ns)
 
 
-def riccati_step(prob, z, x0, lam, reg, dtype=np.float64):
-    """(dz, lam+) of the same Newton step by one backward and one forward Riccati sweep carried out in `dtype`."""
+def riccati_step(prob, z, x0, lam, reg, dtype=np.float64, sp=None):
+    """(dz, lam+) of the same Newton step by one backward and one forward Riccati sweep carried out in `dtype`.  Raises
+    numpy.linalg.LinAlgError at a pivot of a control Hessian that is not above PIVOT_MIN.  sp: stage_problem(prob, z, x0, lam)
+    where the caller already has it (the damping ladder sweeps the same stages at several reg)."""
     assert prob.box is None
     dtype = np.dtype(dtype).type
-    sp = stage_problem(prob, z, x0, lam)
+    if sp is None:
+        sp = stage_problem(prob, z, x0, lam)
     H, nx, nu, ns = prob.H, prob.nx, prob.nu, sp["ns"]
     A, B, c, W, Qs, Rs, gx, gu = (np.asarray(sp[k], dtype=dtype) for k in ("A", "B", "c", "W", "Qs", "Rs", "gx", "gu"))
     regI = (dtype(reg) * np.eye(nu)).astype(dtype)
@@ -160,6 +163,8 @@ def riccati_step(prob, z, x0, lam, reg, dtype=np.float64):
         qu = gu[t] + B[t].T @ Pc
         Qux = W[t][ns:, :ns] + B[t].T @ PA
         L = np.linalg.cholesky(Quu)              # (raises where the solver would restart with more damping)
+        if not (np.diag(L) ** 2 > PIVOT_MIN).all():
+            raise np.linalg.LinAlgError("pivot not above PIVOT_MIN")
         K = -np.linalg.solve(L.T, np.linalg.solve(L, Qux)).astype(dtype)
         kv = -np.linalg.solve(L.T, np.linalg.solve(L, qu)).astype(dtype)
         Ks[t], ks[t] = K, kv
@@ -189,6 +194,128 @@ def sweep_error(prob, x0, z0, steps, reg, dtype):
         acc += float(np.abs(dz - st["dz"]).max())
         out.append(acc)
     return out
+
+
+# --------------------------------------------------------------------------------------
+# The damping state machine: what the solver does when a control Hessian Quu_t is not positive definite.  The same ladder is
+# written three times on the device (csrc/solver_lq_impl.h, solver_lqw_impl.h, solver_lq_scan_impl.h); this is its
+# restatement.  The constants are the code's:
+#   REG_RAISE, REG_RELAX   csrc/solver.hip, ProcessKnobs::reg_raise / reg_relax (half decades)
+#   REG_FLOOR              csrc/solver_args.h, NEMPC_REG_FLOOR: the first damping level of a restarted sweep
+#   REG_RELAX_FLOOR        csrc/solver_merit_impl.h, solver_merit_body: reg <- max(reg * reg_relax, 1e-9)
+#   PIVOT_MIN              csrc/solver_lq_impl.h: a sweep fails at a Cholesky pivot that is not > 1e-12
+#   LQ_ATTEMPTS            csrc/solver.hip, plan_lq: levels tried per iteration when the caller passes lq_attempts = 0
+# --------------------------------------------------------------------------------------
+REG_RAISE = 3.1622776601683795
+REG_RELAX = 0.31622776601683794
+REG_FLOOR = 1e-3
+REG_RELAX_FLOOR = 1e-9
+PIVOT_MIN = 1e-12
+LQ_ATTEMPTS = 3
+ROBUST_D = {np.float64: 1e-3, np.float32: 5e-2}     # relative move of every level's reg that must not change the winner
+
+
+def damping_levels(reg, attempts, raise_=REG_RAISE, floor=REG_FLOOR):
+    """attempts + 1 values: entry j is the stored `reg` raised j times by reg <- max(reg raise_, floor).  Entries 0 ..
+    attempts - 1 are the levels an iteration may sweep at; the last is what is stored when none of them goes through."""
+    out = [float(reg)]
+    for _ in range(attempts):
+        out.append(max(out[-1] * raise_, floor))
+    return out
+
+
+def winning_level(prob, z, x0, lam, reg, attempts, dtype=np.float64, scale=1.0, sp=None):
+    """The first of `attempts` levels from the stored `reg` whose sweep in `dtype` goes through (riccati_step does not
+    raise), or None.  scale: every level's reg times this (winning_level_is_robust)."""
+    if sp is None:
+        sp = stage_problem(prob, z, x0, lam)
+    for j, r in enumerate(damping_levels(reg, attempts)[:attempts]):
+        try:
+            riccati_step(prob, z, x0, lam, r * scale, dtype, sp=sp)
+        except np.linalg.LinAlgError:
+            continue
+        return j
+    return None
+
+
+def winning_level_is_robust(prob, z, x0, lam, reg, attempts, dtype=np.float64, sp=None):
+    """The same winner with every level's reg scaled by 1 - d and by 1 + d (d = ROBUST_D of the handle's precision).  A pivot
+    moves one for one with reg, so the deciding pivots are about d reg away from zero: the device's rounding cannot
+    decide otherwise."""
+    if sp is None:
+        sp = stage_problem(prob, z, x0, lam)
+    d = ROBUST_D[np.dtype(dtype).type]
+    w = winning_level(prob, z, x0, lam, reg, attempts, dtype, 1.0, sp)
+    return all(winning_level(prob, z, x0, lam, reg, attempts, dtype, s, sp) == w for s in (1.0 - d, 1.0 + d))
+
+
+def damped_replay(prob, x0, z0, iterations, reg0, attempts=LQ_ATTEMPTS, dtype=np.float64):
+    """The solver's iteration with full steps and the damping state machine, from z0 with lam_0 = 0 and the stored reg = reg0.
+    Per iteration: the first of `attempts` levels from the stored reg that sweeps through in `dtype` (the handle's precision;
+    the step itself is the dense float64 one at that level's reg) is taken, that level's reg is stored, and only a step whose
+    level is 0 relaxes it, reg <- max(reg REG_RELAX, REG_RELAX_FLOOR); where none goes through the problem sits the iteration
+    out: z, lam unchanged, stored reg = raised `attempts` times.  One dict per iteration: z, lam (after it), level (None =
+    sat out), reg_used (None = sat out), reg_after, dz (zero where sat out), dmerit (l1-merit change of the full step under
+    pen, 0 where sat out), pen (as in `replay`), robust (winning_level_is_robust), z_before, lam_before."""
+    z = np.array(z0, dtype=np.float64)
+    lam = np.zeros(prob.H * prob.nx)
+    pen, reg = 1.0, float(reg0)
+    out = []
+    for _ in range(iterations):
+        sp = stage_problem(prob, z, x0, lam)
+        levels = damping_levels(reg, attempts)
+        level = winning_level(prob, z, x0, lam, reg, attempts, dtype, 1.0, sp)
+        robust = winning_level_is_robust(prob, z, x0, lam, reg, attempts, dtype, sp)
+        if level is None:
+            reg = levels[attempts]
+            out.append(dict(z=z, lam=lam, level=None, reg_used=None, reg_after=reg, dz=np.zeros(prob.n), dmerit=0.0, pen=pen,
+                            robust=robust, z_before=z, lam_before=lam))
+            continue
+        used = levels[level]
+        dz, lamn, _, _ = newton_step(prob, z, x0, lam, used, diagnostics=False)
+        pen = max(pen, 1.5 * float(np.abs(lamn).max()) + 1e-3)
+        dmerit = l1_merit(prob, z + dz, x0, pen) - l1_merit(prob, z, x0, pen)
+        reg = used if level > 0 else max(used * REG_RELAX, REG_RELAX_FLOOR)
+        out.append(dict(z=z + dz, lam=lamn, level=level, reg_used=used, reg_after=reg, dz=dz, dmerit=dmerit, pen=pen,
+                        robust=robust, z_before=z, lam_before=lam))
+        z, lam = z + dz, lamn
+    return out
+
+
+def sweep_error_damped(prob, x0, rp, dtype):
+    """sweep_error for a damped_replay `rp`: cumulative |riccati_step(dtype) - newton_step(float64)|inf over the steps taken,
+    each at the replay's own iterate, multipliers and reg; an iteration that sat out adds nothing."""
+    acc, out = 0.0, []
+    for st in rp:
+        if st["level"] is not None:
+            dz, _ = riccati_step(prob, st["z_before"], x0, st["lam_before"], st["reg_used"], dtype)
+            acc += float(np.abs(dz - st["dz"]).max())
+        out.append(acc)
+    return out
+
+
+def min_passing_reg(prob, z, x0, lam, dtype=np.float64, rel=1e-9):
+    """The smallest reg at which the sweep in `dtype` goes through, by bisection (0.0 where it does undamped).  Going through
+    is monotone in reg: more damping makes every P_t, and with it every Quu_t, larger in the positive semi-definite order."""
+    sp = stage_problem(prob, z, x0, lam)
+
+    def ok(r):
+        try:
+            riccati_step(prob, z, x0, lam, r, dtype, sp=sp)
+            return True
+        except np.linalg.LinAlgError:
+            return False
+    if ok(0.0):
+        return 0.0
+    hi = 1e-6
+    while not ok(hi):
+        hi *= 10.0
+        assert hi < 1e12
+    lo = hi / 10.0 if hi > 1e-6 else 0.0
+    while hi - lo > rel * hi:
+        mid = 0.5 * (lo + hi)
+        lo, hi = (lo, mid) if ok(mid) else (mid, hi)
+    return hi
 
 
 # --------------------------------------------------------------------------------------

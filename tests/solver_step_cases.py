@@ -118,11 +118,11 @@ def _round(a, dtype):
     return np.asarray(a, dtype=np.float64) if dtype == "float64" else np.asarray(a, dtype=np.float32).astype(np.float64)
 
 
-def objective(nx, nu, H, seed, dtype="float64"):
-    """Non-symmetric Q = I + 0.1 N, R = 0.3 I + 0.03 N, QT = 2 I + 0.1 N (N seeded standard normal), random per-stage xref,
-    uref, cx, cu."""
+def objective(nx, nu, H, seed, dtype="float64", r_diag=0.3):
+    """Non-symmetric Q = I + 0.1 N, R = r_diag I + 0.03 N (0.3; negative in the damped cases), QT = 2 I + 0.1 N (N seeded
+    standard normal), random per-stage xref, uref, cx, cu."""
     rng = np.random.default_rng(seed)
-    ob = dict(Q=np.eye(nx) + 0.1 * rng.normal(size=(nx, nx)), R=0.3 * np.eye(nu) + 0.03 * rng.normal(size=(nu, nu)),
+    ob = dict(Q=np.eye(nx) + 0.1 * rng.normal(size=(nx, nx)), R=r_diag * np.eye(nu) + 0.03 * rng.normal(size=(nu, nu)),
               QT=2.0 * np.eye(nx) + 0.1 * rng.normal(size=(nx, nx)), xref=REF_SCALE * rng.normal(size=(H, nx)),
               uref=REF_SCALE * rng.normal(size=(H, nu)), cx=REF_SCALE * rng.normal(size=(H, nx)), cu=REF_SCALE * rng.normal(size=(H, nu)))
     return {k: _round(v, dtype) for k, v in ob.items()}
@@ -132,7 +132,7 @@ class Case:
     """One shape: the network, the objective, BMAX starts and per-problem oracle Problems."""
 
     def __init__(self, name, nx, nu, hidden, integ, DT, H, kernels, dtype, window=1, forward=True, n_extra=0,
-                 act="linear", seed=0, B=BMAX, scale_b=False, x0_range=0.5, out_scale=0.1):
+                 act="linear", seed=0, B=BMAX, scale_b=False, x0_range=0.5, out_scale=0.1, r_diag=0.3):
         self.name, self.nx, self.nu, self.H, self.integ, self.DT = name, nx, nu, H, integ, DT
         self.kernels, self.dtype, self.window, self.forward, self.n_extra, self.B = kernels, dtype, window, forward, n_extra, B
         n_in = window * (nx + nu) + n_extra
@@ -144,7 +144,7 @@ class Case:
         net.W = [_round(w, dtype) for w in net.W]
         net.b = [_round(b, dtype) for b in net.b]
         self.net = net
-        self.obj = objective(nx, nu, H, seed + 100, dtype)
+        self.obj = objective(nx, nu, H, seed + 100, dtype, r_diag)
         rng = np.random.default_rng(seed + 200)
         self.X0 = _round(rng.uniform(-x0_range, x0_range, size=(B, nx)), dtype)
         self.extra = _round(0.5 * rng.normal(size=(B, H, n_extra)), dtype) if n_extra else None
@@ -198,7 +198,7 @@ def nl_case(name):
 
 # (seeds at which the REFERENCE clears both gates of (b) for all 8 problems and all three steps; of the seeds 0..7 the 2/1
 #  Discret network clears them at 1, 2 and 6 -- at the others a reference step meets an indefinite reduced Hessian or raises
-#  the merit, which is the damped / shortened territory these tests leave out)
+#  the merit, which is the damped / shortened territory test (b) leaves out; the damped part is cases (e), (f), (g) below)
 NL_SEEDS = {"2x1_h20": 1, "2x1_h63": 1}
 
 
@@ -387,4 +387,189 @@ def soc_reference(name):
         cands += [(f"half^{k}", z0 + 2.0 ** -k * dz) for k in range(1, MAX_LINESEARCH + 1)] + [("start", z0)]
         out.append(dict(z0=z0, dz=dz, eig=eig, pen=pen, cands=cands, tol=step_tolerance(float(np.abs(dzr - dz).max()), z0 + dz),
                         raises=kkt.l1_merit(prob, z0 + dz, x0, pen) > kkt.l1_merit(prob, z0, x0, pen)))
+    return out
+
+
+# ---- (e) one damped step of an indefinite QP: the rows of QP_ROWS below with R = DAMPED_R_DIAG I + 0.03 N.  With lam0 = 0 and a
+# linear network Quu_t does not depend on the problem: lambda, the smallest reg at which the sweep goes through (bisection
+# on the reference, problem 0, the handle's precision), is one number per row, and reg0 = lambda sqrt(10)^(0.5 - k*) puts level
+# k* half a rung above it and level k* - 1 half a rung below.  lambda per row, from the CPU (the horizons of a row agree to
+# five digits):
+#   2x1_discret H=20, 31, 63  0.3177    6x3_rk4 0.4880     3x2_unity 0.3822     roll3_fwd 0.3186    12x5_discret 0.4188
+#   20x4_discret 0.4188       40x10_discret 0.5001         70x3_discret 0.5479  2x1_fp32 0.3177     40x10_fp32 0.5001
+#   64x8_fp32 0.3692
+# (name, H): the lq kernels taken there -- those of the row's QP_ROWS entry; at 2/1 H = 31 and 63 thread and scan, where the
+# scan fits 2 and 1 levels side by side (3 at H = 20).
+DAMPED_R_DIAG = -0.15
+DAMPED_QP = {
+    ("2x1_discret", 20): QP_ROWS["2x1_discret"][6], ("2x1_discret", 31): ("thread", "scan"), ("2x1_discret", 63): ("thread", "scan"),
+    ("6x3_rk4", 8): QP_ROWS["6x3_rk4"][6], ("3x2_unity", 7): QP_ROWS["3x2_unity"][6], ("roll3_fwd", 10): QP_ROWS["roll3_fwd"][6],
+    ("12x5_discret", 4): QP_ROWS["12x5_discret"][6], ("20x4_discret", 6): QP_ROWS["20x4_discret"][6],
+    ("40x10_discret", 3): QP_ROWS["40x10_discret"][6], ("70x3_discret", 2): QP_ROWS["70x3_discret"][6],
+    ("2x1_fp32", 20): QP_ROWS["2x1_fp32"][6], ("40x10_fp32", 3): QP_ROWS["40x10_fp32"][6], ("64x8_fp32", 1): QP_ROWS["64x8_fp32"][6],
+}
+DAMPED_KSTAR = (1, 2, 4)            # the level that wins, counted from the reg the solve is given
+DAMPED_ATTEMPTS = (1, 3, 5)         # lq_attempts; with 5 and three levels side by side k* = 4 wins in the second round
+DAMPED_SMALL_B = (1, 2, 3)          # at (k* = 2, lq_attempts = 3); every other combination at B = BMAX
+
+
+def iterations_needed(kstar, attempts):
+    """The iteration at which level k* of the ladder is reached when every iteration tries `attempts` levels."""
+    return kstar // attempts + 1
+
+
+@functools.lru_cache(maxsize=None)
+def damped_qp_case(name, H):
+    nx, nu, hidden, integ, DT, _, _, dtype, window, forward, n_extra = QP_ROWS[name]
+    return Case(name, nx, nu, hidden, integ, DT, H, DAMPED_QP[(name, H)], dtype, window, forward, n_extra, act="linear",
+                seed=QP_SEED, r_diag=DAMPED_R_DIAG)
+
+
+@functools.lru_cache(maxsize=None)
+def damped_qp_lambda(name, H):
+    case = damped_qp_case(name, H)
+    return kkt.min_passing_reg(case.problem(0), case.start(0), case.X0[0], np.zeros(H * case.nx), np_dtype(case))
+
+
+@functools.lru_cache(maxsize=None)
+def damped_qp_reference(name, H, kstar):
+    """dict(reg0: what the solve is given, reg_k: level k* of its ladder, probs: per problem (z0, dz at reg_k, lam+,
+    tolerance, sweep error e at reg_k in the handle's precision, dmerit of the full step))."""
+    case = damped_qp_case(name, H)
+    reg0 = damped_qp_lambda(name, H) * kkt.REG_RAISE ** (0.5 - kstar)
+    reg_k = kkt.damping_levels(reg0, kstar)[kstar]
+    lam0 = np.zeros(H * case.nx)
+    probs = []
+    for b in range(case.B):
+        prob, x0, z0 = case.problem(b), case.X0[b], case.start(b)
+        dz, lam, _, _ = kkt.newton_step(prob, z0, x0, lam0, reg_k, diagnostics=False)
+        dzr, _ = kkt.riccati_step(prob, z0, x0, lam0, reg_k, np_dtype(case))
+        e = float(np.abs(dzr - dz).max())
+        pen = max(1.0, 1.5 * float(np.abs(lam).max()) + 1e-3)
+        dmerit = kkt.l1_merit(prob, z0 + dz, x0, pen) - kkt.l1_merit(prob, z0, x0, pen)
+        probs.append((z0, dz, lam, step_tolerance(e, z0 + dz), e, dmerit))
+    return dict(reg0=reg0, reg_k=reg_k, probs=probs)
+
+
+# the relaxation rule: (e) rows and kernels at lq_attempts = 1 (sit, sit, step, sit, step from k* = 2) ...
+RELAX_ROWS = {("2x1_discret", 20): ("thread", "scan"), ("6x3_rk4", 8): ("wave",), ("12x5_discret", 4): ("thread",),
+              ("2x1_fp32", 20): ("wave",)}
+RELAX_KSTAR, RELAX_BUDGETS, RELAX_B = 2, 5, 4
+
+
+@functools.lru_cache(maxsize=None)
+def relax_reference(name, H, attempts=1, kstar=RELAX_KSTAR, budgets=RELAX_BUDGETS):
+    """Per problem (of the first RELAX_B): (damped_replay over `budgets` iterations from reg0 of (e) at k*, cumulative sweep
+    error)."""
+    case = damped_qp_case(name, H)
+    reg0 = damped_qp_reference(name, H, kstar)["reg0"]
+    out = []
+    for b in range(RELAX_B):
+        prob, x0 = case.problem(b), case.X0[b]
+        rp = kkt.damped_replay(prob, x0, case.start(b), budgets, reg0, attempts, np_dtype(case))
+        out.append((rp, kkt.sweep_error_damped(prob, x0, rp, np_dtype(case))))
+    return reg0, out
+
+
+# ---- (f) mixed levels inside one launch: tanh networks at the first step (lam0 = 0: the blocks are zero and Quu_t = R + R' + reg
+# + B_t' P B_t varies with the problem through B_t), output layer not scaled down, X0 in +-1, B = 16, seed 0, fp64.
+# name: (nx, nu, hidden, integrator, DT, H, lq kernels, diagonal of R, reg0)
+MIXED_ROWS = {
+    "2x1_h20": (2, 1, [64, 64], "discret", 1.0, 20, ("thread", "wave", "scan", "auto"), -0.15, 0.012),
+    "12x5_h4": (12, 5, [16], "discret", 1.0, 4, ("thread", "wave"), -0.3, 0.0658),
+    "20x4_h6": (20, 4, [24], "discret", 1.0, 6, ("thread", "wave"), -0.3, 0.0475),
+}
+MIXED_ATTEMPTS = (5, 3)
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_case(name):
+    nx, nu, hidden, integ, DT, H, kernels, r_diag, _ = MIXED_ROWS[name]
+    return Case(name, nx, nu, hidden, integ, DT, H, kernels, "float64", act="tanh", seed=0, B=BMAX, x0_range=1.0, out_scale=1.0,
+                r_diag=r_diag)
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_reference(name):
+    """Per problem: z0, level (the first of MIXED_ATTEMPTS[0] = 5 levels from reg0 that sweeps through, None if none),
+    robust, reg_k, dz (the dense step at reg_k), tol, raises (the full step raises the l1 merit), cands: [(label, point)] --
+    the full step, z0 + 2^-j dz for j = 1 .. MAX_LINESEARCH, and z0; all from the problem's own winning level."""
+    case = mixed_case(name)
+    reg0 = MIXED_ROWS[name][8]
+    lam0 = np.zeros(case.H * case.nx)
+    out = []
+    for b in range(case.B):
+        prob, x0, z0 = case.problem(b), case.X0[b], case.start(b)
+        sp = kkt.stage_problem(prob, z0, x0, lam0)
+        level = kkt.winning_level(prob, z0, x0, lam0, reg0, MIXED_ATTEMPTS[0], sp=sp)
+        robust = kkt.winning_level_is_robust(prob, z0, x0, lam0, reg0, MIXED_ATTEMPTS[0], sp=sp)
+        r = dict(z0=z0, level=level, robust=robust, lam_min=kkt.min_passing_reg(prob, z0, x0, lam0))
+        if level is not None:
+            reg_k = kkt.damping_levels(reg0, level)[level]
+            dz, lam, _, _ = kkt.newton_step(prob, z0, x0, lam0, reg_k, diagnostics=False)
+            dzr, _ = kkt.riccati_step(prob, z0, x0, lam0, reg_k, np.float64, sp=sp)
+            pen = max(1.0, 1.5 * float(np.abs(lam).max()) + 1e-3)
+            cands = [("full", z0 + dz)] + [(f"half^{j}", z0 + 2.0 ** -j * dz) for j in range(1, MAX_LINESEARCH + 1)] + [("start", z0)]
+            r.update(reg_k=reg_k, dz=dz, tol=step_tolerance(float(np.abs(dzr - dz).max()), z0 + dz), cands=cands,
+                     raises=kkt.l1_merit(prob, z0 + dz, x0, pen) >= kkt.l1_merit(prob, z0, x0, pen))
+        out.append(r)
+    return out
+
+
+# ---- (g) several iterations with the real state machine: the tanh 2/1 network of (b) (output layer times 0.1, X0 in +-0.5),
+# default reg, default 3 attempts, 4 iterations, at seeds where the multipliers of the first step make a control Hessian
+# indefinite: the problem then sits out while reg climbs 1e-9 -> 1e-2 -> 0.316 through the floor and takes a damped step.
+CLIMB_SEEDS = (5, 7)
+CLIMB_ITERATIONS, CLIMB_B, CLIMB_POOL = 4, 8, 32
+CLIMB_KERNELS = ("thread", "wave", "scan", "auto")
+
+
+@functools.lru_cache(maxsize=None)
+def climb_case(seed):
+    """(case of CLIMB_B problems, per problem (damped_replay, cumulative sweep error)): of a seeded pool of CLIMB_POOL starts
+    the first CLIMB_B whose replay is robust at every iteration and whose every taken step lowers the l1 merit -- of which
+    at most CLIMB_B - 2 may be problems that restart: at seed 5 the first eight such starts all sit out after their first
+    step (the pool's 18 and 21 are its first that never restart), at seed 7 the cap changes nothing."""
+    nx, nu, hidden, integ, DT, H = 2, 1, [64, 64], "discret", 1.0, 20
+    pool = Case(f"climb{seed}", nx, nu, hidden, integ, DT, H, CLIMB_KERNELS, "float64", act="tanh", seed=seed, B=CLIMB_POOL,
+                scale_b=True)
+    keep, ref, n_restarting = [], [], 0
+    for b in range(pool.B):
+        prob, x0 = pool.problem(b), pool.X0[b]
+        rp = kkt.damped_replay(prob, x0, pool.start(b), CLIMB_ITERATIONS, REG, kkt.LQ_ATTEMPTS)
+        restarts = any(s["level"] != 0 for s in rp)
+        if restarts and n_restarting == CLIMB_B - 2:
+            continue
+        if all(s["robust"] for s in rp) and all(s["dmerit"] < 0.0 for s in rp if s["level"] is not None):
+            n_restarting += restarts
+            keep.append(b)
+            ref.append((rp, kkt.sweep_error_damped(prob, x0, rp, np.float64)))
+        if len(keep) == CLIMB_B:
+            break
+    assert len(keep) == CLIMB_B, keep
+    pool.X0, pool.B, pool.kept = pool.X0[keep].copy(), CLIMB_B, tuple(keep)
+    return pool, ref
+
+
+def climbed(rp):
+    """The replay sat out at least once and later took a damped step."""
+    sat = [i for i, s in enumerate(rp) if s["level"] is None]
+    return bool(sat) and any(s["level"] is not None and s["reg_used"] >= kkt.REG_FLOOR for s in rp[sat[0] + 1:])
+
+
+# ... and the guard of the rule: the tanh 2/1 network of (f) with lq_attempts = 2.  At GUARD_REG0 the first step of problems
+# 4, 5, 7, 8, 9, 13 and 14 goes through at level 1, and with that step's multipliers in the blocks their second sweep needs level
+# 1 again from the reg the first step stored.  Had the acceptance of the first step relaxed the reg (it must not: the
+# opening sweep restarted), both levels of the second iteration would fail and the problem would sit out.
+GUARD_REG0, GUARD_ATTEMPTS = 0.0783, 2
+
+
+@functools.lru_cache(maxsize=None)
+def guard_reference():
+    case = mixed_case("2x1_h20")
+    out = []
+    for b in range(case.B):
+        prob, x0 = case.problem(b), case.X0[b]
+        rp = kkt.damped_replay(prob, x0, case.start(b), 2, GUARD_REG0, GUARD_ATTEMPTS)
+        out.append((rp, kkt.sweep_error_damped(prob, x0, rp, np.float64)))
     return out

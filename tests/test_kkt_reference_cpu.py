@@ -4,7 +4,10 @@ The GPU tests in tests/test_gpu_solver_steps.py hold the solver's steps against 
 to a tolerance derived from `riccati_step`; here those four agree with each other, with the KKT conditions and with SciPy
 SLSQP on the oracle's callbacks, on the very shapes the GPU tests use.  The size formula that predicts the solver's LQ plan
 (solver_step_cases.lds_bytes) is held against the figures the wide rows were chosen by, and the recursion of the
-second-order correction (csrc/solver_soc_impl.h) passes a sanitized stand-alone host program."""
+second-order correction (csrc/solver_soc_impl.h) passes a sanitized stand-alone host program.  The damping state machine
+(damping_levels / winning_level / damped_replay) is worked by hand on a scalar problem, and every condition the damped GPU
+cases (e), (f), (g) stand on is asserted from the reference: lambda per row and the targeted winner in the handle's precision,
+level counts and robustness, kept-problem counts."""
 import os
 import re
 import shutil
@@ -226,3 +229,183 @@ def test_the_correction_cases_reject_the_full_step_and_keep_their_candidates_apa
         d = np.abs(P[:, None, :] - P[None, :, :]).max(axis=2) + np.eye(len(P)) * 1e300
         assert d.min() > 1e3 * r["tol"], (b, d.min(), r["tol"])
     assert helped >= 1
+
+
+# --------------------------------------------------------------------------------------
+# The damping state machine (kkt.damping_levels / winning_level / damped_replay) and what the damped GPU cases stand on
+# --------------------------------------------------------------------------------------
+def _scalar_problem():
+    """One state, one control, H = 2, x+ = x + u (one linear layer), f = x_1^2 + x_2^2 - 1.2 (u_1^2 + u_2^2): by hand
+    P_1 = 2, Quu_1 = reg - 0.4, P_0 = 4 - 4 / (reg - 0.4), Quu_0 = reg + 1.6 - 4 / (reg - 0.4); both pivots are positive iff
+    reg^2 + 1.2 reg - 4.64 > 0, i.e. reg > lambda = (sqrt(20) - 1.2) / 2 = 1.63607."""
+    from oracle import nempc_oracle as orc
+    net = orc.MLP([np.array([[0.0], [1.0]])], [np.zeros(1)], ["linear"])
+    prob = orc.Problem(net, 2, 1, 1, orc.DISCRET, 1.0, Q=[[1.0]], R=[[-1.2]], QT=[[1.0]])
+    x0 = np.array([0.7])
+    return prob, x0, orc.cold_start(x0, 2, 1), (np.sqrt(20.0) - 1.2) / 2.0
+
+
+def test_the_damping_ladder_and_its_replay_on_a_problem_worked_by_hand():
+    r10 = np.sqrt(10.0)
+    assert kkt.REG_RAISE == pytest.approx(r10, rel=1e-15) and kkt.REG_RELAX == pytest.approx(1.0 / r10, rel=1e-15)
+    np.testing.assert_allclose(kkt.damping_levels(1e-9, 3), [1e-9, 1e-3, 1e-3 * r10, 1e-2], rtol=1e-14)     # through the floor
+    np.testing.assert_allclose(kkt.damping_levels(0.1, 4), [0.1, 0.1 * r10, 1.0, r10, 10.0], rtol=1e-14)
+    assert kkt.damping_levels(0.5, 0) == [0.5]
+    prob, x0, z0, lam_min = _scalar_problem()
+    lam0 = np.zeros(2)
+    assert kkt.min_passing_reg(prob, z0, x0, lam0) == pytest.approx(lam_min, rel=1e-8)
+    for reg, passes in ((lam_min * 0.999, False), (lam_min * 1.001, True), (0.41, False), (0.39, False)):
+        if passes:
+            kkt.riccati_step(prob, z0, x0, lam0, reg)
+        else:
+            with pytest.raises(np.linalg.LinAlgError):
+                kkt.riccati_step(prob, z0, x0, lam0, reg)
+    # from 0.1 the levels are 0.1, 0.316, 1, 3.16, 10: the first above lambda = 1.636 is level 3
+    assert kkt.winning_level(prob, z0, x0, lam0, 0.1, 5) == 3 and kkt.winning_level(prob, z0, x0, lam0, 0.1, 4) == 3
+    assert kkt.winning_level(prob, z0, x0, lam0, 0.1, 3) is None
+    assert kkt.winning_level(prob, z0, x0, lam0, 2.0, 1) == 0
+    assert kkt.winning_level_is_robust(prob, z0, x0, lam0, 0.1, 5)
+    # a ladder with a level within d = 1e-3 of lambda is not robust: level 1 of reg sits at lambda (1 + 5e-4)
+    assert not kkt.winning_level_is_robust(prob, z0, x0, lam0, lam_min * (1.0 + 5e-4) / r10, 3)
+    # two attempts per iteration: sit out (0.1, 0.316 fail; stored 1), then level 1 (1 fails, 3.16 goes through; stored 3.16,
+    # not relaxed: the sweep restarted), then level 0 at 3.16 (the network is linear: lambda stays) and the relaxation to 1
+    rp = kkt.damped_replay(prob, x0, z0, 3, 0.1, attempts=2)
+    assert [s["level"] for s in rp] == [None, 1, 0] and all(s["robust"] for s in rp)
+    assert rp[0]["reg_used"] is None and rp[0]["reg_after"] == pytest.approx(1.0, rel=1e-14)
+    assert np.array_equal(rp[0]["z"], z0) and np.array_equal(rp[0]["lam"], lam0) and not rp[0]["dz"].any() and rp[0]["pen"] == 1.0
+    assert rp[1]["reg_used"] == pytest.approx(r10, rel=1e-14) and rp[1]["reg_after"] == rp[1]["reg_used"]
+    dz, lamn, _, _ = kkt.newton_step(prob, z0, x0, lam0, rp[1]["reg_used"])
+    assert np.array_equal(rp[1]["z"], z0 + dz) and np.array_equal(rp[1]["lam"], lamn)
+    assert rp[1]["pen"] == max(1.0, 1.5 * np.abs(lamn).max() + 1e-3)
+    assert rp[2]["reg_used"] == rp[1]["reg_after"] and rp[2]["reg_after"] == pytest.approx(1.0, rel=1e-14)
+    # five attempts: level 3 at once; one attempt from above lambda: level 0 and the relaxation, floored at 1e-9
+    one = kkt.damped_replay(prob, x0, z0, 1, 0.1, attempts=5)[0]
+    assert one["level"] == 3 and one["reg_after"] == pytest.approx(r10, rel=1e-14) and np.array_equal(one["z"], rp[1]["z"])
+    assert kkt.damped_replay(prob, x0, z0, 1, 2.0, attempts=1)[0]["reg_after"] == pytest.approx(2.0 / r10, rel=1e-14)
+    # out of attempts three times in a row: the stored reg keeps climbing, 1e-9 -> 1e-3 -> 3.16e-3 -> 1e-2
+    climb = kkt.damped_replay(prob, x0, z0, 3, 1e-9, attempts=1)
+    assert [s["level"] for s in climb] == [None] * 3
+    np.testing.assert_allclose([s["reg_after"] for s in climb], [1e-3, 1e-3 * r10, 1e-2], rtol=1e-14)
+    assert kkt.sweep_error_damped(prob, x0, rp, np.float64)[0] == 0.0
+    e = kkt.sweep_error_damped(prob, x0, rp, np.float32)
+    assert e[0] == 0.0 and 0.0 < e[1] <= e[2] < 1e-5
+
+
+# lambda per (e) row as solver_step_cases records it (the horizons of 2x1_discret agree to five digits)
+DAMPED_LAMBDA = {"2x1_discret": 0.3177, "6x3_rk4": 0.4880, "3x2_unity": 0.3822, "roll3_fwd": 0.3186, "12x5_discret": 0.4188,
+                 "20x4_discret": 0.4188, "40x10_discret": 0.5001, "70x3_discret": 0.5479, "2x1_fp32": 0.3177, "40x10_fp32": 0.5001,
+                 "64x8_fp32": 0.3692}
+
+
+@pytest.mark.parametrize("name,H", list(sc.DAMPED_QP))
+def test_the_targeted_level_wins_on_every_damped_qp_row(name, H):
+    """(e): lambda is the recorded one and the same for two problems (Quu does not depend on the problem); from reg0 =
+    lambda sqrt(10)^(0.5 - k*) the levels below k* fail and k* goes through, robustly, in the handle's precision; no reg0
+    meets the floor; the dense full step at reg_k* lowers the l1 merit for all 16 problems."""
+    case = sc.damped_qp_case(name, H)
+    dt = sc.np_dtype(case)
+    lam0 = np.zeros(H * case.nx)
+    lam_min = sc.damped_qp_lambda(name, H)
+    assert lam_min == pytest.approx(DAMPED_LAMBDA[name], abs=1e-4)
+    assert kkt.min_passing_reg(case.problem(1), case.start(1), case.X0[1], lam0, dt) == pytest.approx(lam_min, rel=1e-6)
+    assert set(case.kernels) <= set(sc.QP_ROWS[name][6])
+    worst_tol = 0.0
+    for ks in sc.DAMPED_KSTAR:
+        ref = sc.damped_qp_reference(name, H, ks)
+        assert ref["reg0"] > 5.0 * kkt.REG_FLOOR and ref["reg_k"] == pytest.approx(lam_min * np.sqrt(np.sqrt(10.0)), rel=1e-12)
+        for b in range(3):
+            prob, x0, z0 = case.problem(b), case.X0[b], case.start(b)
+            assert kkt.winning_level(prob, z0, x0, lam0, ref["reg0"], 5, dt) == ks
+            assert kkt.winning_level_is_robust(prob, z0, x0, lam0, ref["reg0"], 5, dt)
+            assert kkt.winning_level(prob, z0, x0, lam0, ref["reg0"], ks, dt) is None
+        assert all(p[5] < 0.0 for p in ref["probs"])
+        worst_tol = max(worst_tol, max(p[3] for p in ref["probs"]))
+        es = [p[4] for p in ref["probs"]]
+        assert max(es) < (1e-11 if case.dtype == "float64" else 1e-5)
+    for ks, at in ((1, 1), (2, 1), (4, 1), (1, 3), (2, 3), (4, 3), (4, 5)):
+        assert sc.iterations_needed(ks, at) == {(1, 1): 2, (2, 1): 3, (4, 1): 5, (1, 3): 1, (2, 3): 1, (4, 3): 2, (4, 5): 1}[(ks, at)]
+    print(f"[damped qp {name} H={H}] lambda {lam_min:.4f}; sweep error {min(es):.1e} .. {max(es):.1e}; largest tolerance {worst_tol:.1e}")
+
+
+@pytest.mark.parametrize("name,H", list(sc.RELAX_ROWS))
+def test_the_relaxation_rows_sit_sit_step_sit_step(name, H):
+    """One attempt per iteration from k* = 2: the reference sits out twice, steps, sits out (the relaxed reg is half a rung
+    under lambda) and steps again; both steps lower the l1 merit."""
+    reg0, ref = sc.relax_reference(name, H)
+    for rp, cum_e in ref:
+        assert [s["level"] for s in rp] == [None, None, 0, None, 0] and all(s["robust"] for s in rp)
+        assert rp[2]["dmerit"] < 0.0 and rp[4]["dmerit"] < 0.0
+        assert rp[3]["reg_after"] == pytest.approx(rp[2]["reg_used"], rel=1e-12) and rp[2]["reg_after"] < sc.damped_qp_lambda(name, H)
+    print(f"[relax {name} H={H}] largest tolerance after step 1 / step 2: "
+          f"{max(sc.step_tolerance(e[2], rp[2]['z']) for rp, e in ref):.1e} / {max(sc.step_tolerance(e[4], rp[4]['z']) for rp, e in ref):.1e}")
+
+
+def test_the_guard_case_has_problems_whose_second_sweep_needs_the_unrelaxed_reg():
+    """Two attempts per iteration on the tanh 2/1 network of (f): at least four problems step at level 1 twice, robustly and
+    downhill -- and with the reg their first step stored relaxed by sqrt(10) they would find no level in the second
+    iteration."""
+    case = sc.mixed_case("2x1_h20")
+    ref = sc.guard_reference()
+    twice = [b for b, (rp, _) in enumerate(ref) if [s["level"] for s in rp] == [1, 1] and all(s["robust"] for s in rp)
+             and all(s["dmerit"] < 0.0 for s in rp)]
+    assert len(twice) >= 4, twice
+    for b in twice:
+        s = ref[b][0][1]
+        assert kkt.winning_level(case.problem(b), s["z_before"], case.X0[b], s["lam_before"], ref[b][0][0]["reg_after"] * kkt.REG_RELAX,
+                                 sc.GUARD_ATTEMPTS) is None
+        assert np.abs(s["dz"]).max() > 1e6 * sc.step_tolerance(ref[b][1][1], s["z"])
+    print(f"[guard] problems {twice}; levels {[[s['level'] for s in rp] for rp, _ in ref]}")
+
+
+MIXED_LEVELS = {"2x1_h20": {1: 2, 2: 7, 3: 7}, "12x5_h4": {2: 10, 3: 6}, "20x4_h6": {2: 9, 3: 7}}
+MIXED_NOT_ROBUST = {"2x1_h20": [], "12x5_h4": [], "20x4_h6": [6]}
+MIXED_RAISES = {"2x1_h20": 7, "12x5_h4": 0, "20x4_h6": 6}
+
+
+@pytest.mark.parametrize("name", list(sc.MIXED_ROWS))
+def test_the_mixed_level_cases_mix_their_levels(name):
+    """(f): at least two winning levels are each taken by at least two robust problems, at most 2 of 16 are not robust; the
+    level counts, the problems that are not robust and the number whose full step raises the l1 merit are the recorded ones;
+    a problem's winning level is the one its own lambda (bisection) predicts; the candidates of a problem whose step raises
+    the merit are more than a thousand tolerances apart."""
+    ref = sc.mixed_reference(name)
+    reg0 = sc.MIXED_ROWS[name][8]
+    levels = [r["level"] for r in ref if r["robust"]]
+    assert sum(levels.count(lv) >= 2 for lv in set(levels) if lv is not None) >= 2
+    assert sum(not r["robust"] for r in ref) <= 2
+    assert {lv: [r["level"] for r in ref].count(lv) for lv in set(r["level"] for r in ref)} == MIXED_LEVELS[name]
+    assert [b for b, r in enumerate(ref) if not r["robust"]] == MIXED_NOT_ROBUST[name]
+    assert sum(r["raises"] for r in ref) == MIXED_RAISES[name]
+    ladder = kkt.damping_levels(reg0, sc.MIXED_ATTEMPTS[0])
+    for r in ref:
+        assert r["level"] == next(j for j, v in enumerate(ladder) if v >= r["lam_min"])
+        if r["raises"]:
+            P = np.stack([p for _, p in r["cands"]])
+            d = np.abs(P[:, None, :] - P[None, :, :]).max(axis=2) + np.eye(len(P)) * 1e300
+            assert d.min() > 1e3 * r["tol"], (d.min(), r["tol"])
+    print(f"[mixed {name}] lambda {min(r['lam_min'] for r in ref):.3f} .. {max(r['lam_min'] for r in ref):.3f}; levels "
+          f"{[r['level'] for r in ref]}; largest tolerance {max(r['tol'] for r in ref):.1e}")
+
+
+CLIMB_KEPT = {5: (0, 1, 6, 7, 9, 12, 18, 21), 7: (0, 1, 2, 3, 4, 5, 7, 8)}
+
+
+@pytest.mark.parametrize("seed", sc.CLIMB_SEEDS)
+def test_the_climbing_cases_climb(seed):
+    """(g): per seed at least 2 of the 8 kept problems sat out and then took a damped step within the 4 iterations, at least
+    2 never restarted; every kept replay is robust at every iteration and every taken step lowers the l1 merit; a climbing
+    problem's reg goes 1e-9 -> 1e-2 -> 0.316 over its two sat-out iterations and its damped step has the first step's
+    multipliers in the blocks."""
+    case, ref = sc.climb_case(seed)
+    assert case.kept == CLIMB_KEPT[seed] and len(ref) == sc.CLIMB_B
+    climbing = [b for b, (rp, _) in enumerate(ref) if sc.climbed(rp)]
+    assert len(climbing) >= 2 and sum(all(s["level"] == 0 for s in rp) for rp, _ in ref) >= 2
+    for rp, _ in ref:
+        assert all(s["robust"] for s in rp) and all(s["dmerit"] < 0.0 for s in rp if s["level"] is not None)
+    for b in climbing:
+        rp = ref[b][0]
+        assert [s["level"] for s in rp[:3]] == [0, None, None] and rp[3]["level"] in (1, 2)
+        np.testing.assert_allclose([s["reg_after"] for s in rp[:3]], [1e-9, 1e-2, 10.0 ** -0.5], rtol=1e-12)
+        assert np.array_equal(rp[3]["lam_before"], rp[0]["lam"]) and np.abs(rp[0]["lam"]).max() > 0.1
+    print(f"[climb seed {seed}] levels {[[s['level'] for s in rp] for rp, _ in ref]}; largest tolerance "
+          f"{max(sc.step_tolerance(e[-1], rp[-1]['z']) for rp, e in ref):.1e}")
